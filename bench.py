@@ -8,7 +8,10 @@ WeightedMeanReadout + LBM, InfoNCE, backward, Adam(amsgrad) -- exactly trainer/t
 N > 1: one process per GPU (torch.distributed / RCCL), each rank its own batch (weak scaling), one flat gradient
 all-reduce per step.
 
-Prints ONE JSON line (rank 0) with value = total egonet-edges/s over all ranks, plus
+Prints ONE JSON line (rank 0) with value = total egonet-edges/s over all ranks and ms_per_step = one timed step.  A plain run does only
+that: set-up, warm-up, the --steps timed steps, the outputs of the last one if --dump-outputs DIR is given, the line.  With --full the
+same run then also measures and checks everything below, and the line carries
+  sanity        -- the timed route's loss against the plain route's (config.sanity), before anything is timed
   roofline      -- the dominant kernel by time in an instrumented pass (HIP events on the launch stream, per launch); flops are
                    ALGORITHMIC (unpadded operand sizes)
   roofline_all  -- the same for every kernel class (the message/reduce kernels are HBM-bound, the projections MFMA-bound)
@@ -21,6 +24,7 @@ Prints ONE JSON line (rank 0) with value = total egonet-edges/s over all ranks, 
                    batches, with the GPU/CPU ratio), the eval scoring loop on the MAG-CS and MAG-Full shapes (candidates scored / s),
                    and the training step of BASELINE configs[4] (PGCN+MR+BIM) and configs[3] (PGAT 2-layer on the MAG-Full taxonomy)
                    with their dominant kernel's roofline
+  and the A/B legs and fresh-batch steps of the full record (bench_extra.json, BENCH_FULL on stderr).
 """
 import argparse
 import ctypes
@@ -150,13 +154,15 @@ _RNG = {}
 SECOND_STREAM_TAG = " [second stream]"
 
 
-def train_step(model, opt, batch, target, world, loss_fn=None):
+def train_step(model, opt, batch, target, world, loss_fn=None, keep=None):
     from taxoexpan_amd.loss import info_nce_loss
     from taxoexpan_amd.scoring import allreduce_gradients
     g = batch["g"]
     g.ndata["pos"] = batch["pos"]
     opt.zero_grad(set_to_none=True)
     pred = model(g, batch["x"], batch["qf"])                       # trainer.py:51
+    if keep is not None:                                             # (--dump-outputs: the scores the caller receives)
+        keep["scores"] = pred.detach()
     loss = (loss_fn or info_nce_loss)(pred.reshape(N_QUERIES, -1), target)   # trainer.py:52-56, loss.py:52-57 (one launch, gradient included)
     if world > 1:      # the output layer's gradient bucket is all-reduced under the backward of the layer below, the rest afterwards
         from taxoexpan_amd.scoring import overlapped_gradient_allreduce
@@ -175,6 +181,26 @@ def assert_finite(model, loss, what):
     ok = bool(torch.isfinite(loss.detach()).all()) and all(bool(torch.isfinite(p).all()) for p in model.parameters())
     assert ok, f"{what}: the model diverged (non-finite loss or parameters) -- the timing is void"
     return float(loss.detach())
+
+
+DUMP_LIMIT = 64 << 20     # bytes, all --dump-outputs files together
+
+
+def dump_outputs(out_dir, model, loss, scores):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the scores of its egonets, and every parameter after the
+    optimizer's update with the gradient that update used -- as <out_dir>/<name>.npy, float32, whole (the largest workload's set is
+    ~47 MB).  The inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    arrays = {"loss": loss, "scores": scores}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 SETTLE_STEPS = 256        # untimed steps before the contract's --warmup (reported as config.settle_steps)
@@ -762,7 +788,7 @@ def compact_line(full):
     """The ONE stdout line of the contract, <= COMPACT_LIMIT bytes: the driver's keys, `config` (workload, sizes, parallelism, routes),
     a flat `roofline`, a flat `cpu_baseline` and a handful of flat scalars.  Everything else bench.py measures (roofline_all, the A/B legs,
     the per-config extras, the prose) goes to bench_extra.json and to stderr -- never to stdout."""
-    c, r, cb = full["config"], full["roofline"], full.get("cpu_baseline") or None
+    c, r, cb = full["config"], full.get("roofline") or {}, full.get("cpu_baseline") or None
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                  "vs_baseline", "dtype", "data")}
     # `dtype` is the arithmetic the path computes in: fp32 in, fp32 out, fp32 accumulation.  `matrix_pipe` says HOW the big products are
@@ -818,17 +844,34 @@ def emit(full):
     print(out, flush=True)
 
 
+def emit_plain(head):
+    """a plain run (no --full): the single stdout line of the headline figure; no roofline, no full record, nothing written"""
+    line = compact_line(head)
+    line["roofline"] = None
+    del line["extra_file"]
+    out = json.dumps(line, separators=(",", ":"))
+    assert len(out) < COMPACT_LIMIT, f"compact bench line is {len(out)} bytes"
+    print(out, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also run the route sanity check, the A/B legs, the fresh-batch steps, the instrumented "
+                         "roofline pass, the extras and the CPU baseline; the full record goes to bench_extra.json and stderr")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(with --full) skip the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, scores, updated parameters, gradients) to DIR/<name>.npy")
     ap.add_argument("--workload", default="pgat", choices=["pgat", "pgcn", "pgat2"],
                     help="pgat = BASELINE configs[1] (default, the metric's workload); pgcn = configs[4] (PGCN+MR+BIM, same batches); "
                          "pgat2 = configs[3] (MAG-Full-shaped taxonomy, PGAT num_layers=2 heads [4,4,1])")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -862,7 +905,18 @@ def main():
     opt = Adam(model.parameters(), lr=LR, weight_decay=0, amsgrad=True)
     batches = build_batches(tax, 4, seed0=1000 * (rank + 1), device=device)
     target = torch.zeros(N_QUERIES, dtype=torch.long, device=device)
-    sanity = route_sanity(model, batches[0], target)       # before anything is timed: the step's loss is finite and route-independent
+    sanity = None
+    if args.full:                                          # before anything is timed: the step's loss is finite and route-independent
+        sanity = route_sanity(model, batches[0], target)
+        rng_after = (torch.get_rng_state(), torch.cuda.get_rng_state(device))
+    # the generators where route_sanity leaves them -- seeded, one forward pass's dropout seed drawn -- so that the steps from here on
+    # compute the same with or without --full
+    torch.manual_seed(4711)
+    from taxoexpan_amd import ops as _ops_s
+    _ops_s.new_seed()
+    if args.full:
+        assert all(torch.equal(a, b) for a, b in zip(rng_after, (torch.get_rng_state(), torch.cuda.get_rng_state(device)))), \
+            "route_sanity no longer leaves the generators where a plain run puts them"
 
     # before the contract's W warm-up steps: a quarter of a second of the same steps, untimed -- a process that starts on an idle GPU has
     # been seen to run its first ~150 steps 20 % slow (clocks and the caching allocator settling: 1.23 ms where every later leg of the
@@ -884,9 +938,10 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     edges = 0
+    last = {}
     for i in range(args.steps):
         b = batches[i % len(batches)]
-        last_loss = train_step(model, opt, b, target, world)
+        last_loss = train_step(model, opt, b, target, world, keep=last if i == args.steps - 1 else None)
         edges += b["n_edges"]
     torch.cuda.synchronize()
     if world > 1:
@@ -903,6 +958,33 @@ def main():
         e = torch.tensor([edges], dtype=torch.float64, device=device)
         dist.all_reduce(e, op=dist.ReduceOp.SUM)
         edges = float(e.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last_loss, last["scores"])
+    head = {
+        "metric": "egonet_edges_per_sec_%s_fwd_bwd" % args.workload, "value": edges / elapsed, "unit": "egonet-edges/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "matrix_pipe": "bf16x3-split(6 products, fp32 accumulate)" if args.workload != "pgcn" else "fp32-mfma",
+        "config": {"workload": WORKLOAD_TEXT[args.workload] + STEP_TEXT,
+                   "output_layer": "folded behind the weighted-mean readout (exact re-association, DESIGN 4.1): G graph rows instead of N node rows"
+                                   + ("" if args.workload == "pgcn" else "; and, the query rows of a training batch repeating 32 times, through the "
+                                      "bilinear matcher (DESIGN 4.9): its three G x D x Kp products run on the 128 query runs -- every output and "
+                                      "gradient still produced, all work inside the timed region"),
+                   "egonets_per_step_per_gpu": N_QUERIES * (1 + NEG), "avg_edges_per_step_per_gpu": edges / args.steps / world,
+                   "matrix_pipe": "the first layer's projection and weight gradient (and, in the eval extras, the scoring loop and the encoder's two large "
+                                  "products) run on the bf16 MFMA as SIX exact plane products per fp32 product with fp32 accumulation -- every fp32 "
+                                  "operand is the exact sum of three bf16 numbers; results are as close to float64 as an fp32 GEMM's "
+                                  "(DESIGN 4.10, tests/test_gpu_split_gemm.py, tests/test_split_arithmetic.py); step_fp32_mfma_ms = the same "
+                                  "step with those products on the fp32 MFMA; roofline_all prices them against 2.5 PF/s / 6",
+                   "settle_steps": SETTLE_STEPS, "sanity": sanity, "routes": routes_timed, "lr": LR, "final_loss": final_loss,
+                   "parallelism": f"dp{world}"},
+    }
+    if not args.full:                                    # a plain run ends with its headline figure
+        if rank == 0:
+            emit_plain(head)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # the same resident batches with the query features as ops.RepeatedRows -- one row per query + the runs of its 1 + NEG pairs, what
     # data_loaders.DeviceBatchLoader hands out -- instead of the reference collate's stack of one row per pair (data_loaders.py:9-28):
@@ -1099,23 +1181,7 @@ def main():
             if "scoring" in cpu:
                 cpu["scoring_factored_value"] = cpu["scoring"]["factored_value"]
         line = {
-            "metric": "egonet_edges_per_sec_%s_fwd_bwd" % args.workload, "value": edges / elapsed, "unit": "egonet-edges/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "matrix_pipe": "bf16x3-split(6 products, fp32 accumulate)" if args.workload != "pgcn" else "fp32-mfma",
-            "config": {"workload": WORKLOAD_TEXT[args.workload] + STEP_TEXT,
-                       "output_layer": "folded behind the weighted-mean readout (exact re-association, DESIGN 4.1): G graph rows instead of N node rows"
-                                       + ("" if args.workload == "pgcn" else "; and, the query rows of a training batch repeating 32 times, through the "
-                                          "bilinear matcher (DESIGN 4.9): its three G x D x Kp products run on the 128 query runs -- every output and "
-                                          "gradient still produced, all work inside the timed region"),
-                       "egonets_per_step_per_gpu": N_QUERIES * (1 + NEG), "avg_edges_per_step_per_gpu": edges / args.steps / world,
-                       "matrix_pipe": "the first layer's projection and weight gradient (and, in the eval extras, the scoring loop and the encoder's two large "
-                                      "products) run on the bf16 MFMA as SIX exact plane products per fp32 product with fp32 accumulation -- every fp32 "
-                                      "operand is the exact sum of three bf16 numbers; results are as close to float64 as an fp32 GEMM's "
-                                      "(DESIGN 4.10, tests/test_gpu_split_gemm.py, tests/test_split_arithmetic.py); step_fp32_mfma_ms = the same "
-                                      "step with those products on the fp32 MFMA; roofline_all prices them against 2.5 PF/s / 6",
-                       "settle_steps": SETTLE_STEPS, "sanity": sanity, "routes": routes_timed, "lr": LR, "final_loss": final_loss,
-                       "parallelism": f"dp{world}"},
+            **head,
             "roofline_all": roof_all,
             "extra": extra,
             "cpu_baseline": cpu,

@@ -1198,13 +1198,13 @@ def test_rank_kernel_against_metric_definition(G, pitch, larger):
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline` objects (short run)"""
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline` objects (short run)"""
     import json
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extra"], cwd=repo,
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-extra"], cwd=repo,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -1243,6 +1243,37 @@ def test_bench_contract_line():
     assert 0.5 * d["ms_per_step"] < d["step_repeated_queries_ms"] < 1.5 * d["ms_per_step"] and d["step_incl_batch_build_repeated_queries_ms"] > 0.0
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == d["unit"] and "sample" in c
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """a plain bench.py run (no --full) prints the headline line alone -- --steps timed steps, ms_per_step, no roofline, no full record --
+    and --dump-outputs writes the last timed step's loss, scores, parameters and gradients as float32 .npy files"""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         cwd=repo, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["metric"] == "egonet_edges_per_sec_pgat_fwd_bwd" and d["unit"] == "egonet-edges/s" and d["higher_is_better"] is True
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["avg_edges_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "roofline_all" not in d and "extra_file" not in d
+    assert not any(ln.startswith("BENCH_FULL ") for ln in out.stderr.splitlines())
+    files = sorted(os.listdir(tmp_path))
+    assert files and all(f.endswith(".npy") for f in files), files
+    arrays = {f[:-len(".npy")]: np.load(tmp_path / f) for f in files}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["scores"].shape == (4096, 1) and arrays["loss"].shape == ()
+    assert abs(float(arrays["loss"]) - d["config"]["final_loss"]) <= 1e-5 * abs(d["config"]["final_loss"])
+    assert arrays["param.match.W.weight"].shape == arrays["grad.match.W.weight"].shape == (1, 500, 250)
 
 
 @pytest.mark.parametrize("kind,readout,drop", [("PGAT", "WMR", 0.0), ("PGAT", "MR", 0.0), ("PGAT", "WMR", 0.2), ("PGCN", "MR", 0.0),

@@ -15,7 +15,7 @@ mkdir -p "$O"
 for W in $WLS; do
   export TXE_PROF_WORKLOAD=$W
   if [ "$W" = pgat ]; then
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${W}_kt" -o kt -- python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > "$O/${W}_kt.log" 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${W}_kt" -o kt -- python bench.py --steps 20 --warmup 5 --full --no-extra --no-cpu-baseline > "$O/${W}_kt.log" 2>&1
   else
     rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${W}_kt" -o kt -- python tools/profile_workload.py > "$O/${W}_kt.log" 2>&1
   fi

@@ -9,7 +9,7 @@ O=gpurun_out/quick_kt
 rm -rf "$O"; mkdir -p "$O"
 export TXE_PROF_WORKLOAD=$W
 if [ "$W" = pgat ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -o kt -- python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > "$O/log" 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -o kt -- python bench.py --steps 20 --warmup 5 --full --no-extra --no-cpu-baseline > "$O/log" 2>&1
 else
   rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -o kt -- python tools/profile_workload.py > "$O/log" 2>&1
 fi

@@ -51,7 +51,7 @@ def summarize(src, wl, tag):
                 on_main = qs.get(main_q, 0.0)
                 tot = sum(qs.values())
                 queue_of[k] = "main" if on_main >= 0.999 * tot else ("2nd" if on_main <= 0.001 * tot else f"main {100 * on_main / tot:.0f}% / 2nd")
-        lines += ["## kernel-trace --stats (" + ("python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline" if wl == "pgat" else f"TXE_PROF_WORKLOAD={wl} python tools/profile_workload.py") + ")", "",
+        lines += ["## kernel-trace --stats (" + ("python bench.py --steps 20 --warmup 5 --full --no-extra --no-cpu-baseline" if wl == "pgat" else f"TXE_PROF_WORKLOAD={wl} python tools/profile_workload.py") + ")", "",
                   "stream: `main` = the caller's stream (critical path); `2nd` = the library's second stream -- those launches run concurrently with",
                   "main-stream kernels, their durations are stretched by sharing the machine and do not add to the step time.", "",
                   "| kernel | calls | total ms | avg us | % | stream |", "|---|---|---|---|---|---|"]
