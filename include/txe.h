@@ -325,6 +325,33 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
                    void* stream);
 
+/* ---- all-candidate scoring loop of the MLP matcher (model_zoo.py:285-298 under test_fast.py:121-123 / infer.py:97-99) ---------------
+ * W1 = ffn[0].weight [H][l+r] = [W1a | W1b], b1, w2 = ffn[2].weight [H], b2 = ffn[2].bias [1].  A = hg W1a^T + b1 [G][H] comes from
+ * txe_linear_fwd (x2 = NULL); then S[q][g] = b2 + sum_h w2[h] relu(A[g][h] + B[q][h]), B = Qf W1b^T, is evaluated on the VALU as
+ * c[q] + sum_h w2[h] max(A[g][h], -B[q][h]) with c[q] = b2 + sum_h w2[h] B[q][h] (one max + one FMA per pair and h; h ascending, never
+ * split: every mode below sees bit-identical scores).  Rows of A or B holding NaN / +-Inf / |x| > lim = 2^120 / max(1, sum |w2|) are
+ * flagged and their pairs take the literal formula (NaN propagates through relu as in torch).  Hp = txe_mlp_padded_h(H) (a multiple of
+ * 16): A, -B and w2 are zero-padded to it.
+ * txe_mlp_project: Ap [G][Hp] = A padded, flag_a [G], mw [Hp + 2] = (w2 padded, b2, lim) -- once per candidate set (G may be 0: mw only).
+ * txe_mlp_query_project: per query block, W1bT [r][H] = W1b transposed: nB [nq][Hp] = -B padded, c [nq], flag_b [nq].
+ * The four scoring entry points mirror txe_score_block / txe_score_positives / txe_score_count_block / txe_score_topk_block (same
+ * pos_off / thr / counts / part_key / part_idx / floor_ws conventions; the top-k tiles are 128 candidates wide: txe_score_topk_tiles(G));
+ * positives take the candidate rows directly (pos_idx [n_pos]; a row outside [0, G) gives 0: a positive of another shard). */
+int txe_mlp_padded_h(int H);
+int txe_mlp_project(const float* A, long long ld_a, int G, int H, const float* w2, const float* b2, float* Ap, float* mw, int* flag_a,
+                    void* stream);
+int txe_mlp_query_project(const float* Qf, long long ld_q, int nq, int r, const float* W1bT, int H, const float* mw, float* nB, float* c,
+                          int* flag_b, void* stream);
+int txe_mlp_score_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                        const float* mw, float* S, long long ld_s, void* stream);
+int txe_mlp_score_positives(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                            const float* mw, const int* pos_off, const int* pos_idx, int n_pos, float* thr, void* stream);
+int txe_mlp_score_count_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                              const float* mw, const int* pos_off, const float* thr, int larger_is_better, int* counts, void* stream);
+int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                             const float* mw, int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws,
+                             int* out_idx, float* out_key, void* stream);
+
 /* plain dense product on the fp32 MFMA GEMM (tests / micro-benchmarks).  layout 0: C = A[M][K] B[N][K]^T; 1: C = A[M][K] B[K][N];
  * 2: C = A[K][M]^T B[K][N].  splits > 1: `splits` partial products at C + z*M*ldc.  ws/ws_bytes (optional, txe_gemm_tail_ws_bytes):
  * scratch that lets the last, partial round of workgroups be split along k ("tail splitting").

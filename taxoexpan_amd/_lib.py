@@ -77,6 +77,13 @@ SIGNATURES = {
     "txe_bilinear_pair_bwd_ws_bytes": (SZ, [I, I, I]),
     "txe_bilinear_pair_bwd": (I, [P, L, P, L, I, I, I, P, I, P, P, P, P, L, P, L, P, P, SZ, P]),
     "txe_score_block": (I, [P, L, I, P, L, I, I, I, P, L, P, SZ, P, SZ, P, P]),
+    "txe_mlp_padded_h": (I, [I]),
+    "txe_mlp_project": (I, [P, L, I, I, P, P, P, P, P, P]),
+    "txe_mlp_query_project": (I, [P, L, I, I, P, I, P, P, P, P, P]),
+    "txe_mlp_score_block": (I, [P, P, I, P, P, P, I, I, P, P, L, P]),
+    "txe_mlp_score_positives": (I, [P, P, I, P, P, P, I, I, P, P, P, I, P, P]),
+    "txe_mlp_score_count_block": (I, [P, P, I, P, P, P, I, I, P, P, P, I, P, P]),
+    "txe_mlp_score_topk_block": (I, [P, P, I, P, P, P, I, I, P, I, I, I, P, P, P, P, P, P]),
     "txe_score_split_ws_bytes": (SZ, [I, I, I]),
     "txe_score_count_block": (I, [P, L, I, P, L, I, I, I, P, P, I, P, P, SZ, P, P]),
     "txe_score_positives": (I, [P, L, I, P, L, I, I, I, P, P, P, SZ, P]),
@@ -141,7 +148,8 @@ class GcnPrepareDesc(C.Structure):
 
 _ERR = {-1: "TXE_ERR_ARG", -2: "TXE_ERR_LAUNCH", -3: "TXE_ERR_WORKSPACE"}
 VALUE_RETURNING = {"txe_gat_padded_k", "txe_gat_collapse_e_tiles", "txe_gat_padded_f", "txe_gcn_padded_f", "txe_profile_count", "txe_gat_fused_bwd_supported",
-                   "txe_gat_aggregate_table_supported", "txe_gat_dx_streams", "txe_score_topk_tiles"}   # int results that are not status codes
+                   "txe_gat_aggregate_table_supported", "txe_gat_dx_streams", "txe_score_topk_tiles",
+                   "txe_mlp_padded_h"}   # int results that are not status codes
 
 _lib = None
 

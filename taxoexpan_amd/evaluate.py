@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .graph import device_egonet_batch
-from .scoring import encode_candidates, rank_all_fused, topk_parents, topk_parents_fused
+from .scoring import encode_candidates, fused_matcher_ok, prepare_matcher, rank_all_fused, topk_parents, topk_parents_fused
 
 
 def candidate_graphs(dtax, anchors, expand_factor, seed, batch_size=-1):
@@ -32,25 +32,41 @@ CASE_METRICS = ("macro_mr", "micro_mr", "hit_at_1", "hit_at_3", "hit_at_5", "mrr
 
 
 def _score_blocks(model, hg, qf, qblock):
-    """score blocks [<= qblock queries, G candidates] of the per-query loop test_fast.py:121-123 / infer.py:96-98: one factored GEMM per
-    block for BIM / LBM, the literal expand loop for any other matcher"""
-    from . import ops
-    U = None
+    """score blocks [<= qblock queries, G candidates] of the per-query loop test_fast.py:121-123 / infer.py:96-98: the prepared matcher's
+    block kernel for BIM / LBM / MLP (scoring.prepare_matcher), the literal expand loop for any other matcher"""
+    pm = None
     for q0 in range(0, qf.shape[0], qblock):
-        if hasattr(model.match, "W") and hasattr(model.match, "apply_exp"):
-            U = ops.bilinear_project(hg, model.match.W.weight) if U is None else U
-            yield q0, ops.score_block(qf[q0:q0 + qblock], U, model.match.apply_exp)
+        if fused_matcher_ok(model.match):
+            pm = prepare_matcher(model.match, hg) if pm is None else pm
+            yield q0, pm.score(qf[q0:q0 + qblock])
         else:
             yield q0, torch.stack([model.match(hg, q.expand(hg.shape[0], -1)).reshape(-1) for q in qf[q0:q0 + qblock]])
 
 
 def _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock):
-    """the `topk` best candidates of every query, best first (infer.py:100-106 / test_fast.py:125-131): BIM / LBM with topk <= 8 through
-    the fused score + select kernels (no score matrix), anything else by materialising score blocks"""
-    if hasattr(model.match, "W") and hasattr(model.match, "apply_exp") and 1 <= topk <= 8 and hg.shape[0] > 0 and qf.shape[0] > 0:
+    """the `topk` best candidates of every query, best first (infer.py:100-106 / test_fast.py:125-131): BIM / LBM / MLP with topk <= 8
+    through the fused score + select kernels (no score matrix), anything else by materialising score blocks"""
+    if fused_matcher_ok(model.match) and 1 <= topk <= 8 and hg.shape[0] > 0 and qf.shape[0] > 0:
         return topk_parents_fused(model.match, hg, qf, cand_ids, topk, larger_is_better, block=qblock)
     top = [topk_parents(S, cand_ids, topk, larger_is_better) for _q0, S in _score_blocks(model, hg, qf, qblock or 1024)]
     return torch.cat(top) if top else cand_ids.new_zeros((0, 0))
+
+
+def _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock):
+    """ranks of every query's true parents: fused (no score matrix) for BIM / LBM / MLP; any other matcher materialises score blocks with
+    the literal loop and ranks them on device (ops.rank_block)"""
+    from . import ops
+    if fused_matcher_ok(model.match):
+        return rank_all_fused(model.match, hg, qf, pos_off, pos_idx, block=qblock, larger_is_better=larger_is_better)
+    off = np.asarray(pos_off, dtype=np.int64)
+    idx = np.asarray(pos_idx, dtype=np.int64)
+    out = []
+    for q0, S in _score_blocks(model, hg, qf, qblock or 1024):
+        q1 = q0 + S.shape[0]
+        lo, hi = int(off[q0]), int(off[q1])
+        if hi > lo:
+            out.append(ops.rank_block(S.contiguous(), torch.from_numpy(off[q0:q1 + 1] - lo), torch.from_numpy(idx[lo:hi]), larger_is_better))
+    return torch.cat(out) if out else torch.zeros(0, dtype=torch.int32, device=hg.device)
 
 
 def _case_rows(dataset, queries, pos_off, ranks, top, metric_names):
@@ -97,7 +113,7 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     pos_idx = np.concatenate(pos_lists).astype(np.int64) if pos_lists else np.zeros(0, dtype=np.int64)
     qf = dataset.node_features[torch.as_tensor(queries, dtype=torch.long)].to(device)
     with torch.no_grad():
-        ranks = rank_all_fused(model.match, hg, qf, pos_off, pos_idx, block=qblock, larger_is_better=larger_is_better)
+        ranks = _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock)
         if case is not None:                                               # test_fast.py:112-147
             cand_ids = torch.as_tensor(np.asarray(cand, dtype=np.int64), device=device)
             top = _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock).cpu().tolist()

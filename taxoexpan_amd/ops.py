@@ -1889,3 +1889,153 @@ def rank_block(S, pos_off, pos_idx, larger_is_better=True):
         call("txe_rank_block", ptr(S), S.stride(0), nq, G, ptr(pos_off), ptr(pos_idx), ptr(ranks), int(larger_is_better), None,
              _lib.stream_ptr())
     return ranks[:pos_idx.numel()]
+
+
+# ================================================================================================================
+# MLP matcher (model_zoo.py:285-298) on the all-candidate loop: txe_mlp_* (VALU pair kernel, no [G, l+r] x [l+r, H] product per query)
+# ================================================================================================================
+class MLPPrepared:
+    """the candidate side of the MLP matcher, once per candidate set: Ap [G, Hp] = hg W1a^T + b1 zero-padded to Hp, flags [G] (rows
+    with NaN / +-Inf / huge values: their pairs take the literal formula), mw [Hp + 2] = (w2 padded, b2, the flag limit), W1bT [r, H]"""
+    __slots__ = ("Ap", "flags", "mw", "W1bT", "G", "H", "r")
+
+    def __init__(self, Ap, flags, mw, W1bT, G, H, r):
+        self.Ap, self.flags, self.mw, self.W1bT, self.G, self.H, self.r = Ap, flags, mw, W1bT, G, H, r
+
+
+class MLPQueries:
+    """the query side of one block: nB [nq, Hp] = -(Q W1b^T) zero-padded, c [nq] = b2 + B w2, flags [nq]"""
+    __slots__ = ("nB", "c", "flags", "n")
+
+    def __init__(self, nB, c, flags, n):
+        self.nB, self.c, self.flags, self.n = nB, c, flags, n
+
+    @property
+    def shape(self):
+        return (self.n, self.nB.shape[1])
+
+    def __getitem__(self, sl):
+        """a row block (slice) of a prepared query set: rows are independent, so a block of the whole set's preparation is the block's own"""
+        assert isinstance(sl, slice) and sl.step in (None, 1)
+        lo, hi, _ = sl.indices(self.n)
+        hi = max(hi, lo)
+        return MLPQueries(self.nB[lo:hi], self.c[lo:hi], self.flags[lo:hi], hi - lo)
+
+
+def mlp_project(hg, match):
+    """prepare the candidate side of an MLP matcher for scoring: A = hg W1a^T + b1 on the fp32 GEMM (txe_linear_fwd), padded and
+    flagged by txe_mlp_project.  Returns MLPPrepared."""
+    W1, b1 = match.ffn[0].weight, match.ffn[0].bias
+    w2, b2 = match.ffn[2].weight, match.ffn[2].bias
+    _need_cuda(hg, W1, b1, w2, b2)
+    hg, ld = _rows(hg)
+    G, l = hg.shape
+    H, K = W1.shape
+    r = K - l
+    assert r >= 1 and w2.numel() == H and b2.numel() == 1, "mlp_project: ffn = Linear(l + r, H), ReLU, Linear(H, 1)"
+    with _lib.on_device(hg.device):
+        Hp = pure("txe_mlp_padded_h", H)
+        Ap = _empty((max(G, 1), Hp), hg)
+        flags = torch.zeros(max(G, 1), dtype=torch.int32, device=hg.device)
+        mw = _empty((Hp + 2,), hg)
+        A = None
+        if G > 0:
+            W1a = _f32(W1[:, :l])
+            A = _empty((G, H), hg)
+            call("txe_linear_fwd", ptr(hg), ld, l, None, 0, 0, G, ptr(W1a), ptr(_f32(b1)), H, 0, ptr(A), _lib.stream_ptr())
+        call("txe_mlp_project", ptr(A) if A is not None else None, H, G, H, ptr(_f32(w2.reshape(-1))), ptr(_f32(b2.reshape(-1))),
+             ptr(Ap), ptr(mw), ptr(flags), _lib.stream_ptr())
+    return MLPPrepared(Ap[:G], flags[:G], mw, _f32(W1[:, l:].t()), G, H, r)
+
+
+def mlp_prepare_queries(Q, prep):
+    """the query side of a block (or of a whole query set: MLPQueries slices into blocks)"""
+    if isinstance(Q, MLPQueries):
+        return Q
+    _need_cuda(Q)
+    Q, ldq = _rows(Q)
+    nq, r = Q.shape
+    assert r == prep.r, "mlp_prepare_queries: query width != the matcher's r"
+    Hp = prep.mw.numel() - 2
+    nB = _empty((max(nq, 1), Hp), Q)
+    c = _empty((max(nq, 1),), Q)
+    flags = torch.zeros(max(nq, 1), dtype=torch.int32, device=Q.device)
+    if nq > 0:
+        with _lib.on_device(Q.device):
+            call("txe_mlp_query_project", ptr(Q), ldq, nq, r, ptr(prep.W1bT), prep.H, ptr(prep.mw), ptr(nB), ptr(c), ptr(flags),
+                 _lib.stream_ptr())
+    return MLPQueries(nB[:nq], c[:nq], flags[:nq], nq)
+
+
+def _mlp_args(qp, prep):
+    return (ptr(prep.Ap), ptr(prep.flags), prep.G, ptr(qp.nB), ptr(qp.c), ptr(qp.flags), qp.n, prep.H, ptr(prep.mw))
+
+
+def mlp_score_block(Q, prep, out=None):
+    """S[q][g] = match(hg[g], Q[q]) of an MLP matcher for a block of queries (raw [nq, r] or MLPQueries) against every candidate
+    (txe_mlp_score_block).  out: [nq, G] view with unit column stride; default: rows on a 16-byte pitch like score_block."""
+    qp = mlp_prepare_queries(Q, prep)
+    G = prep.G
+    S = out if out is not None else _empty((qp.n, (G + 3) // 4 * 4), prep.Ap)[:, :G]
+    assert S.dtype == torch.float32 and (S.numel() == 0 or S.stride(1) == 1)
+    if qp.n > 0 and G > 0:
+        with _lib.on_device(prep.Ap.device):
+            call("txe_mlp_score_block", *_mlp_args(qp, prep), ptr(S), S.stride(0), _lib.stream_ptr())
+    return S
+
+
+def mlp_positive_scores(Q, prep, pos_off, pos_idx, out=None):
+    """thr[j] = match(hg[pos_idx[j]], Q[q]) for each query's true parents (the pair kernel's own chain: bit-identical to the stored
+    block); pos_idx outside [0, G) (a positive that lives in another candidate shard) gives 0"""
+    qp = mlp_prepare_queries(Q, prep)
+    dev = prep.Ap.device
+    pos_off = _i32(pos_off, dev)
+    pos_idx = _i32(pos_idx, dev)
+    n_pos = int(pos_idx.numel())
+    thr = out if out is not None else torch.zeros(n_pos, dtype=torch.float32, device=dev)
+    assert thr.dtype == torch.float32 and thr.is_contiguous() and thr.numel() >= n_pos
+    if n_pos > 0 and qp.n > 0:
+        with _lib.on_device(dev):
+            call("txe_mlp_score_positives", *_mlp_args(qp, prep), ptr(pos_off), ptr(pos_idx), n_pos, ptr(thr), _lib.stream_ptr())
+    return thr[:n_pos]
+
+
+def mlp_score_count_block(Q, prep, pos_off, thr, larger_is_better=True, counts=None):
+    """fused scoring + ranking of one query block (txe_mlp_score_count_block): int32 counts [n_pos] of candidates strictly better than
+    each positive's threshold; no [nq x G] block is materialised.  counts (zeroed by the caller) accumulate: shards add."""
+    qp = mlp_prepare_queries(Q, prep)
+    dev = prep.Ap.device
+    pos_off = _i32(pos_off, dev)
+    thr = _f32(thr)
+    if counts is None:
+        counts = torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=dev)
+    if thr.numel() == 0 or qp.n == 0 or prep.G == 0:
+        return counts
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
+    with _lib.on_device(dev):
+        call("txe_mlp_score_count_block", *_mlp_args(qp, prep), ptr(pos_off), ptr(thr), int(larger_is_better), ptr(counts),
+             _lib.stream_ptr())
+    return counts
+
+
+def mlp_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=None):
+    """fused scoring + best-k selection of one query block (txe_mlp_score_topk_block): (idx int32 [nq, k] = candidate rows + idx_base,
+    key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(8, G).  scratch: dict reused across blocks."""
+    qp = mlp_prepare_queries(Q, prep)
+    dev = prep.Ap.device
+    G, nq = prep.G, qp.n
+    assert 1 <= k <= 8 and k <= G, "mlp_score_topk_block: 1 <= k <= min(8, candidates)"
+    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    key = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if nq == 0:
+        return idx, key
+    with _lib.on_device(dev):
+        nt = pure("txe_score_topk_tiles", G)
+        need = nq * nt * k
+        sc = scratch if scratch is not None else {}
+        if sc.get("n", 0) < need or sc.get("nq", 0) < nq or sc["key"].device != dev:
+            sc["key"], sc["idx"], sc["n"] = _empty((need,), prep.Ap), torch.empty(need, dtype=torch.int32, device=dev), need
+            sc["floor"], sc["nq"] = torch.empty(nq, dtype=torch.int32, device=dev), nq
+        call("txe_mlp_score_topk_block", *_mlp_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]),
+             ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
+    return idx, key

@@ -15,19 +15,82 @@ import torch.distributed as dist
 from . import ops
 
 
+class _PreparedBilinear:
+    """a BIM / LBM matcher over a candidate set: U = hg W once (txe_bilinear_project), every query block one GEMM with its epilogue"""
+
+    def __init__(self, match, hg):
+        self.U, self.exp = ops.bilinear_project(hg, match.W.weight), match.apply_exp
+
+    def queries(self, Q):
+        return ops.pad_queries_like(Q, self.U)
+
+    def score(self, qb, out=None):
+        return ops.score_block(qb, self.U, self.exp, out=out)
+
+    def positives(self, qb, off, rows, out):
+        return ops.positive_scores_staircase(qb, ops.gather_padded_rows(self.U, rows), self.exp, off, out)
+
+    def count(self, qb, off, thr, larger_is_better, counts):
+        return ops.score_count_block(qb, self.U, self.exp, off, thr, larger_is_better, counts=counts, q_padded=True)
+
+    def topk(self, qb, k, larger_is_better, idx_base, scratch):
+        return ops.score_topk_block(qb, self.U, self.exp, k, larger_is_better, idx_base=idx_base, q_padded=True, scratch=scratch)
+
+
+class _PreparedMLP:
+    """the MLP matcher over a candidate set: A = hg W1a^T + b1 once (ops.mlp_project), every query block through the VALU pair kernel
+    (txe_mlp_*) -- the same four modes, the same scratch and count conventions"""
+
+    def __init__(self, match, hg):
+        self.prep = ops.mlp_project(hg, match)
+
+    def queries(self, Q):
+        return ops.mlp_prepare_queries(Q, self.prep)
+
+    def score(self, qb, out=None):
+        return ops.mlp_score_block(qb, self.prep, out=out)
+
+    def positives(self, qb, off, rows, out):
+        return ops.mlp_positive_scores(qb, self.prep, off, rows, out=out)
+
+    def count(self, qb, off, thr, larger_is_better, counts):
+        return ops.mlp_score_count_block(qb, self.prep, off, thr, larger_is_better, counts=counts)
+
+    def topk(self, qb, k, larger_is_better, idx_base, scratch):
+        return ops.mlp_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
+
+
+def fused_matcher_ok(match):
+    """does `match` have a fused all-candidate route (prepare_matcher)?  BIM / LBM and MLP do; anything else (NTN, a user's module) is
+    scored by calling it (evaluate._score_blocks)"""
+    from .model_zoo import MLP
+    return isinstance(match, MLP) or (hasattr(match, "W") and hasattr(match, "apply_exp"))
+
+
+def prepare_matcher(match, hg):
+    """the one place that dispatches on the matcher: a prepared candidate side with score / positives / count / topk over query blocks
+    (blocks of .queries(all queries) for the last three)"""
+    from .model_zoo import MLP
+    if isinstance(match, MLP):
+        return _PreparedMLP(match, hg)
+    if hasattr(match, "W") and hasattr(match, "apply_exp"):
+        return _PreparedBilinear(match, hg)
+    raise TypeError(f"no fused all-candidate route for a {type(match).__name__} matcher (BIM / LBM / MLP have one)")
+
+
 def score_all(match, hg, queries, block=None, out=None):
-    """S[q][g] = match(hg[g], queries[q]) for all pairs; match is a BIM / LBM module.
+    """S[q][g] = match(hg[g], queries[q]) for all pairs; match is a BIM / LBM / MLP module.
     block: queries per GEMM launch; default: a query set of up to 4,096 goes in ONE launch (MAG-CS: 2,459 queries x 24.7 k candidates
     are 7.6 rounds of tiles -- in blocks of 1,024 every block pays its own partial last round and a second, 16-tile launch), larger
     sets in blocks of 1,024."""
-    U = ops.bilinear_project(hg, match.W.weight)
+    pm = prepare_matcher(match, hg)
     Q = queries.shape[0]
     G = hg.shape[0]
     if block is None:
         block = 1024 if Q > 4096 else max(int(Q), 1)
     S = out if out is not None else torch.empty((Q, (G + 3) // 4 * 4), dtype=torch.float32, device=hg.device)[:, :G]
     for q0 in range(0, Q, block):
-        ops.score_block(queries[q0:q0 + block], U, match.apply_exp, out=S[q0:q0 + block])
+        pm.score(queries[q0:q0 + block], out=S[q0:q0 + block])
     return S
 
 
@@ -106,11 +169,12 @@ def score_all_sharded(match, hg_local, n_total, queries, block=1024, group=None,
     c = math.ceil(n_total / world)
     dev = hg_local.device
     if local_score_fn is None:
-        U = ops.bilinear_project(hg_local, match.W.weight) if hg_local.shape[0] > 0 else hg_local.new_zeros((0, queries.shape[1]))
+        n_local = hg_local.shape[0]
+        pm = prepare_matcher(match, hg_local) if n_local > 0 else None
 
         def local_score_fn(qb, out):
-            if U.shape[0] > 0:
-                ops.score_block(qb, U, match.apply_exp, out=out[:, :U.shape[0]])
+            if pm is not None:
+                pm.score(qb, out=out[:, :n_local])
     Q = queries.shape[0]
     bmax = min(block, max(Q, 1))
     nbuf = 3 if pipeline else 1
@@ -174,17 +238,12 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
         block = 1024 if queries.shape[0] > 4096 else max(int(queries.shape[0]), 1)
     if local_fns is None and hg.shape[0] > 0:
         return _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_is_better, group, shard_lo, distributed)
-    if local_fns is None:
-        U = ops.bilinear_project(hg, match.W.weight) if hg.shape[0] > 0 else None
-        exp = match.apply_exp
-
+    if local_fns is None:                                          # (an empty shard: it scores nothing, but joins the collectives)
         def f_thr(qb, off, idx_local):
-            return ops.positive_scores(qb, U, exp, off, idx_local) if U is not None else torch.zeros(idx_local.numel(), device=dev)
+            return torch.zeros(idx_local.numel(), device=dev)
 
         def f_cnt(qb, off, thr):
-            if U is None:
-                return torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=dev)
-            return ops.score_count_block(qb, U, exp, off, thr, larger_is_better)
+            return torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=dev)
     else:
         f_thr, f_cnt = local_fns
     pos_off_h = torch.as_tensor(pos_off).to(torch.int64).cpu()            # block boundaries are host integers
@@ -240,9 +299,8 @@ def _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_i
     offs = up(offs_h, torch.int32)
     all_local = bool(local_h.all())
     localb = None if all_local else up(local_h, torch.bool)
-    U = ops.bilinear_project(hg, match.W.weight)
-    exp = match.apply_exp
-    Qp = ops.pad_queries_like(queries, U)
+    pm = prepare_matcher(match, hg)
+    Qp = pm.queries(queries)
     counts = torch.zeros(n_pos, dtype=torch.int32, device=dev)
     ranks = torch.empty(n_pos, dtype=torch.int32, device=dev)
     thr_all = torch.empty(n_pos, dtype=torch.float32, device=dev)
@@ -256,12 +314,12 @@ def _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_i
         qb = Qp[q0:q1]
         # thresholds: the positives' scores through the SAME score kernel as the block (bit-identical values), the staircase of tiles
         # that holds them only
-        thr = ops.positive_scores_staircase(qb, ops.gather_padded_rows(U, idxc[lo:hi]), exp, off, thr_all[lo:hi])
+        thr = pm.positives(qb, off, idxc[lo:hi], thr_all[lo:hi])
         if localb is not None:                                           # a positive that lives in another shard contributes 0 here
             thr.copy_(torch.where(localb[lo:hi], thr, torch.zeros((), device=dev)))      # (not a product: the placeholder may be inf)
         if distributed:
             dist.all_reduce(thr, op=dist.ReduceOp.SUM, group=group)      # each positive lives in exactly one shard
-        ops.score_count_block(qb, U, exp, off, thr, larger_is_better, counts=counts[lo:hi], q_padded=True)
+        pm.count(qb, off, thr, larger_is_better, counts[lo:hi])
         if distributed:
             dist.all_reduce(counts[lo:hi], op=dist.ReduceOp.SUM, group=group)
         ops.rank_finalize(off, thr, counts[lo:hi], larger_is_better, out=ranks[lo:hi])
@@ -431,7 +489,7 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
     each tile's best k columns per row (txe_score_topk_block) + a merge launch -- no [Q, G] scores, no [Q, G] index temporaries (the
     torch composite topk_parents below needs two int64 [Q, G] ones: 3.5 GB per 1,024-query block on MAG-Full).  Same selection and
     order as topk_parents on the materialised scores of the same kernel (bit-identical values): better score first, ties by ascending
-    candidate position (Python's stable sort), NaN last.  match: BIM / LBM.  hg: this rank's candidate rows (positions
+    candidate position (Python's stable sort), NaN last.  match: BIM / LBM / MLP.  hg: this rank's candidate rows (positions
     [shard_lo, shard_lo + len) of the global list).  Candidate-sharded (ONLY when asked: `group` given or sharded=True, _sharded_call
     -- every rank then holds a DISJOINT slice, which the merge relies on): every rank's [Q, k] lists
     are all-gathered (k * 8 bytes per query instead of the [queries x candidates] block) and merged by the same kernel.
@@ -445,12 +503,11 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
         block = 1024 if Q > 4096 else max(Q, 1)
     outs = []
     if k_loc > 0 and Q > 0:
-        U = ops.bilinear_project(hg, match.W.weight)
-        Qp = ops.pad_queries_like(queries, U)
+        pm = prepare_matcher(match, hg)
+        Qp = pm.queries(queries)
         scratch = {}
         for q0 in range(0, Q, block):
-            outs.append(ops.score_topk_block(Qp[q0:q0 + block], U, match.apply_exp, k_loc, larger_is_better, idx_base=shard_lo, q_padded=True,
-                                             scratch=scratch))
+            outs.append(pm.topk(Qp[q0:q0 + block], k_loc, larger_is_better, shard_lo, scratch))
     if outs:
         idx, key = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
     else:
