@@ -473,6 +473,22 @@ int txe_egonet_fill(const int* par_ptr, const int* par_idx, const int* chd_ptr, 
                     const int* exclude, int G, int expand, unsigned long long seed, int index_base, const int* node_off, int* ids, int* pos,
                     int* rowptr_in, int* col_src, int* eid_in, int* rowptr_out, int* col_dst, int* pos_out, void* stream);
 
+/* ---- training-anchor sampling on device, sampling_mode 1: data_loader/dataset.py:334-381 (one positive through the positive pointer,
+ * exactly k negatives) for the Q queries at positions start .. start+Q-1 of the epoch order (order [n_order]: indices into node_list).
+ * Writes the index arrays of txe_egonet_offsets / txe_egonet_fill in one launch, B = Q (1 + k), packed [4B + 1]:
+ *   [0, B) anchors (query i: its positive, then its k negatives) | [B, 2B) exclude (the query for the positive, -1 for negatives) |
+ *   repeated == 0: [2B, 3B) the query id of every pair;  repeated != 0: [2B, 2B+Q) the distinct query ids, [3B, 3B+Q+1) run offsets i (1+k).
+ * Positive: p = par_idx[par_ptr[q] + pos_ptr[q]], then pos_ptr[q] = (pos_ptr[q] + 1) % (parents of q) -- in place, the host walk exactly.
+ * Negative slot j of epoch position s: attempt t = 0 .. 63 draws pool[(hi32(h) n_pool) >> 32], h = mix64(seed ^ mix64(epoch << 44 |
+ * s << 20 | j << 6 | t)) (csrc/txe_common.h), accepted when not in q's sorted mask row mask_idx[mask_ptr[q] .. mask_ptr[q+1]); after 64
+ * rejections the last draw stays and *n_padded is incremented (dataset.py:370-375 pads with nodes that may be masked).  A query must not
+ * appear twice among launches in flight on different streams (the pointer update is not atomic).
+ * TXE_ERR_ARG (before any device work): a NULL pointer, k < 1 or k >= 2^14, Q < 0, n_pool < 1, start < 0, start + Q > n_order or > 2^24,
+ * epoch outside [0, 2^20), 4B + 1 >= 2^31. */
+int txe_sample_anchors(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                       const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k, unsigned long long seed,
+                       int epoch, int repeated, int* packed, int* n_padded, void* stream);
+
 /* ---- optional per-kernel timing (debug / bench): HIP events on the launch stream around every kernel launch, with the
  * algorithmic work (flops or compulsory bytes) its launcher attributes to it.  Global state (see the conventions at the top); off by
  * default.  txe_profile_get synchronises on record i's events. */

@@ -1,0 +1,110 @@
+// Training-anchor sampling ON DEVICE for sampling_mode 1 (data_loader/dataset.py:334-381: one positive per query through the positive
+// pointer, exactly k negatives): one launch writes a batch straight into the packed index layout begin_device_batch uploads, so the
+// egonet builder (txe_egonet_offsets / txe_egonet_fill) takes it unchanged.
+//
+// Negative slot j of the query at epoch position s: attempt t = 0, 1, .. draws pool[(hi32(h) * n_pool) >> 32] with
+// h = mix64(seed ^ mix64(ctr(epoch, s, j, t))) and keeps the first draw that is not in the query's (sorted) mask row.  The draw is a pure
+// function of (seed, epoch, s, j, t): it does not depend on the batch size or on the batch index (taxoexpan_amd/sampler.py host_draw
+// restates it).  After SAMPLE_TRIES rejections the slot keeps its last draw and counts itself in n_padded -- the reference's corner case
+// (dataset.py:370-375) pads with queue-head nodes that may be masked too; the anchor is always a pool node, never an invalid id.
+#include "txe_common.h"
+
+#define SAMPLE_TRIES 64
+
+namespace txe {
+
+// bits: t [0, 6) | j [6, 20) | s [20, 44) | epoch [44, 64) -- the argument checks keep every field inside its range
+__host__ __device__ __forceinline__ uint64_t sample_ctr(int epoch, int s, int j, int t) {
+    return ((uint64_t)epoch << 44) | ((uint64_t)s << 20) | ((uint64_t)j << 6) | (uint64_t)t;
+}
+
+// first position of the sorted row r[0..n) whose value is >= v
+__device__ __forceinline__ int lower_bound(const int* __restrict__ r, int n, int v) {
+    int lo = 0;
+    while (n > 0) {
+        const int half = n >> 1;
+        if (r[lo + half] < v) { lo += half + 1; n -= half + 1; } else { n = half; }
+    }
+    return lo;
+}
+
+// One wavefront per query, lane = negative slot (strides of 64 for k >= 64); lane 0 also takes the positive.
+// A query appears once in an epoch order, and the loader's two batches in flight run on its one side stream, so no two waves -- of one
+// launch or of two -- touch the same positive pointer at the same time: the read-modify-write of pos_ptr needs no atomic.
+__global__ __launch_bounds__(256) void sample_anchors_kernel(const int* __restrict__ order, int start, int Q, const int* __restrict__ node_list,
+                                                             const int* __restrict__ par_ptr, const int* __restrict__ par_idx,
+                                                             const int* __restrict__ mask_ptr, const int* __restrict__ mask_idx,
+                                                             const int* __restrict__ pool, int n_pool, int* __restrict__ pos_ptr, int k,
+                                                             unsigned long long seed, int epoch, int repeated, int* __restrict__ packed,
+                                                             int* __restrict__ n_padded) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + w;
+    if (i >= Q) return;
+    const int s = start + i;
+    const int q = node_list[order[s]];
+    const int B = Q * (1 + k);
+    const int base = i * (1 + k);
+    int* anchors = packed;
+    int* exclude = packed + B;
+    int* qids = packed + 2 * B;
+    if (l == 0) {                                     // the positive: dataset.py:336-340
+        const int pb = par_ptr[q], np_ = par_ptr[q + 1] - pb;
+        int p = q;                                    // (a query always has a parent: sampler.py checks; never an invalid id regardless)
+        if (np_ > 0) {
+            int c = pos_ptr[q];
+            c = (c >= 0 && c < np_) ? c : 0;
+            p = par_idx[pb + c];
+            pos_ptr[q] = (c + 1) % np_;
+        }
+        anchors[base] = p;
+        exclude[base] = q;
+        if (repeated) {                               // one run per query: the distinct id and the run's first pair
+            qids[i] = q;
+            packed[3 * B + i] = base;
+            if (i == Q - 1) packed[3 * B + Q] = B;
+        } else {
+            qids[base] = q;
+        }
+    }
+    const int mb = mask_ptr[q], mn = mask_ptr[q + 1] - mb;
+    const int* mrow = mask_idx + mb;
+    for (int j0 = 0; j0 < k; j0 += 64) {
+        const int j = j0 + l;
+        if (j >= k) break;
+        int a = 0;
+        bool ok = false;
+        for (int t = 0; t < SAMPLE_TRIES && !ok; ++t) {
+            const uint64_t h = mix64(seed ^ mix64(sample_ctr(epoch, s, j, t)));
+            a = pool[(int)(((h >> 32) * (uint64_t)n_pool) >> 32)];
+            const int at = lower_bound(mrow, mn, a);
+            ok = !(at < mn && mrow[at] == a);
+        }
+        if (!ok) atomicAdd(n_padded, 1);
+        const int o = base + 1 + j;
+        anchors[o] = a;
+        exclude[o] = -1;
+        if (!repeated) qids[o] = q;
+    }
+}
+
+}  // namespace txe
+
+using namespace txe;
+
+extern "C" {
+
+int txe_sample_anchors(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                       const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k, unsigned long long seed,
+                       int epoch, int repeated, int* packed, int* n_padded, void* stream) {
+    if (!order || !node_list || !par_ptr || !par_idx || !mask_ptr || !mask_idx || !pool || !pos_ptr || !packed || !n_padded) return TXE_ERR_ARG;
+    if (k < 1 || k >= (1 << 14) || Q < 0 || n_pool < 1 || n_order < 0 || start < 0 || epoch < 0 || epoch >= (1 << 20)) return TXE_ERR_ARG;
+    if ((long long)start + Q > n_order || (long long)start + Q > (1 << 24)) return TXE_ERR_ARG;
+    if (4LL * Q * (1 + k) + 1 > 0x7fffffffLL) return TXE_ERR_ARG;
+    if (Q == 0) return TXE_OK;
+    hipLaunchKernelGGL(sample_anchors_kernel, dim3((Q + 3) / 4), dim3(256), 0, (hipStream_t)stream, order, start, Q, node_list, par_ptr,
+                       par_idx, mask_ptr, mask_idx, pool, n_pool, pos_ptr, k, seed, epoch, repeated, packed, n_padded);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
+}  // extern "C"

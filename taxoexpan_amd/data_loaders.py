@@ -201,15 +201,27 @@ class DeviceBatchLoader:
     repeated_queries (default): the query features are an ops.RepeatedRows -- the sampler pairs one query with 1 + negative_size
     consecutive anchors, only the distinct rows are gathered and BIM / LBM project those (every other matcher of model_zoo densifies it;
     `.dense()` gives the reference's stacked [B, in_dim] tensor); False: the stacked tensor itself.  Yields (graph, node features, query features, labels) -- MaskedGraphDataLoader's small-batch
-    tuple with the node features popped, all on `device`."""
+    tuple with the node features popped, all on `device`.
+    sampler="host" (default): the anchors come from dataset.sample_anchors (the reference's `random`-module trace, host Python per pair).
+    sampler="device" (sampling_mode 1, train / validation): sampler.DeviceAnchorSampler draws them on the side stream in one launch per
+    batch -- no host work per pair, no upload per batch (the epoch order goes up once per epoch), labels a cached device tensor.  Its
+    positives walk the same pointers as the host sampler, starting from the dataset's node2positive_pointer when the loader is made; the
+    host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py)."""
 
-    def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True):
+    def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host"):
+        if sampler not in ("host", "device"):
+            raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
         self.repeated_queries = bool(repeated_queries)
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         self.shuffle, self.seed, self.drop_last = shuffle, int(seed), drop_last
         self.dtax = dataset.device_taxonomy(self.device)
         self.features = self.dtax.features
         self._side = torch.cuda.Stream(device=self.device)
+        self.sampler = None
+        if sampler == "device":
+            from .sampler import DeviceAnchorSampler
+            self.sampler = DeviceAnchorSampler(dataset, self.device, seed=self.seed, dtax=self.dtax)
+            self._labels = {}
         torch.cuda.current_stream(self.device).synchronize()      # the resident taxonomy / feature table are complete from here on
         self._epoch = 0
 
@@ -223,6 +235,9 @@ class DeviceBatchLoader:
         if self.shuffle:
             random.Random(self.seed + self._epoch).shuffle(order)
         self._epoch += 1
+        if self.sampler is not None:
+            yield from self._iter_device(order, self._epoch - 1)
+            return
         def begin(b):
             idx = order[b * self.batch_size:(b + 1) * self.batch_size]
             query, anchor, label, exclude = self.dataset.sample_anchors(idx)
@@ -236,3 +251,26 @@ class DeviceBatchLoader:
             batch = finish_device_batch(pending, self.features)
             nxt = begin(b + 1) if b + 1 < len(self) else None
             yield batch["g"], batch["x"], batch["qf"], torch.as_tensor(label).to(self.device, non_blocking=True)
+
+    def _label(self, Q):
+        """[1, 0 x k] per query, int64 on the device, made once per batch size"""
+        lab = self._labels.get(Q)
+        if lab is None:
+            lab = torch.zeros(Q, 1 + self.sampler.k, dtype=torch.int64, device=self.device)
+            lab[:, 0] = 1
+            lab = self._labels[Q] = lab.reshape(-1)
+        return lab
+
+    def _iter_device(self, order, epoch):
+        n, bs = len(order), self.batch_size
+        order_dev = self.sampler.upload_order(order, self._side)     # once per epoch, on the side stream the launches use
+        def begin(b):
+            Q = min(bs, n - b * bs)
+            return Q, self.sampler.begin(order_dev, b * bs, Q, epoch, self.repeated_queries, self._side,
+                                         egonet_seed=self.seed + 7919 * self._epoch + b)
+        nxt = begin(0) if len(self) else None
+        for b in range(len(self)):
+            Q, pending = nxt
+            batch = finish_device_batch(pending, self.features)
+            nxt = begin(b + 1) if b + 1 < len(self) else None
+            yield batch["g"], batch["x"], batch["qf"], self._label(Q)

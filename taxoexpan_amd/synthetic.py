@@ -70,6 +70,29 @@ def make_named_taxonomy(name, seed=47, features=True):
     return make_taxonomy(s["n_nodes"], s["n_edges"], s["dim"], seed=seed, features=features)
 
 
+def write_raw(directory, name, edges, features):
+    """a taxonomy as the reference's raw files (README.md:21-51): `<name>.terms` (taxon id, name), `<name>.taxo` (parent id, child id),
+    `<name>.terms.embed` (word2vec text) -- what MAGDataset(name, directory, raw=True) reads.  edges: (parent, child) node indices;
+    features [n, d].  Taxon ids are T<index>."""
+    import os
+    feats = np.asarray(features, dtype=np.float32)
+    n, d = feats.shape
+    with open(os.path.join(directory, f"{name}.terms"), "w") as f:
+        f.writelines(f"T{i}\tterm number {i}\n" for i in range(n))
+    with open(os.path.join(directory, f"{name}.taxo"), "w") as f:
+        f.writelines(f"T{int(p)}\tT{int(c)}\n" for p, c in np.asarray(edges, dtype=np.int64).reshape(-1, 2))
+    with open(os.path.join(directory, f"{name}.terms.embed"), "w") as f:
+        f.write(f"{n} {d}\n")
+        rows = np.char.add(np.char.add("T", np.arange(n).astype(str)), " ")
+        body = np.array([" ".join(r) for r in np.char.mod("%.6f", feats)])
+        f.writelines(np.char.add(np.char.add(rows, body), "\n"))
+
+
+def taxonomy_edges(tax):
+    """(parent, child) pairs of a Taxonomy, by parent"""
+    return np.stack([np.repeat(np.arange(tax.n_nodes), np.diff(tax.chd_ptr)), tax.chd_idx], 1)
+
+
 def split_candidates(tax, seed=47):
     """10 % of the leaves -> validation, 10 % -> test, the rest of the nodes = candidate anchors (dataset.py:173-179,251)."""
     rs = np.random.RandomState(seed)
