@@ -489,6 +489,35 @@ int txe_sample_anchors(const int* order, int n_order, int start, int Q, const in
                        const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k, unsigned long long seed,
                        int epoch, int repeated, int* packed, int* n_padded, void* stream);
 
+/* ---- validation-anchor sampling on device, sampling_mode 0: data_loader/dataset.py:304-307,340-355 (every parent, then at most k
+ * negatives) for the Q queries at positions start .. start+Q-1 of the epoch order.  Query i's run: node2parents[q] in order (label 1,
+ * exclude q), then the surviving negatives in slot order (label 0, exclude -1).  Negative slot j of epoch position s in round t draws
+ * pool[(hi32(h) n_pool) >> 32], h = mix64(seed ^ mix64(epoch << 44 | s << 20 | j << 6 | t)) (as txe_sample_anchors); the query keeps the
+ * unmasked draws of the first round t in 0 .. 63 that has one.  If no round has one, it keeps slot 0 of round 63 (masked) and
+ * *n_padded is incremented: every query keeps 1 .. k negatives.  The batch total B = sum of the runs is known on the device only:
+ * *total = B, packed [4B + 1] is laid out as txe_sample_anchors' (repeated: [3B, 3B+Q+1) the run offsets), labels [B] int64.
+ * cap: the caller's capacity, >= sum of |parents| + Q k (packed holds 4 cap + 1 ints, labels cap); a B above it writes nothing but
+ * *total.  ws: 3Q + 1 ints of scratch.  Three launches (count, scan, fill) on `stream`.
+ * TXE_ERR_ARG (before any device work): a NULL pointer, k < 1 or k >= 2^14, Q < 0, n_pool < 1, start < 0, start + Q > n_order or > 2^24,
+ * epoch outside [0, 2^20), cap < Q, 4 cap + 1 >= 2^31. */
+int txe_sample_groups(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                      const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int k, unsigned long long seed, int epoch,
+                      int repeated, int cap, int* packed, long long* labels, int* total, int* ws, int* n_padded, void* stream);
+
+/* ---- grouped ranking of a labelled batch: model/metric.py:33-60 (obtain_ranks) on the device.  score [B] fp32, labels [B] int32
+ * (label_bytes 4) or int64 (8).  Groups start at 0 and at every 0 -> 1 label transition; the rank of a positive (label 1) is 1 + the
+ * negatives (label != 1) of its group strictly better in fp32 (mode 0: smaller, 1: larger; NaN and ties never count; a group without
+ * negatives gives rank 1).  Writes ranks [n_pos], pos_off [n_groups + 1] (capacities B and B + 1) and counts [2] = {n_groups, n_pos};
+ * nothing is read back.  TXE_ERR_ARG: a NULL pointer, B < 1, label_bytes not 4 or 8, mode not 0 or 1; TXE_ERR_WORKSPACE: ws_bytes below
+ * txe_group_rank_ws_bytes(B). */
+size_t txe_group_rank_ws_bytes(int B);
+int txe_group_rank(const float* score, const void* labels, int label_bytes, int B, int mode, int* ranks, int* pos_off, int* counts, void* ws,
+                   size_t ws_bytes, void* stream);
+/* the metrics of one txe_group_rank result (model/metric.py:62-96), added in one launch to acc [n_which + 2] fp64: acc[m] += metric
+ * (which >> 4m) & 15 for m < n_which (0 macro_mr, 1 micro_mr, 2 hit_at_1, 3 hit_at_3, 4 hit_at_5, 5 mrr_scaled_10, 6 combined_metrics),
+ * acc[n_which] += n_groups, acc[n_which + 1] += n_pos.  TXE_ERR_ARG: a NULL pointer, n_which outside [1, 16], an id above 6. */
+int txe_group_metrics(const int* ranks, const int* pos_off, const int* counts, unsigned long long which, int n_which, double* acc, void* stream);
+
 /* ---- optional per-kernel timing (debug / bench): HIP events on the launch stream around every kernel launch, with the
  * algorithmic work (flops or compulsory bytes) its launcher attributes to it.  Global state (see the conventions at the top); off by
  * default.  txe_profile_get synchronises on record i's events. */

@@ -116,6 +116,10 @@ SIGNATURES = {
     "txe_egonet_offsets": (I, [P, P, P, P, P, I, I, U64, I, P, P, SZ, P]),
     "txe_egonet_fill": (I, [P, P, P, P, P, P, I, I, U64, I, P, P, P, P, P, P, P, P, P, P]),
     "txe_sample_anchors": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P]),
+    "txe_sample_groups": (I, [P, I, I, I, P, P, P, P, P, P, I, I, U64, I, I, I, P, P, P, P, P, P]),
+    "txe_group_rank_ws_bytes": (SZ, [I]),
+    "txe_group_rank": (I, [P, P, I, I, I, P, P, P, P, SZ, P]),
+    "txe_group_metrics": (I, [P, P, P, U64, I, P, P]),
     "txe_info_nce": (I, [P, L, I, I, P, P, P, L, P]),
     "txe_adam_step": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P]),
     "txe_dropout_uniform_host": (F, [U64, U64]),

@@ -87,6 +87,149 @@ __global__ __launch_bounds__(256) void sample_anchors_kernel(const int* __restri
     }
 }
 
+// ---- sampling_mode 0 (data_loader/dataset.py:304-307,340-355): every parent of the query (label 1), then AT MOST k negatives (label 0).
+// Negative slot j of the query at epoch position s in round t draws pool[(hi32(h) * n_pool) >> 32], h = mix64(seed ^ mix64(ctr(epoch, s,
+// j, t))) -- the hash above -- and the query keeps, in slot order, the draws of round t that are not in its mask row (the reference
+// drops masked entries of its k-wide queue window).  Round 0 is used unless all k of its draws are masked; then all k slots are redrawn in
+// round 1, and so on.  When SAMPLE_TRIES rounds leave no survivor, the query keeps slot 0 of the last round (masked) and counts itself in
+// n_padded.  (The reference's `while True` spins forever on such a window; the host sampler raises.)
+// Three launches: count (one wave per query: the round and its survivor count), scan (one workgroup: per-query offsets and the batch
+// total B, on the device), fill (one wave per query, the same draws again, written compacted at the final layout stride B).
+__device__ __forceinline__ int group_draw(unsigned long long seed, int epoch, int s, int j, int t, const int* __restrict__ pool, int n_pool) {
+    const uint64_t h = mix64(seed ^ mix64(sample_ctr(epoch, s, j, t)));
+    return pool[(int)(((h >> 32) * (uint64_t)n_pool) >> 32)];
+}
+
+__device__ __forceinline__ bool unmasked(const int* __restrict__ mrow, int mn, int a) {
+    const int at = lower_bound(mrow, mn, a);
+    return !(at < mn && mrow[at] == a);
+}
+
+__global__ __launch_bounds__(256) void sample_groups_count_kernel(const int* __restrict__ order, int start, int Q, const int* __restrict__ node_list,
+                                                                  const int* __restrict__ par_ptr, const int* __restrict__ mask_ptr,
+                                                                  const int* __restrict__ mask_idx, const int* __restrict__ pool, int n_pool, int k,
+                                                                  unsigned long long seed, int epoch, int* __restrict__ qcnt,
+                                                                  int* __restrict__ qround, int* __restrict__ n_padded) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + w;
+    if (i >= Q) return;                               // (wave-uniform: every lane of a live wave takes part in the ballots)
+    const int s = start + i;
+    const int q = node_list[order[s]];
+    const int mb = mask_ptr[q], mn = mask_ptr[q + 1] - mb;
+    const int* mrow = mask_idx + mb;
+    int t = 0, n = 0;
+    for (; t < SAMPLE_TRIES; ++t) {
+        n = 0;
+        for (int j0 = 0; j0 < k; j0 += 64) {
+            const int j = j0 + l;
+            const bool ok = j < k && unmasked(mrow, mn, group_draw(seed, epoch, s, j, t, pool, n_pool));
+            n += __popcll(__ballot(ok));
+        }
+        if (n > 0) break;
+    }
+    if (l == 0) {
+        if (n == 0) {                                 // t == SAMPLE_TRIES: one padded (masked) negative
+            atomicAdd(n_padded, 1);
+            n = 1;
+        }
+        qcnt[i] = par_ptr[q + 1] - par_ptr[q] + n;
+        qround[i] = t;
+    }
+}
+
+// exclusive scan of qcnt [Q] into qoff [Q + 1] by one workgroup of 1024 threads; *total = qoff[Q] = B
+__global__ __launch_bounds__(1024) void sample_groups_scan_kernel(const int* __restrict__ qcnt, int Q, int* __restrict__ qoff, int* __restrict__ total) {
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+    int carry = 0;
+    for (int b0 = 0; b0 < Q; b0 += 1024) {
+        const int i = b0 + tid;
+        const int v = i < Q ? qcnt[i] : 0;
+        int x = v;                                    // inclusive scan inside the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(x, d);
+            if (l >= d) x += y;
+        }
+        if (l == 63) wsum[w] = x;
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int u = 0; u < 16; ++u) {
+            before += (u < w) ? wsum[u] : 0;
+            all += wsum[u];
+        }
+        if (i < Q) qoff[i] = carry + before + x - v;
+        carry += all;
+        __syncthreads();                              // (wsum is rewritten by the next chunk)
+    }
+    if (tid == 0) {
+        qoff[Q] = carry;
+        *total = carry;
+    }
+}
+
+__global__ __launch_bounds__(256) void sample_groups_fill_kernel(const int* __restrict__ order, int start, int Q, const int* __restrict__ node_list,
+                                                                 const int* __restrict__ par_ptr, const int* __restrict__ par_idx,
+                                                                 const int* __restrict__ mask_ptr, const int* __restrict__ mask_idx,
+                                                                 const int* __restrict__ pool, int n_pool, int k, unsigned long long seed, int epoch,
+                                                                 int repeated, int cap, const int* __restrict__ qoff,
+                                                                 const int* __restrict__ qround, const int* __restrict__ total,
+                                                                 int* __restrict__ packed, long long* __restrict__ labels) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + w;
+    const int B = *total;
+    if (i >= Q || B < 0 || B > cap) return;           // (a capacity below the batch writes nothing: the caller checks B <= cap)
+    const int s = start + i;
+    const int q = node_list[order[s]];
+    const int base = qoff[i];
+    int* anchors = packed;
+    int* exclude = packed + B;
+    int* qids = packed + 2 * B;
+    const int pb = par_ptr[q], np_ = par_ptr[q + 1] - pb;
+    for (int c = l; c < np_; c += 64) {               // the positives: node2parents[q] in order
+        const int o = base + c;
+        anchors[o] = par_idx[pb + c];
+        exclude[o] = q;
+        labels[o] = 1;
+        if (!repeated) qids[o] = q;
+    }
+    const int t = qround[i];
+    int o = base + np_;
+    if (t >= SAMPLE_TRIES) {                          // padded: slot 0 of the last round
+        if (l == 0) {
+            anchors[o] = group_draw(seed, epoch, s, 0, SAMPLE_TRIES - 1, pool, n_pool);
+            exclude[o] = -1;
+            labels[o] = 0;
+            if (!repeated) qids[o] = q;
+        }
+    } else {
+        const int mb = mask_ptr[q], mn = mask_ptr[q + 1] - mb;
+        const int* mrow = mask_idx + mb;
+        for (int j0 = 0; j0 < k; j0 += 64) {          // the survivors of round t, compacted in slot order
+            const int j = j0 + l;
+            int a = 0;
+            bool ok = false;
+            if (j < k) {
+                a = group_draw(seed, epoch, s, j, t, pool, n_pool);
+                ok = unmasked(mrow, mn, a);
+            }
+            const unsigned long long m = __ballot(ok);
+            if (ok) {
+                const int p = o + __popcll(m & ((1ull << l) - 1ull));
+                anchors[p] = a;
+                exclude[p] = -1;
+                labels[p] = 0;
+                if (!repeated) qids[p] = q;
+            }
+            o += __popcll(m);
+        }
+    }
+    if (repeated && l == 0) {                         // one run per query: the distinct id and the run's first pair
+        qids[i] = q;
+        packed[3 * B + i] = base;
+        if (i == Q - 1) packed[3 * B + Q] = B;
+    }
+}
+
 }  // namespace txe
 
 using namespace txe;
@@ -103,6 +246,30 @@ int txe_sample_anchors(const int* order, int n_order, int start, int Q, const in
     if (Q == 0) return TXE_OK;
     hipLaunchKernelGGL(sample_anchors_kernel, dim3((Q + 3) / 4), dim3(256), 0, (hipStream_t)stream, order, start, Q, node_list, par_ptr,
                        par_idx, mask_ptr, mask_idx, pool, n_pool, pos_ptr, k, seed, epoch, repeated, packed, n_padded);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
+int txe_sample_groups(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                      const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int k, unsigned long long seed, int epoch,
+                      int repeated, int cap, int* packed, long long* labels, int* total, int* ws, int* n_padded, void* stream) {
+    if (!order || !node_list || !par_ptr || !par_idx || !mask_ptr || !mask_idx || !pool || !packed || !labels || !total || !ws || !n_padded)
+        return TXE_ERR_ARG;
+    if (k < 1 || k >= (1 << 14) || Q < 0 || n_pool < 1 || n_order < 0 || start < 0 || epoch < 0 || epoch >= (1 << 20)) return TXE_ERR_ARG;
+    if ((long long)start + Q > n_order || (long long)start + Q > (1 << 24)) return TXE_ERR_ARG;
+    if (cap < Q || 4LL * cap + 1 > 0x7fffffffLL) return TXE_ERR_ARG;
+    if (Q == 0) return TXE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    int* qcnt = ws;
+    int* qround = ws + Q;
+    int* qoff = ws + 2 * Q;
+    hipLaunchKernelGGL(sample_groups_count_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, order, start, Q, node_list, par_ptr, mask_ptr, mask_idx,
+                       pool, n_pool, k, seed, epoch, qcnt, qround, n_padded);
+    TXE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sample_groups_scan_kernel, dim3(1), dim3(1024), 0, s, qcnt, Q, qoff, total);
+    TXE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sample_groups_fill_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, order, start, Q, node_list, par_ptr, par_idx, mask_ptr,
+                       mask_idx, pool, n_pool, k, seed, epoch, repeated, cap, qoff, qround, total, packed, labels);
     TXE_CHECK_LAUNCH();
     return TXE_OK;
 }

@@ -206,7 +206,12 @@ class DeviceBatchLoader:
     sampler="device" (sampling_mode 1, train / validation): sampler.DeviceAnchorSampler draws them on the side stream in one launch per
     batch -- no host work per pair, no upload per batch (the epoch order goes up once per epoch), labels a cached device tensor.  Its
     positives walk the same pointers as the host sampler, starting from the dataset's node2positive_pointer when the loader is made; the
-    host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py)."""
+    host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py).
+    sampler="device" on a sampling_mode 0 dataset (validation batches of the shipped configs; train / validation): sampler.DeviceGroupSampler
+    draws every parent and at most negative_size negatives per query, labels an int64 device tensor.  The batch size B is then known on
+    the device only, so three batches are in flight: each next() after the first finishes batch b (its node count, read back one next()
+    ago), begins the egonet count of batch b+1 (its B, read back one next() ago) and samples batch b+2 -- no next() waits on work it
+    enqueued itself."""
 
     def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host"):
         if sampler not in ("host", "device"):
@@ -218,7 +223,10 @@ class DeviceBatchLoader:
         self.features = self.dtax.features
         self._side = torch.cuda.Stream(device=self.device)
         self.sampler = None
-        if sampler == "device":
+        if sampler == "device" and dataset.sampling_mode == 0:
+            from .sampler import DeviceGroupSampler
+            self.sampler = DeviceGroupSampler(dataset, self.device, seed=self.seed, dtax=self.dtax)
+        elif sampler == "device":
             from .sampler import DeviceAnchorSampler
             self.sampler = DeviceAnchorSampler(dataset, self.device, seed=self.seed, dtax=self.dtax)
             self._labels = {}
@@ -236,7 +244,9 @@ class DeviceBatchLoader:
             random.Random(self.seed + self._epoch).shuffle(order)
         self._epoch += 1
         if self.sampler is not None:
-            yield from self._iter_device(order, self._epoch - 1)
+            from .sampler import DeviceGroupSampler
+            it = self._iter_groups if isinstance(self.sampler, DeviceGroupSampler) else self._iter_device
+            yield from it(order, self._epoch - 1)
             return
         def begin(b):
             idx = order[b * self.batch_size:(b + 1) * self.batch_size]
@@ -274,3 +284,22 @@ class DeviceBatchLoader:
             batch = finish_device_batch(pending, self.features)
             nxt = begin(b + 1) if b + 1 < len(self) else None
             yield batch["g"], batch["x"], batch["qf"], self._label(Q)
+
+    def _iter_groups(self, order, epoch):
+        """sampling_mode 0: sample b+2, begin the egonet count of b+1, finish b (see the class docstring)"""
+        n, bs, nb = len(order), self.batch_size, len(self)
+        order_dev = self.sampler.upload_order(order, self._side)
+        main = torch.cuda.current_stream(self.device)
+        sample = lambda b: self.sampler.sample(order_dev, b * bs, min(bs, n - b * bs), epoch, self.repeated_queries, self._side)
+        begin = lambda b, sampled: self.sampler.egonet_begin(sampled, egonet_seed=self.seed + 7919 * self._epoch + b)
+        sampled = [sample(b) for b in range(min(nb, 2))]
+        nxt = begin(0, sampled.pop(0)) if nb else None
+        for b in range(nb):
+            pending, labels = nxt
+            batch = finish_device_batch(pending, self.features)
+            if self._side is not main:
+                labels.record_stream(main)
+            nxt = begin(b + 1, sampled.pop(0)) if b + 1 < nb else None
+            if b + 2 < nb:
+                sampled.append(sample(b + 2))
+            yield batch["g"], batch["x"], batch["qf"], labels

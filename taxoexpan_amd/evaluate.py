@@ -163,3 +163,51 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
             for q, parents in out:
                 fout.write(f"{q}\t{', '.join(parents)}\n")
     return out
+
+
+VALIDATION_METRICS = ("macro_mr", "micro_mr", "hit_at_1", "hit_at_3", "mrr_scaled_10")
+
+
+def validate(model, loader, metrics=VALIDATION_METRICS, larger_is_better=True):
+    """trainer.py:96-124 (Trainer._valid_epoch) on the device: model.eval() and no_grad over every batch of `loader` (the training flag
+    is restored after), then per batch the forward, the grouped ranks (metric.obtain_ranks, csrc/txe_grouprank.hip) and the requested
+    metrics of the batch, added in one launch to an fp64 device accumulator; ONE host read-back per epoch.
+    loader: any iterable of (g, h, qf, label) -- DeviceBatchLoader with either sampler -- or of (g, qf, label) -- MaskedGraphDataLoader's
+    small batches: h = g.ndata.pop('x'), and the tensors are moved to the model's device as trainer.py:109-112 does.
+    Returns dict(val_metrics=[mean over batches, in the order of `metrics`], n_batches, n_groups, n_positives)."""
+    from . import _lib
+    from .metric import METRIC_IDS, _check_batch, _device_group_ranks
+    metrics = list(metrics)
+    if not 1 <= len(metrics) <= 16 or any(m not in METRIC_IDS for m in metrics):
+        raise ValueError(f"metrics must be 1 to 16 names out of {sorted(METRIC_IDS)}, got {metrics}")
+    which = sum(METRIC_IDS[m] << (4 * i) for i, m in enumerate(metrics))
+    mode = 1 if larger_is_better else 0
+    dev = next(model.parameters()).device
+    acc = torch.zeros(len(metrics) + 2, dtype=torch.float64, device=dev)
+    n_batches = 0
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for batch in loader:
+                if len(batch) == 4:
+                    g, h, qf, label = batch
+                else:
+                    g, qf, label = batch
+                    h = g.ndata.pop("x")
+                h = h.to(dev, non_blocking=True)
+                qf = qf.to(dev, non_blocking=True) if torch.is_tensor(qf) else qf
+                label = label.to(dev, non_blocking=True)
+                score, label = _check_batch(model(g, h, qf), label)
+                if score.shape[0] == 0:
+                    raise ValueError("validate() got an empty batch")
+                ranks, pos_off, counts = _device_group_ranks(score, label, mode)
+                with _lib.on_device(dev):
+                    _lib.call("txe_group_metrics", _lib.ptr(ranks), _lib.ptr(pos_off), _lib.ptr(counts), which, len(metrics), _lib.ptr(acc),
+                              _lib.stream_ptr())
+                n_batches += 1
+    finally:
+        model.train(was_training)
+    host = acc.cpu().numpy()
+    vals = (host[:len(metrics)] / n_batches).tolist() if n_batches else [float("nan")] * len(metrics)
+    return dict(val_metrics=vals, n_batches=n_batches, n_groups=int(host[len(metrics)]), n_positives=int(host[len(metrics) + 1]))
