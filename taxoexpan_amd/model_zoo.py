@@ -568,7 +568,7 @@ class _Bilinear(nn.Module):
         if route == "folded":                              # hg = Z W^T never formed: the output layer's product runs on the query runs
             return e1.match_folded(W, ex, e2)
         if route == "expand":                              # the eval loop's `nf.expand(n_position, -1)` (test_fast.py:122-123)
-            return ops.score_block(e2[:1], ops.bilinear_project(_graph_vector(e1), W), ex).reshape(-1, 1)
+            return ops.score_block(e2[:1], ops.bilinear_prepare(_graph_vector(e1), W), ex).reshape(-1, 1)
         # pair form: V = e2 W^T needs neither the graph nor the encoder -- with the encoder not launched yet it goes to the second stream
         lazy = isinstance(e1, DeferredGraphVector) and not e1.started()
         pre = ops.bilinear_query_prefetch(e2, W) if (route == "pair" and lazy and torch.is_grad_enabled()) else None

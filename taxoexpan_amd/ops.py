@@ -1601,8 +1601,26 @@ class BilinearFoldedRunsFunction(torch.autograd.Function):
 # ================================================================================================================
 # inference-side helpers (no autograd)
 # ================================================================================================================
-def bilinear_project(hg, W):
-    """U = hg @ W[0]  (G x r): the factored half of the bilinear form, computed once per candidate set."""
+class BilinearPrepared:
+    """the candidate side of a BIM / LBM matcher, once per candidate set: full [max(G, 1), rp] = hg W with every row zero-padded to rp
+    columns (U = full[:G, :r]); planes = its packed bf16 planes for the split route, or None (the C side then packs per call); version
+    = full._version when they were packed -- a later in-place write to U leaves them stale, and _planes() stops handing them out"""
+    __slots__ = ("full", "G", "r", "rp", "planes", "version", "__weakref__")
+
+    def __init__(self, full, G, r, rp, planes, version):
+        self.full, self.G, self.r, self.rp, self.planes, self.version = full, G, r, rp, planes, version
+
+    @property
+    def U(self):
+        return self.full[:self.G, :self.r]
+
+    def gather(self, idx):
+        """the rows idx, gathered WITH their zero padding (a plain U[idx] of r = 250 is a packed copy: 8-byte rows, a ragged last k-tile)"""
+        return BilinearPrepared(self.full.index_select(0, idx), int(idx.numel()), self.r, self.rp, None, 0)
+
+
+def bilinear_prepare(hg, W):
+    """U = hg @ W[0]  (G x r): the factored half of the bilinear form, computed once per candidate set.  Returns BilinearPrepared."""
     _need_cuda(hg, W)
     hg, ld = _rows(hg)
     Wf = _f32(W).reshape(W.shape[-2], W.shape[-1])
@@ -1612,7 +1630,6 @@ def bilinear_project(hg, W):
     # loader (r = 250 would leave a ragged last tile on the generic one); zeros add exactly nothing to the products
     rp = (r + 31) // 32 * 32
     Ufull = _empty((max(G, 1), rp), hg)
-    U = Ufull[:G, :r]
     if rp != r:
         # the WEIGHT is padded instead of U: W [l][r] -> [l][rp] with zero columns (0.5 MB), so the product writes U's zero padding
         # itself and reads a 16-byte-aligned operand (rows of 250 floats are only 8-byte aligned: the two-float loader ran this GEMM
@@ -1620,77 +1637,90 @@ def bilinear_project(hg, W):
         Wp = torch.zeros((l, rp), dtype=torch.float32, device=hg.device)
         Wp[:, :r].copy_(Wf)
         Wf = Wp
+    planes = None
     with _lib.on_device(hg.device):
         swb = 0 if (_NO_SPLIT_GEMM or G < 1) else pure("txe_gemm_plain_split_ws_bytes", G, rp, l)
         sws = _ws(swb, hg) if swb else None
         call("txe_bilinear_project", ptr(hg), ld, G, l, ptr(Wf), rp, ptr(Ufull), rp, ptr(sws), swb, _lib.stream_ptr())
-    _ZERO_PADDED[U.data_ptr()] = (rp, weakref.ref(Ufull))
-    if not _NO_SPLIT_GEMM and G >= 1:
-        # the candidates' bf16 planes for the scoring loop, once per candidate set (every score_* call on this U finds them: the loop
-        # over query blocks packs only its queries).  U is never written after this point -- the planes ARE this U.
-        with _lib.on_device(hg.device):
+        if not _NO_SPLIT_GEMM and G >= 1:
+            # the candidates' bf16 planes for the scoring loop, once per candidate set: the loop over query blocks packs only its queries
             planes = torch.empty(pure("txe_split_packed_bytes", G, rp), dtype=torch.uint8, device=hg.device)
             call("txe_split_pack", ptr(Ufull), rp, G, rp, 1, ptr(planes), _lib.stream_ptr())
-        key = U.data_ptr()
-        _PACKED_U[key] = (rp, G, weakref.ref(Ufull, lambda _ref, key=key: _PACKED_U.pop(key, None)), planes)    # (the planes die with their U)
+    return BilinearPrepared(Ufull, G, r, rp, planes, Ufull._version)
+
+
+def bilinear_project(hg, W):
+    """bilinear_prepare() as the [G, r] tensor U.  The tensor carries its BilinearPrepared (attribute `prepared`): the score_* functions
+    find the padded pitch and the planes on this very tensor -- not on a slice, a view or a copy of it.  (U -> prepared -> full and no
+    way back: dropping U frees the buffer and the planes at once.)"""
+    prep = bilinear_prepare(hg, W)
+    U = prep.U
+    U.prepared = prep
     return U
 
 
-_ZERO_PADDED = {}      # data_ptr of a U made by bilinear_project -> (zero-padded row width, weak reference to its storage)
-_PACKED_U = {}         # ... -> (contraction width, rows, weak reference to its storage, the packed bf16 planes of side 1)
+def _as_prepared(U):
+    """the candidate side of a score_* call: a BilinearPrepared as it is; a tensor's `prepared` if the tensor still is that object's U;
+    any other tensor as an unpadded, unpacked candidate set"""
+    if isinstance(U, BilinearPrepared):
+        return U
+    prep = getattr(U, "prepared", None)
+    if prep is not None and U.data_ptr() == prep.full.data_ptr() and U.shape == (prep.G, prep.r) and U.stride() == (prep.full.stride(0), 1):
+        return prep
+    U = _rows(U)[0]
+    return BilinearPrepared(U, U.shape[0], U.shape[1], U.shape[1], None, 0)
 
 
-def _u_planes(U, r):
-    """the planes bilinear_project packed for this very U (all its rows, contraction width r), or None"""
-    ent = _PACKED_U.get(U.data_ptr())
-    if ent is None or _NO_SPLIT_GEMM:
-        return None
-    rp, G, ref, planes = ent
-    if ref() is None:
-        del _PACKED_U[U.data_ptr()]
-        return None
-    return planes if (rp == r and U.shape[0] == G and U.stride(0) == rp) else None
-
-
-def _padded_width(U, r):
-    """row width up to which U's columns beyond r are known zeros (bilinear_project output), else r"""
-    ent = _ZERO_PADDED.get(U.data_ptr())
-    if ent is None:
-        return r
-    rp, ref = ent
-    if ref() is None:                                   # the buffer died; the address may have been reused
-        del _ZERO_PADDED[U.data_ptr()]
-        return r
-    return rp if (U.stride(0) == rp and U.shape[1] == r) else r
+def _planes(prep, K):
+    """the packed planes of prep's rows for a reduction over K columns, or None: they cover the padded width, and they are the rows'
+    only while nothing has written to the buffer since the pack"""
+    ok = prep.planes is not None and K == prep.rp and prep.full._version == prep.version and not _NO_SPLIT_GEMM
+    return prep.planes if ok else None
 
 
 def gather_padded_rows(U, idx):
-    """U[idx] for a bilinear_project output, gathered WITH its zero padding: the result is again a [n, r] view of a [n, rp] buffer that
-    score kernels take on the plain 16-byte loader (a plain U[idx] is a packed [n, 250] copy: 8-byte rows, a ragged last k-tile)"""
-    ent = _ZERO_PADDED.get(U.data_ptr())
-    full = ent[1]() if ent is not None else None
-    if full is None or U.stride(0) != ent[0]:
-        return U.index_select(0, idx)
-    out_full = full.index_select(0, idx)
-    out = out_full[:, :U.shape[1]]
-    if len(_ZERO_PADDED) > 256:                         # (entries of buffers that died)
-        for k in [k for k, v in _ZERO_PADDED.items() if v[1]() is None]:
-            del _ZERO_PADDED[k]
-    _ZERO_PADDED[out.data_ptr()] = (ent[0], weakref.ref(out_full))
-    return out
+    """U[idx] for a bilinear_project output, gathered WITH its zero padding (BilinearPrepared.gather), for positive_scores_staircase"""
+    return _as_prepared(U).gather(idx)
 
 
-def _pad_queries(Q, r, rp):
-    """queries on the same zero-padded pitch as U"""
-    Qp = torch.zeros((Q.shape[0], rp), dtype=torch.float32, device=Q.device)
-    Qp[:, :r].copy_(Q)
-    return Qp
+def _query_layout(nq, r, ldq, rp, q_padded):
+    """what a score kernel's query operand needs: nq queries of r columns on a pitch of ldq floats against candidates whose rows are
+    zero-padded to rp columns.  Returns (what to do, the contraction width K, the pitch afterwards).  Every fused route promises the
+    bits of every other one: they all take K and the loader (the pitch) from here."""
+    if nq > 0 and rp != r:                              # both operands zero-padded to whole k-tiles: K = rp, the plain 16-byte loader
+        return ("padded", rp, ldq) if q_padded else ("pad", rp, rp)
+    if nq > 0 and ldq % 4 != 0:                         # rows re-laid on a 16-byte pitch (a few hundred KB per block)
+        return "relay", r, (r + 3) // 4 * 4
+    return "as_is", r, ldq
+
+
+def _lay_queries(Q, prep, q_padded=False):
+    """Q as _query_layout asks: (Q, ldq, K).  q_padded: Q is a row block of pad_queries_like(all queries, U) -- fp32, its columns up
+    to the candidates' padded width zeros already; the pointer is taken as it is."""
+    if q_padded:
+        assert Q.dtype == torch.float32 and Q.dim() == 2 and Q.stride(1) == 1, "q_padded: a row block of pad_queries_like()"
+    else:
+        Q = _rows(Q)[0]
+    nq, r = Q.shape
+    assert r == prep.r, "the queries' width != the candidates'"
+    how, K, ldq = _query_layout(nq, r, Q.stride(0), prep.rp, q_padded)
+    if how == "padded":
+        assert ldq == prep.rp, "q_padded: a row block of pad_queries_like()"
+    elif how == "pad":
+        Qp = torch.zeros((nq, prep.rp), dtype=torch.float32, device=Q.device)
+        Qp[:, :r].copy_(Q)
+        Q = Qp
+    elif how == "relay":
+        Qp = _empty((nq, ldq), Q)[:, :r]
+        Qp.copy_(Q)
+        Q = Qp
+    return Q, ldq, K
 
 
 def _score_sws(nq, G, r, ref, u_packed=False):
     """scratch with which a scoring entry point runs on the bf16 matrix pipe: (tensor, bytes), or (None, 0) on the fp32-MFMA
     route.  The four entry points compare scores bit for bit among themselves: the switch is one module attribute for all of them.
-    u_packed: the candidates' planes exist already (_u_planes) -- room for the queries' only."""
+    u_packed: the candidates' planes exist already (_planes) -- room for the queries' only."""
     if _NO_SPLIT_GEMM or nq < 1 or G < 1:
         return None, 0
     n = (pure("txe_split_packed_bytes", int(nq), int(r)) + 255) // 256 * 256 if u_packed else pure("txe_score_split_ws_bytes", int(nq), int(G), int(r))
@@ -1698,27 +1728,19 @@ def _score_sws(nq, G, r, ref, u_packed=False):
 
 
 def score_block(Q, U, apply_exp, out=None):
-    """S[q][g] = match(hg[g], Q[q]) for a block of queries against every candidate (test_fast.py:116-123)."""
-    _need_cuda(Q, U)
-    Q, ldq = _rows(Q)
-    U, ldu = _rows(U)
-    nq, r = Q.shape
-    rp = _padded_width(U, r)
-    if rp != r and nq > 0:                              # both operands zero-padded to whole k-tiles: K = rp
-        Q = _pad_queries(Q, r, rp)
-        ldq, r = rp, rp
-    elif ldq % 4 != 0 and nq > 0:                       # query rows re-laid out on a 16-byte pitch (a few hundred KB per block)
-        Qp = _empty((nq, (r + 3) // 4 * 4), Q)[:, :r]
-        Qp.copy_(Q)
-        Q, ldq = Qp, Qp.stride(0)
-    G = U.shape[0]
+    """S[q][g] = match(hg[g], Q[q]) for a block of queries against every candidate (test_fast.py:116-123).  U: a [G, r] tensor (that of
+    bilinear_project brings its padding and planes along) or a BilinearPrepared, here and in the score_* functions below."""
+    prep = _as_prepared(U)
+    _need_cuda(Q, prep.full)
+    Q, ldq, K = _lay_queries(Q, prep)
+    nq, G = Q.shape[0], prep.G
     S = out if out is not None else _empty((nq, (G + 3) // 4 * 4), Q)[:, :G]     # 16-byte row pitch: vector stores / rank sweeps
     with _lib.on_device(Q.device):
         tws = _tail_ws(Q)
-        up = _u_planes(U, r)
-        sws, swb = _score_sws(nq, G, r, Q, up is not None)
-        call("txe_score_block", ptr(Q), ldq, nq, ptr(U), ldu, G, r, int(apply_exp), ptr(S), S.stride(0), ptr(tws), tws.numel(), ptr(sws), swb,
-             ptr(up), _lib.stream_ptr())
+        up = _planes(prep, K)
+        sws, swb = _score_sws(nq, G, K, Q, up is not None)
+        call("txe_score_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), ptr(S), S.stride(0), ptr(tws),
+             tws.numel(), ptr(sws), swb, ptr(up), _lib.stream_ptr())
     return S
 
 
@@ -1744,27 +1766,31 @@ def positive_scores(Q, U, apply_exp, pos_off, pos_idx):
 
 def pad_queries_like(Q, U):
     """the query matrix zero-padded to U's k-tile pitch, ONCE for a whole scoring loop: blocks `Qp[q0:q1, :r]` of the result go to
-    score_count_block(..., q_padded=True) without being copied again.  Returns Q itself when U carries no padding."""
-    r = Q.shape[1]
-    rp = _padded_width(_rows(U)[0], r)
-    Qr = _rows(Q)[0]                                    # fp32, unit column stride: score_count_block(q_padded=True) takes the pointer as it is
-    return _pad_queries(Qr, r, rp)[:, :r] if rp != r else Qr
+    score_count_block(..., q_padded=True) without being copied again.  Returns Q itself (fp32, unit column stride) when U carries no
+    padding: the entry points re-lay a block on an odd pitch themselves, and the staircase reads it where it lies."""
+    prep = _as_prepared(U)
+    Qr = _rows(Q)[0]
+    how = _query_layout(Qr.shape[0], Qr.shape[1], Qr.stride(0), prep.rp, False)[0]
+    return _lay_queries(Qr, prep)[0][:, :prep.r] if how == "pad" else Qr
 
 
 def positive_scores_staircase(Q, Up, apply_exp, pos_off, out):
     """out[j] = match(Q[q], Up[j]) for j in [pos_off[q], pos_off[q+1]): Up holds the candidate rows of the queries' true parents, query
-    by query.  The score kernel's own tiles (bit-identical values), only those along the staircase (txe_score_positives)."""
-    _need_cuda(Q, Up)
+    by query (a tensor, or BilinearPrepared.gather's result).  The score kernel's own tiles (bit-identical values), only those along
+    the staircase (txe_score_positives).  The queries are read where they lie, on any pitch: of _query_layout's answers only 'both
+    operands padded' (pad_queries_like + gather) applies -- the whole reduction on the plain loader, the very k-tiles
+    txe_score_count_block runs."""
+    prep = _as_prepared(Up)
+    _need_cuda(Q, prep.full)
+    assert Q.dtype == torch.float32 and Q.stride(1) == 1 and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= prep.G
+    nq, r = Q.shape
     ldq = Q.stride(0)
-    Up, ldu = _rows(Up)
-    assert Q.dtype == torch.float32 and Q.stride(1) == 1 and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= Up.shape[0]
-    r = Q.shape[1]
-    rp = _padded_width(Up, r)
-    if rp != r and ldq == rp:            # both operands carry zeros up to the same k-tile pitch (pad_queries_like / gather_padded_rows): the
-        r = rp                           # whole reduction on the plain loader -- and the very k-tiles txe_score_count_block runs
+    how, K, _ = _query_layout(nq, r, ldq, prep.rp, ldq == prep.rp)
+    if how != "padded":
+        K = r
     with _lib.on_device(Q.device):
-        sws, swb = _score_sws(Q.shape[0], Up.shape[0], r, Q)
-        call("txe_score_positives", ptr(Q), ldq, Q.shape[0], ptr(Up), ldu, Up.shape[0], r, int(apply_exp), ptr(pos_off), ptr(out),
+        sws, swb = _score_sws(nq, prep.G, K, Q)
+        call("txe_score_positives", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), prep.G, K, int(apply_exp), ptr(pos_off), ptr(out),
              ptr(sws), swb, _lib.stream_ptr())
     return out
 
@@ -1773,25 +1799,10 @@ def score_count_block(Q, U, apply_exp, pos_off, thr, larger_is_better=True, coun
     """fused scoring + ranking of one query block against a candidate (shard) matrix U: int32 counts [n_pos] of candidates that beat
     each positive's score thr[j] (txe_score_count_block; no [nq x G] score block is materialised).
     q_padded: Q is a row block of pad_queries_like(all queries, U) -- its columns up to U's padded width are zeros already."""
-    _need_cuda(Q, U)
-    if q_padded:
-        assert Q.dtype == torch.float32 and Q.dim() == 2 and Q.stride(1) == 1, "q_padded: a row block of pad_queries_like()"
-        ldq = Q.stride(0)
-    else:
-        Q, ldq = _rows(Q)
-    U, ldu = _rows(U)
-    nq, r = Q.shape
-    rp = _padded_width(U, r)
-    if q_padded and rp != r and nq > 0:
-        assert ldq == rp and Q.stride(1) == 1, "q_padded: a row block of pad_queries_like()"
-        r = rp
-    elif rp != r and nq > 0:
-        Q = _pad_queries(Q, r, rp)
-        ldq, r = rp, rp
-    elif ldq % 4 != 0 and nq > 0:
-        Qp = _empty((nq, (r + 3) // 4 * 4), Q)[:, :r]
-        Qp.copy_(Q)
-        Q, ldq = Qp, Qp.stride(0)
+    prep = _as_prepared(U)
+    _need_cuda(Q, prep.full)
+    Q, ldq, K = _lay_queries(Q, prep, q_padded)
+    nq, G = Q.shape[0], prep.G
     pos_off = _i32(pos_off, Q.device)
     thr = _f32(thr)
     if counts is None:
@@ -1800,11 +1811,21 @@ def score_count_block(Q, U, apply_exp, pos_off, thr, larger_is_better=True, coun
         return counts
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
     with _lib.on_device(Q.device):
-        up = _u_planes(U, r)
-        sws, swb = _score_sws(nq, U.shape[0], r, Q, up is not None)
-        call("txe_score_count_block", ptr(Q), ldq, nq, ptr(U), ldu, U.shape[0], r, int(apply_exp), ptr(pos_off), ptr(thr),
+        up = _planes(prep, K)
+        sws, swb = _score_sws(nq, G, K, Q, up is not None)
+        call("txe_score_count_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), ptr(pos_off), ptr(thr),
              int(larger_is_better), ptr(counts), ptr(sws), swb, ptr(up), _lib.stream_ptr())
     return counts
+
+
+def _topk_scratch(sc, nq, need, ref):
+    """the best-k entry points' per-tile lists (key fp32 / idx int32 [need]) and floors (int32 [nq]) in the dict a loop over blocks
+    passes along (None: for this call only), grown when a block needs more or the device changed"""
+    sc = sc if sc is not None else {}
+    if sc.get("n", 0) < need or sc.get("nq", 0) < nq or sc["key"].device != ref.device:
+        sc["key"], sc["idx"], sc["n"] = _empty((need,), ref), torch.empty(need, dtype=torch.int32, device=ref.device), need
+        sc["floor"], sc["nq"] = torch.empty(nq, dtype=torch.int32, device=ref.device), nq
+    return sc
 
 
 def score_topk_block(Q, U, apply_exp, k, larger_is_better=True, idx_base=0, q_padded=False, scratch=None):
@@ -1812,42 +1833,22 @@ def score_topk_block(Q, U, apply_exp, k, larger_is_better=True, idx_base=0, q_pa
     (idx int32 [nq, k] = candidate rows + idx_base, best first, ties by ascending row like Python's stable sort, NaN last;
     key fp32 [nq, k] = the scores, negated when smaller is better).  No [nq x G] block is materialised.  1 <= k <= min(8, G).
     q_padded: as in score_count_block.  scratch: dict reused across the blocks of a loop (the per-tile lists)."""
-    _need_cuda(Q, U)
-    if q_padded:
-        assert Q.dtype == torch.float32 and Q.dim() == 2 and Q.stride(1) == 1, "q_padded: a row block of pad_queries_like()"
-        ldq = Q.stride(0)
-    else:
-        Q, ldq = _rows(Q)
-    U, ldu = _rows(U)
-    nq, r = Q.shape
-    G = U.shape[0]
+    prep = _as_prepared(U)
+    _need_cuda(Q, prep.full)
+    G = prep.G
     assert 1 <= k <= 8 and k <= G, "score_topk_block: 1 <= k <= min(8, candidates)"
-    rp = _padded_width(U, r)
-    if q_padded and rp != r and nq > 0:
-        assert ldq == rp
-        r = rp
-    elif rp != r and nq > 0:
-        Q = _pad_queries(Q, r, rp)
-        ldq, r = rp, rp
-    elif ldq % 4 != 0 and nq > 0:
-        Qp = _empty((nq, (r + 3) // 4 * 4), Q)[:, :r]
-        Qp.copy_(Q)
-        Q, ldq = Qp, Qp.stride(0)
+    Q, ldq, K = _lay_queries(Q, prep, q_padded)
+    nq = Q.shape[0]
     idx = torch.empty((nq, k), dtype=torch.int32, device=Q.device)
     key = _empty((nq, k), Q)
     if nq == 0:
         return idx, key
     with _lib.on_device(Q.device):
-        nt = pure("txe_score_topk_tiles", G)
-        up = _u_planes(U, r)
-        sws, swb = _score_sws(nq, G, r, Q, up is not None)
-        need = nq * nt * k
-        sc = scratch if scratch is not None else {}
-        if sc.get("n", 0) < need or sc.get("nq", 0) < nq or sc["key"].device != Q.device:
-            sc["key"], sc["idx"], sc["n"] = _empty((need,), Q), torch.empty(need, dtype=torch.int32, device=Q.device), need
-            sc["floor"], sc["nq"] = torch.empty(nq, dtype=torch.int32, device=Q.device), nq
-        call("txe_score_topk_block", ptr(Q), ldq, nq, ptr(U), ldu, G, r, int(apply_exp), int(larger_is_better), int(k), int(idx_base),
-             ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), ptr(sws), swb, ptr(up), _lib.stream_ptr())
+        up = _planes(prep, K)
+        sws, swb = _score_sws(nq, G, K, Q, up is not None)
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * k, Q)
+        call("txe_score_topk_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), int(larger_is_better), int(k),
+             int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), ptr(sws), swb, ptr(up), _lib.stream_ptr())
     return idx, key
 
 
@@ -2030,12 +2031,7 @@ def mlp_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=
     if nq == 0:
         return idx, key
     with _lib.on_device(dev):
-        nt = pure("txe_score_topk_tiles", G)
-        need = nq * nt * k
-        sc = scratch if scratch is not None else {}
-        if sc.get("n", 0) < need or sc.get("nq", 0) < nq or sc["key"].device != dev:
-            sc["key"], sc["idx"], sc["n"] = _empty((need,), prep.Ap), torch.empty(need, dtype=torch.int32, device=dev), need
-            sc["floor"], sc["nq"] = torch.empty(nq, dtype=torch.int32, device=dev), nq
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * k, prep.Ap)
         call("txe_mlp_score_topk_block", *_mlp_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]),
              ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
     return idx, key

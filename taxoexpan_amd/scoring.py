@@ -16,25 +16,25 @@ from . import ops
 
 
 class _PreparedBilinear:
-    """a BIM / LBM matcher over a candidate set: U = hg W once (txe_bilinear_project), every query block one GEMM with its epilogue"""
+    """a BIM / LBM matcher over a candidate set: U = hg W once (ops.bilinear_prepare), every query block one GEMM with its epilogue"""
 
     def __init__(self, match, hg):
-        self.U, self.exp = ops.bilinear_project(hg, match.W.weight), match.apply_exp
+        self.prep, self.exp = ops.bilinear_prepare(hg, match.W.weight), match.apply_exp
 
     def queries(self, Q):
-        return ops.pad_queries_like(Q, self.U)
+        return ops.pad_queries_like(Q, self.prep)
 
     def score(self, qb, out=None):
-        return ops.score_block(qb, self.U, self.exp, out=out)
+        return ops.score_block(qb, self.prep, self.exp, out=out)
 
     def positives(self, qb, off, rows, out):
-        return ops.positive_scores_staircase(qb, ops.gather_padded_rows(self.U, rows), self.exp, off, out)
+        return ops.positive_scores_staircase(qb, self.prep.gather(rows), self.exp, off, out)
 
     def count(self, qb, off, thr, larger_is_better, counts):
-        return ops.score_count_block(qb, self.U, self.exp, off, thr, larger_is_better, counts=counts, q_padded=True)
+        return ops.score_count_block(qb, self.prep, self.exp, off, thr, larger_is_better, counts=counts, q_padded=True)
 
     def topk(self, qb, k, larger_is_better, idx_base, scratch):
-        return ops.score_topk_block(qb, self.U, self.exp, k, larger_is_better, idx_base=idx_base, q_padded=True, scratch=scratch)
+        return ops.score_topk_block(qb, self.prep, self.exp, k, larger_is_better, idx_base=idx_base, q_padded=True, scratch=scratch)
 
 
 class _PreparedMLP:

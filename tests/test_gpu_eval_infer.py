@@ -376,3 +376,80 @@ def test_fused_top_k_equals_the_composite_on_materialised_scores(G, Q, k):
                     cat_k = torch.cat([p[1][:, :kk] for p in parts], 1)
                     idx, _key = ops.topk_merge(cat_k, cat_i, kk)
                     assert torch.equal(ids[idx.long()], topk_parents(S, ids, kk, larger)), (kind, larger, "shards")
+
+
+def _projected_case(monkeypatch, no_split, G=1003, r=250, l=96, nq=300):
+    """candidates whose rows carry padding (r = 250 -> 256) and, on the split route, packed planes; queries with 1-5 positives each"""
+    from taxoexpan_amd import model_zoo as mz, ops
+    monkeypatch.setattr(ops, "_NO_SPLIT_GEMM", no_split)
+    dev = _dev()
+    gen = torch.Generator().manual_seed(G + r)
+    hg = (torch.randn(G, l, generator=gen) * 0.3).to(dev)
+    Q = torch.nn.functional.normalize(torch.randn(nq, r, generator=gen), dim=1).to(dev)
+    torch.manual_seed(5)
+    match = mz.LBM(l, r).to(dev)
+    rs = np.random.RandomState(1)
+    npos = rs.randint(1, 6, size=nq)
+    pos_idx = torch.from_numpy(np.concatenate([rs.choice(G, size=k, replace=False) for k in npos]).astype(np.int64)).to(dev)
+    pos_off = np.concatenate([[0], np.cumsum(npos)]).astype(np.int64)
+    return match, hg, Q, pos_off, pos_idx
+
+
+@pytest.mark.parametrize("no_split", [False, True])
+def test_scoring_follows_an_in_place_write_to_the_projected_candidates(monkeypatch, no_split):
+    """U = bilinear_project(hg, W) brings planes packed from its rows.  After U.mul_(0.5) they are another matrix's: every entry point
+    must score the U that is there -- score_block like on a copy of it, and the ranking loop's thresholds (padded gather of the
+    positives' rows + positive_scores_staircase on pad_queries_like's queries) equal to the block's own entries, bit for bit.
+    (Before BilinearPrepared recorded the buffer's version, the block of the split route came from the stale planes and the thresholds
+    from the live rows: run once on the parent commit, the no_split=False case failed at the first assertion, the other one passed.)"""
+    from taxoexpan_amd import ops
+    match, hg, Q, pos_off, pos_idx = _projected_case(monkeypatch, no_split)
+    ex = match.apply_exp
+    with torch.no_grad():
+        U = ops.bilinear_project(hg, match.W.weight)
+        U.mul_(0.5)
+        S = ops.score_block(Q, U, ex)
+        S_copy = ops.score_block(Q, U.clone(), ex)
+        print("score_block(U) vs score_block(U.clone()): entries that differ", int((S != S_copy).sum()), "of", S.numel(),
+              "max |diff|", float((S - S_copy).abs().max()))
+        assert torch.equal(S, S_copy)
+        thr = torch.empty(pos_idx.numel(), device=_dev())
+        off32 = torch.from_numpy(pos_off.astype(np.int32)).to(_dev())
+        ops.positive_scores_staircase(ops.pad_queries_like(Q, U), ops.gather_padded_rows(U, pos_idx), ex, off32, thr)
+        qid = torch.repeat_interleave(torch.arange(Q.shape[0]), torch.from_numpy(np.diff(pos_off))).to(_dev())
+        print("staircase thresholds vs the block's entries: differ", int((thr != S[qid, pos_idx]).sum()), "of", thr.numel())
+        assert torch.equal(thr, S[qid, pos_idx])
+
+
+@pytest.mark.parametrize("no_split", [False, True])
+def test_fused_routes_agree_between_the_prepared_matcher_and_the_projected_tensor(monkeypatch, no_split):
+    """score / positives / count / top-k give the same bits whether they are reached through scoring.prepare_matcher(match, hg) (a
+    BilinearPrepared handed over) or through the tensor of ops.bilinear_project (the prepared side found on the tensor), for the
+    whole query set in one block and for blocks with a ragged last one"""
+    from taxoexpan_amd import ops, scoring
+    match, hg, Q, pos_off, pos_idx = _projected_case(monkeypatch, no_split)
+    ex, dev, nq = match.apply_exp, _dev(), Q.shape[0]
+    with torch.no_grad():
+        pm = scoring.prepare_matcher(match, hg)
+        U = ops.bilinear_project(hg, match.W.weight)
+        Qa, Qb = pm.queries(Q), ops.pad_queries_like(Q, U)
+        assert torch.equal(Qa, Qb) and Qa.stride() == Qb.stride() == (256, 1)
+        for block in (nq, 128):                                            # 300 = 128 + 128 + 44
+            for q0 in range(0, nq, block):
+                q1 = min(q0 + block, nq)
+                lo, hi = int(pos_off[q0]), int(pos_off[q1])
+                off = torch.from_numpy((pos_off[q0:q1 + 1] - lo).astype(np.int32)).to(dev)
+                rows = pos_idx[lo:hi]
+                assert torch.equal(pm.score(Q[q0:q1]), ops.score_block(Q[q0:q1], U, ex))
+                thr_a = pm.positives(Qa[q0:q1], off, rows, torch.empty(hi - lo, device=dev))
+                thr_b = ops.positive_scores_staircase(Qb[q0:q1], ops.gather_padded_rows(U, rows), ex, off, torch.empty(hi - lo, device=dev))
+                assert torch.equal(thr_a, thr_b)
+                for larger in (True, False):
+                    cnt_a = pm.count(Qa[q0:q1], off, thr_a, larger, torch.zeros(hi - lo, dtype=torch.int32, device=dev))
+                    cnt_b = ops.score_count_block(Qb[q0:q1], U, ex, off, thr_b, larger, q_padded=True)
+                    cnt_c = ops.score_count_block(Q[q0:q1], U, ex, off, thr_b, larger)
+                    assert torch.equal(cnt_a, cnt_b) and torch.equal(cnt_a, cnt_c)
+                    top_a = pm.topk(Qa[q0:q1], 5, larger, 7, None)
+                    top_b = ops.score_topk_block(Qb[q0:q1], U, ex, 5, larger, idx_base=7, q_padded=True)
+                    top_c = ops.score_topk_block(Q[q0:q1], U, ex, 5, larger, idx_base=7)
+                    assert all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(top_a, top_b, top_c))

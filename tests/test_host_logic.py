@@ -373,3 +373,59 @@ def test_bench_compact_line_fits_the_drivers_tail_and_keeps_the_contract():
               "candidates_scored_per_s_fused_allreduce", "allgather_gbs_per_rank", "allreduce_counts_queries_per_s"):
         assert k in line8, k
     assert len(json.dumps(line8, separators=(",", ":"))) < 3500
+
+
+@pytest.mark.parametrize("args,want", [
+    # (nq, r, ldq, rp, q_padded) -> (what to do, contraction width K, query pitch afterwards)
+    ((300, 250, 250, 256, False), ("pad", 256, 256)),        # r = 250 against rows padded to 256: the queries are zero-padded too
+    ((300, 250, 256, 256, True), ("padded", 256, 256)),      # ... a block of pad_queries_like(): taken as it is, K = 256
+    ((300, 64, 64, 64, False), ("as_is", 64, 64)),           # no padding, rows on a 16-byte pitch
+    ((300, 64, 64, 64, True), ("as_is", 64, 64)),
+    ((300, 10, 10, 10, False), ("relay", 10, 12)),           # plain candidates, 40-byte query rows: re-laid on a 16-byte pitch
+    ((300, 10, 10, 10, True), ("relay", 10, 12)),
+    ((300, 10, 10, 32, False), ("pad", 32, 32)),             # (r = 10 out of bilinear_project is padded to one k-tile)
+    ((300, 10, 32, 32, True), ("padded", 32, 32)),
+    ((0, 250, 250, 256, False), ("as_is", 250, 250)),        # no query: nothing is copied, whatever the shapes
+    ((0, 250, 256, 256, True), ("as_is", 250, 256)),
+    ((0, 10, 10, 10, False), ("as_is", 10, 10)),
+])
+def test_query_layout_decision_table(args, want):
+    """the one place that decides how a query block meets the candidates (ops._query_layout): every fused route takes K and the
+    pitch from it, so that they all run the same k-tiles on the same loader"""
+    from taxoexpan_amd import ops
+    assert ops._query_layout(*args) == want
+
+
+def test_prepared_candidates_travel_on_the_very_tensor_only():
+    """ops._as_prepared: bilinear_project's tensor carries its BilinearPrepared as an attribute.  It is honoured on that tensor object
+    alone (not on a slice, a view from another row, or a copy); the packed planes are withheld after an in-place write to U; and
+    nothing but U keeps the buffer and the planes alive (no table, no reference cycle: they go with U, without a collector pass)."""
+    import gc as pygc
+    import weakref
+    from taxoexpan_amd import ops
+    G, r, rp = 7, 10, 32
+    full = torch.zeros(G, rp)
+    full[:, :r] = torch.randn(G, r)
+    planes = torch.zeros(16, dtype=torch.uint8)
+    prep = ops.BilinearPrepared(full, G, r, rp, planes, full._version)      # (as bilinear_prepare builds it; that needs the device)
+    U = prep.U
+    U.prepared = prep
+    assert ops._as_prepared(prep) is prep and ops._as_prepared(U) is prep
+    assert ops._planes(prep, rp) is planes and ops._planes(prep, r) is None
+    for other in (U[:3], U[1:], U.clone(), U[:], U.view(G, r)):
+        got = ops._as_prepared(other)
+        assert got is not prep and got.planes is None and (got.G, got.r, got.rp) == (other.shape[0], r, r)
+        assert got.full.stride(1) == 1 and torch.equal(got.U, other)
+    rows = prep.gather(torch.tensor([4, 0, 4]))
+    assert rows.planes is None and (rows.G, rows.r, rows.rp) == (3, r, rp) and torch.equal(rows.full, full[[4, 0, 4]])
+    U.mul_(1)                                                               # any in-place write: the planes no longer are U's
+    assert ops._as_prepared(U) is prep and ops._planes(prep, rp) is None
+    refs = [weakref.ref(o) for o in (prep, full, planes)]
+    pygc.disable()
+    try:
+        del prep, full, planes, got, other, rows
+        assert all(ref() is not None for ref in refs)
+        del U
+        assert all(ref() is None for ref in refs)
+    finally:
+        pygc.enable()
