@@ -681,8 +681,9 @@ int txe_gemm_plain(int layout, const float* A, long long lda, const float* B, lo
 //   y[G][O] = act([x1 | x2] W^T + b),  W [O][l+r], x2/b optional, act 0 none / 1 relu / 2 tanh.  The concat is virtual (VMat).
 int txe_linear_fwd(const float* x1, long long ld1, int l, const float* x2, long long ld2, int r, int G, const float* W, const float* b,
                    int O, int act, float* y, void* stream) {
-    if (G < 0 || l < 1 || r < 0 || O < 1 || !x1 || !W || !y || (r > 0 && !x2)) return TXE_ERR_ARG;
-    if (G == 0) return TXE_OK;
+    if (G < 0 || l < 1 || r < 0 || O < 1 || !W) return TXE_ERR_ARG;
+    if (G == 0) return TXE_OK;                                  // (no rows: the row pointers of an empty batch may be NULL)
+    if (!x1 || !y || (r > 0 && !x2)) return TXE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     VMat A = vmat_plain(x1, ld1, G, l + r);
     A.cols_main = l; A.p2 = x2; A.ld2 = ld2;
@@ -706,14 +707,20 @@ size_t txe_linear_bwd_ws_bytes(int G, int l, int r, int O) {
 int txe_linear_bwd(const float* x1, long long ld1, int l, const float* x2, long long ld2, int r, int G, const float* W, int O, int act,
                    const float* y, const float* dy, float* dx1, long long ld_dx1, float* dx2, long long ld_dx2, float* dW, float* db,
                    void* ws, size_t ws_bytes, void* stream) {
-    if (G < 0 || l < 1 || r < 0 || O < 1 || !x1 || !W || !y || !dy || !dW || !ws || (r > 0 && !x2)) return TXE_ERR_ARG;
+    if (G < 0 || l < 1 || r < 0 || O < 1 || !W || !dW || !ws) return TXE_ERR_ARG;
     if (ws_bytes < txe_linear_bwd_ws_bytes(G, l, r, O)) return TXE_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
+    if (G == 0) {                                               // an empty sum (the row pointers of an empty batch may be NULL)
+        if (hipMemsetAsync(dW, 0, (size_t)O * (l + r) * sizeof(float), s) != hipSuccess) return TXE_ERR_LAUNCH;
+        if (db && hipMemsetAsync(db, 0, (size_t)O * sizeof(float), s) != hipSuccess) return TXE_ERR_LAUNCH;
+        return TXE_OK;
+    }
+    if (!x1 || !y || !dy || (r > 0 && !x2)) return TXE_ERR_ARG;
     float* dz = (float*)ws;
-    float* part = (float*)((char*)ws + mt_align((size_t)(G > 0 ? G : 1) * O * 4));
+    float* part = (float*)((char*)ws + mt_align((size_t)G * O * 4));
     const int K = l + r;
     int rc;
-    if (G > 0) {
+    {
         const long long n = (long long)G * O;
         hipLaunchKernelGGL(act_bwd_kernel, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, s, dy, y, n, act, dz);
         TXE_CHECK_LAUNCH();
@@ -740,9 +747,8 @@ int txe_linear_bwd(const float* x1, long long ld1, int l, const float* x2, long 
     if (rc) return rc;
     const long long n = (long long)O * K;
     hipLaunchKernelGGL(reduce_splits_kernel2, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, s, (const float*)part,
-                       G > 0 ? S : 0, E.split_stride, n, dW);
+                       S, E.split_stride, n, dW);
     TXE_CHECK_LAUNCH();
-    if (db && G == 0) (void)hipMemsetAsync(db, 0, (size_t)O * 4, s);
     return TXE_OK;
 }
 

@@ -216,7 +216,11 @@ __global__ void readout_dpw_reduce_kernel(const float* __restrict__ part, int G,
 // ---- SumReadout / MaxReadout / ConcatReadout (model_zoo.py:244-276) ---------------------------------------------------
 // mode 1 SUM   : hg[g][d]       = sum_v h[v][d]
 // mode 2 MAX   : hg[g][d]       = max_v h[v][d]            (argmax[g][d] = first maximiser, for backward)
+//                NaN is pinned to torch.max's behaviour: a NaN in the column wins over every number, argmax = the FIRST NaN of the
+//                column, and the backward sends the column's gradient there (tests/test_gpu_readout_match_ops.py)
 // mode 3 CONCAT: hg[g][c*D + d] = sum_{v: pos_v == c} h[v][d] * s_c,  s_0 = s_2 = 1/n_g,  s_1 = 1/#{pos == 1}   (c < 3)
+//                formed as the reference forms it, sum_v h[v][d] * [pos_v == c] (a weighted dgl.sum_nodes): a NaN or Inf in h[v][d]
+//                makes column d of ALL three parts NaN (x * 0), not only the part of v's own class -- pinned by the same test
 // One wavefront per egonet; a lane owns RM_NB columns 64 apart, so every node costs RM_NB independent loads (first version: one
 // column at a time, one load in flight -- 126 us for the MAG batch; these variants are API completeness, not the hot path).
 constexpr int RM_NB = 8;
@@ -248,14 +252,15 @@ __global__ __launch_bounds__(RO_WAVES * 64) void readout_multi_fwd_kernel(const 
         }
         for (int v = beg; v < end; ++v) {
             const int pc = (mode == 3) ? pos[v] : 0;
+            const float m0 = (pc == 0) ? 1.f : 0.f, m1 = (pc == 1) ? 1.f : 0.f, m2 = (pc == 2) ? 1.f : 0.f;
             float x[RM_NB];
 #pragma unroll
             for (int i = 0; i < RM_NB; ++i) x[i] = h[(long long)v * ld_h + dc[i]];
 #pragma unroll
             for (int i = 0; i < RM_NB; ++i) {
                 if (mode == 1) a0[i] += x[i];
-                else if (mode == 2) { if (x[i] > a0[i]) { a0[i] = x[i]; am[i] = v; } }
-                else { a0[i] += (pc == 0) ? x[i] : 0.f; a1[i] += (pc == 1) ? x[i] : 0.f; a2[i] += (pc == 2) ? x[i] : 0.f; }
+                else if (mode == 2) { if (x[i] > a0[i] || (x[i] != x[i] && a0[i] == a0[i])) { a0[i] = x[i]; am[i] = v; } }
+                else { a0[i] = fmaf(x[i], m0, a0[i]); a1[i] = fmaf(x[i], m1, a1[i]); a2[i] = fmaf(x[i], m2, a2[i]); }
             }
         }
 #pragma unroll
