@@ -3,6 +3,7 @@
 torch is plumbing here: it owns device memory (caching allocator), the current HIP stream and autograd's tape;
 every number is produced by the hand-written HIP kernels.  There is no CPU path -- host tensors raise.
 """
+import typing
 import weakref
 
 import torch
@@ -116,7 +117,7 @@ class _CaptureList(list):
 class debug_capture:
     """`with ops.debug_capture() as runs:` -- every GAT / GCN stack forward inside the block appends (csr, cfg, states): the per-layer
     buffers of the fused stack (X = padded layer input, Y = projection output, alpha [E, H] in destination-CSR order, cl = the folded
-    output layer's (a12, alpha, coef, wsum, gid, Z, hg)).  Parity tests read the intermediates the reference exposes per layer
+    output layer's GatFolded / GcnFolded: cl.Z, cl.alpha, ...).  Parity tests read the intermediates the reference exposes per layer
     (model_zoo.py:90-95) from here; nothing is copied and nothing changes in the computation."""
 
     def __enter__(self):
@@ -311,6 +312,9 @@ class GATConfig:
         self.final = final          # 'mean' (PGAT/GAT: .mean(1) over heads of the last layer) | 'none' (GATLayer: N x H x D)
         self.seed = int(seed)
         self.n_layers = len(self.heads)
+        # what the caller of one run adds on a copy: apply_stack its grad mode; DeferredNodeOutput._collapse `final` = 'collapse' /
+        # 'collapse_z' and, for the latter, the FoldLink and the matcher's job (folded_match_job)
+        self.grad_enabled, self.link, self.fold_job = True, None, None
 
 
 def dropout_mask(n_rows, n_cols, p, seed, ref):
@@ -336,9 +340,30 @@ def _tail_ws(ref):
     return t
 
 
+class GatFolded(typing.NamedTuple):
+    """what the folded GAT output layer's forward keeps for its backward (_GatLayerState.cl): a12 [N, 2] attention logits' halves, alpha [E]
+    (destination-CSR order), coef [N] / wsum [G] of the readout, gid [N] node -> graph, Z [G, Kp], hg [G, D] (None when the stack stops at Z)"""
+    a12: torch.Tensor
+    alpha: torch.Tensor
+    coef: torch.Tensor
+    wsum: torch.Tensor
+    gid: torch.Tensor
+    Z: torch.Tensor
+    hg: typing.Optional[torch.Tensor]
+
+
 class _GatLayerState:
-    __slots__ = ("X", "Wp", "mask", "Y", "alpha", "W", "al", "ar", "P", "Kh", "Pd", "Kp", "Fp", "H", "D", "seed", "cl", "prepared", "x_dropped", "Xt",
-                 "vx")      # vx: X is NOT stored (a first layer on the bf16 pipe: the packs form dropout([h | Emb[pos]]) themselves)
+    __slots__ = ("X", "Wp", "mask", "Y", "alpha", "W", "al", "ar", "P", "pos", "Kh", "Pd", "Kp", "Fp", "H", "D", "seed", "cl", "prepared",
+                 "x_dropped", "Xt", "vx")
+
+    def __init__(self):
+        self.X = self.Wp = self.mask = self.Y = self.alpha = self.Xt = None
+        self.W = self.al = self.ar = self.P = None
+        self.pos = None             # the nodes' positions if the layer has a position table P, else None
+        self.Kh = self.Pd = self.Kp = self.Fp = self.H = self.D = self.seed = 0
+        self.cl = None              # GatFolded: the output layer folded behind the readout
+        self.prepared = self.x_dropped = False
+        self.vx = False             # X is NOT stored (a first layer on the bf16 pipe: the packs form dropout([h | Emb[pos]]) themselves)
 
 
 def _virtual_x_ok(st, h, ld_h, N, need, first_is_folded):
@@ -364,17 +389,16 @@ def _x_dropped_ok(cfg, states, l, collapse):
 
 
 def _gat_layers_prepare(items, feat_p):
-    """_gat_layer_prepare for several layers of a stack in ONE launch (txe_gat_layers_prepare): items = [(st, h, ld_h, pos, dropped)],
+    """_gat_layer_prepare for several layers of a stack in ONE launch (txe_gat_layers_prepare): items = [(st, h, ld_h, dropped)],
     st.X allocated.  A layer's preparation never depends on the layer below's output, so the whole stack is prepared before its first
     GEMM.  dropped: X is written with the feature dropout already applied (a first layer on raw features whose X only GEMMs read)."""
     import ctypes
     descs = (_lib.GatPrepareDesc * len(items))()
-    for d, (st, h, ld_h, pos, dropped) in zip(descs, items):
+    for d, (st, h, ld_h, dropped) in zip(descs, items):
         N = st.X.shape[0]
-        st.vx = getattr(st, "vx", False)
         st.Wp = _empty((st.Fp, st.Kp), st.X)
         st.mask = torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=st.X.device) if feat_p > 0.0 else None
-        d.h, d.ld_h, d.n_nodes, d.Kh, d.pos, d.P, d.Pd, d.X = ptr(h), ld_h, N, st.Kh, ptr(pos), ptr(st.P), st.Pd, (None if st.vx else ptr(st.X))
+        d.h, d.ld_h, d.n_nodes, d.Kh, d.pos, d.P, d.Pd, d.X = ptr(h), ld_h, N, st.Kh, ptr(st.pos), ptr(st.P), st.Pd, (None if st.vx else ptr(st.X))
         d.W, d.attn_l, d.attn_r, d.H, d.D, d.Wp = ptr(st.W), ptr(st.al), ptr(st.ar), st.H, st.D, ptr(st.Wp)
         d.feat_drop_p, d.seed, d.mask = feat_p, st.seed, ptr(st.mask)
         st.x_dropped = bool(dropped and feat_p > 0.0)
@@ -383,26 +407,26 @@ def _gat_layers_prepare(items, feat_p):
     call("txe_gat_layers_prepare", ctypes.cast(descs, ctypes.c_void_p), len(items), _lib.stream_ptr())
 
 
-def _gat_layer_prepare(st, h, ld_h, pos, feat_p):
+def _gat_layer_prepare(st, h, ld_h, feat_p):
     """layer input X = [h | Emb[pos] | 0] (h == None: the producer already wrote the feature columns), packed weights, keep mask"""
-    if getattr(st, "prepared", False):
+    if st.prepared:
         return
     N = st.X.shape[0]
     s = _lib.stream_ptr()
     st.Wp = _empty((st.Fp, st.Kp), st.X)
     st.mask = torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=st.X.device) if feat_p > 0.0 else None
-    call("txe_gat_layer_prepare", ptr(h), ld_h, N, st.Kh, ptr(pos), ptr(st.P), st.Pd, ptr(st.X), ptr(st.W), ptr(st.al), ptr(st.ar),
+    call("txe_gat_layer_prepare", ptr(h), ld_h, N, st.Kh, ptr(st.pos), ptr(st.P), st.Pd, ptr(st.X), ptr(st.W), ptr(st.al), ptr(st.ar),
          st.H, st.D, ptr(st.Wp), feat_p, st.seed, ptr(st.mask), s)
 
 
-def _gat_collapse_fwd(csr, st, h, ld_h, pos, rpos, pw, feat_p, attn_p, attn_slope, a12=None, z_only=False, fold_job=None, link=None):
+def _gat_collapse_fwd(csr, st, h, ld_h, rpos, pw, feat_p, attn_p, attn_slope, a12=None, z_only=False, fold_job=None, link=None):
     """output layer (one head) folded behind the weighted-mean readout: hg [G, D] (txe_gat_collapse_fwd).
     a12 given: the layer is already prepared and the previous layer's aggregation has formed its attention logits.
     z_only: stop at Z [G, Kp] (hg = Z W^T is left to the consumer: FoldedGraphLinearFunction / BilinearFoldedRunsFunction)."""
     N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
     ready = a12 is not None
     if not ready:
-        _gat_layer_prepare(st, h, ld_h, pos, feat_p)
+        _gat_layer_prepare(st, h, ld_h, feat_p)
         a12 = _empty((max(N, 1), 2), st.X)
     alpha, coef = _empty((max(E, 1),), st.X), _empty((max(N, 1),), st.X)
     wsum, Z, hg = _empty((max(G, 1),), st.X), _empty((max(G, 1), st.Kp), st.X), (None if z_only else _empty((G, st.D), st.X))
@@ -415,21 +439,20 @@ def _gat_collapse_fwd(csr, st, h, ld_h, pos, rpos, pw, feat_p, attn_p, attn_slop
     Tf = zrow = e_part = None
     if z_only and fold_job is not None and link is not None and N > 0 and G > 0 and not _NO_FOLD_EDOT:
         nt = pure("txe_gat_collapse_e_tiles", N, G, st.Kh, st.Pd)
-        fw = fold_job(st.Wp, st.D) if nt > 0 else None       # the matcher's runs, V and T, formed now: T rides in the Z sweep
-        if fw is not None:
-            Tf, zrow, e_part = fw["T"], _fold_job_run_ids(fw, G, st.X), _empty((N, nt), st.X)
-            link.fwd, link.e_part = fw, e_part
-            # (what the matcher's forward needs to sum its scores from e_part: txe_gat_collapse_fold_scores)
-            fw["score"] = (csr.graph_off, N, G, st.Kh, st.Pd, coef, wsum, feat_p, int(st.mask is not None and feat_p > 0.0))
+        job = fold_job(st.Wp, st.D) if nt > 0 else None      # the matcher's runs, V and T, formed now: T rides in the Z sweep
+        if job is not None:
+            Tf, zrow, e_part = job.T, job.run_ids(G), _empty((N, nt), st.X)
+            link.fwd, link.e_part = job, e_part
+            job.score = FoldScore(csr.graph_off, N, G, st.Kh, st.Pd, coef, wsum, feat_p, int(st.mask is not None and feat_p > 0.0))
     call("txe_gat_collapse_fwd", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
          ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(st.Wp), st.D, feat_p, ptr(st.mask), attn_slope, attn_p, st.seed + 1,
          ptr(rpos), ptr(pw), ptr(a12), int(ready) | (2 if split_hg else 0), ptr(alpha), ptr(coef), ptr(wsum), ptr(gid), ptr(Z), ptr(hg), st.D, ptr(Tf), ptr(zrow),
          ptr(e_part), ptr(ws), wsb, _lib.stream_ptr())
-    st.cl = (a12, alpha, coef, wsum, gid, Z, hg)
+    st.cl = GatFolded(a12, alpha, coef, wsum, gid, Z, hg)
     return Z if z_only else hg
 
 
-def _gat_collapse_bwd(csr, st, pos, rpos, pw, vocab, feat_p, attn_p, attn_slope, d_hg, act_on, act_slope):
+def _gat_collapse_bwd(csr, st, rpos, pw, vocab, feat_p, attn_p, attn_slope, d_hg, act_on, act_slope):
     N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
     a12, alpha, coef, wsum, gid, Z, hg = st.cl
     d_hg, ld = _rows(d_hg)
@@ -441,17 +464,17 @@ def _gat_collapse_bwd(csr, st, pos, rpos, pw, vocab, feat_p, attn_p, attn_slope,
     wsb = pure("txe_gat_collapse_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(v, 8))
     ws = _ws(wsb, st.X)
     call("txe_gat_collapse_bwd", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
-         ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(pos if pos is not None else rpos), v, ptr(st.Wp), ptr(st.W),
+         ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(st.pos if st.pos is not None else rpos), v, ptr(st.Wp), ptr(st.W),
          ptr(st.al), ptr(st.ar), st.D, feat_p, ptr(st.mask), attn_slope, attn_p, st.seed + 1, ptr(pw), ptr(a12), ptr(alpha), ptr(coef),
          ptr(wsum), ptr(gid), ptr(Z), ptr(hg), st.D, ptr(d_hg), ld, int(act_on), act_slope if act_slope else 1.0, ptr(d_X), ptr(dW), ptr(dal), ptr(dar), ptr(dP),
          ptr(d_pw), ptr(ws), wsb, _lib.stream_ptr())
     return d_X, dW, dal, dar, dP, d_pw
 
 
-def _gat_layer_fwd(csr, st, h, ld_h, pos, out, ld_out, feat_p, attn_p, attn_slope, out_mode, act_slope, save, nxt=None, out_drop=None):
+def _gat_layer_fwd(csr, st, h, ld_h, out, ld_out, feat_p, attn_p, attn_slope, out_mode, act_slope, save, nxt=None, out_drop=None):
     """st.X is pre-allocated [N, Kp]; h != None copies the raw features in, h == None means the producer already wrote them.
     nxt = (prepared state of the next, folded one-head layer, a12 buffer): its attention logits ride in the aggregation's epilogue."""
-    H, D, Kh, Pd, Kp, Fp = st.H, st.D, st.Kh, st.Pd, st.Kp, st.Fp
+    H, D, Kh, Pd, Kp, Fp, pos = st.H, st.D, st.Kh, st.Pd, st.Kp, st.Fp, st.pos
     F = H * D
     s = _lib.stream_ptr()
     if isinstance(h, GatheredRows):            # eval-mode first layer on table rows: project the table, gather (SURVEY 8f-2)
@@ -472,16 +495,16 @@ def _gat_layer_fwd(csr, st, h, ld_h, pos, out, ld_out, feat_p, attn_p, attn_slop
              ptr(st.Y), Fp, s)
     else:
         N = st.X.shape[0]
-        _gat_layer_prepare(st, h, ld_h, pos, feat_p)
+        _gat_layer_prepare(st, h, ld_h, feat_p)
         st.Y = _empty((N, Fp), st.X)
         tws = _tail_ws(st.X)
-        dropped = getattr(st, "x_dropped", False)
+        dropped = st.x_dropped
         if (dropped or feat_p == 0.0) and not _NO_SPLIT_GEMM:      # X is a plain operand: fp32-accurate product on the bf16 pipe
             wsb = pure("txe_gat_dense_split_ws_bytes", N, Kh, Pd, H, D)
             sws = _ws(wsb, st.X)
             xtb = pure("txe_gat_dense_split_xt_bytes", N, Kh, Pd, H, D) if save else 0
             st.Xt = _ws(xtb, st.X) if xtb else None        # X packed contraction-major: the backward pass's weight gradient reads it
-            if getattr(st, "vx", False):                   # X was never written: the packs read h, the position table and the mask
+            if st.vx:                                      # X was never written: the packs read h, the position table and the mask
                 call("txe_gat_dense_fwd_split_src", ptr(h), ld_h, ptr(pos), ptr(st.P), ptr(st.mask), feat_p if st.mask is not None else 0.0,
                      N, Kh, Pd, ptr(st.Wp), H, D, ptr(st.Xt), ptr(st.Y), ptr(sws), wsb, s)
             else:
@@ -525,7 +548,7 @@ class _TailChain:
         self.keep = []
 
 
-def _gat_dense_bwd(st, pos, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chain=None, defer=False):
+def _gat_dense_bwd(st, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chain=None, defer=False):
     """projection backward of one layer from d_Y: (d_X or None, dW, d_attn_l, d_attn_r, dP).
     chain / defer: see _TailChain (defer: this layer's last reduction launch is left to the bottom layer's)"""
     N = st.X.shape[0]
@@ -538,9 +561,9 @@ def _gat_dense_bwd(st, pos, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chai
         wsb += pure("txe_gat_dense_bwd_split_ws_bytes", N, st.Kh, st.Pd, st.H, st.D)
     ws = _ws(wsb, st.X)
     def run(phases):
-        call("txe_gat_dense_bwd", None if getattr(st, "vx", False) else ptr(st.X), N, st.Kh, st.Pd, ptr(pos), vocab, ptr(st.Wp), ptr(st.W), ptr(st.al), ptr(st.ar), st.H, st.D, feat_p,
+        call("txe_gat_dense_bwd", None if st.vx else ptr(st.X), N, st.Kh, st.Pd, ptr(st.pos), vocab, ptr(st.Wp), ptr(st.W), ptr(st.al), ptr(st.ar), st.H, st.D, feat_p,
              ptr(st.mask), ptr(d_Y), int(need_dh), int(act_on), act_slope if act_slope else 1.0, ptr(d_X), ptr(dW), ptr(dal), ptr(dar),
-             ptr(dP), int(getattr(st, "x_dropped", False)), ptr(getattr(st, "Xt", None)), phases, chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
+             ptr(dP), int(st.x_dropped), ptr(st.Xt), phases, chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
     # (a first PGAT layer's d_X -- position columns only -- is one HBM stream over d_Y, txe_dxpos.hip; every other d_X is a GEMM)
     run(7 | (16 if split_dx else 0) | (64 if (defer and chain is not None) else 0))
     if chain is not None:
@@ -548,9 +571,9 @@ def _gat_dense_bwd(st, pos, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chai
     return d_X, dW, dal, dar, dP
 
 
-def _gat_layer_bwd(csr, st, pos, vocab, feat_p, attn_p, attn_slope, d_pre, ld_dpre, need_dh, act_on, act_slope, chain=None, defer=False):
+def _gat_layer_bwd(csr, st, vocab, feat_p, attn_p, attn_slope, d_pre, ld_dpre, need_dh, act_on, act_slope, chain=None, defer=False):
     d_Y = _gat_aggregate_bwd(csr, st, attn_p, attn_slope, d_pre, ld_dpre)
-    return _gat_dense_bwd(st, pos, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chain, defer)
+    return _gat_dense_bwd(st, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chain, defer)
 
 
 def _order(first, then):
@@ -579,16 +602,37 @@ class FoldLink:
     """What the producer of Z (GATStackFunction, cfg.final == 'collapse_z') shares with whoever consumes Z as the folded graph vector
     hg = Z W^T: the consumer's backward leaves the main part of the output layer's weight gradient here (S slices [D, Kp], summed in
     order) and hands dZ back through autograd; the producer's backward adds the attention rows' part and returns the whole dW."""
-    __slots__ = ("part", "S", "fwd", "e_part", "m", "by_k", "one_col")
+    __slots__ = ("part", "S", "fwd", "e_part", "ds", "s", "apply_exp", "by_k", "one_col")
 
     def __init__(self):
         self.part, self.S = None, 0
         # the producer's weight packing: a GAT layer's Wp [Fp][Kp] (rows < D the weight) or -- by_k -- a GCN layer's Wp [Kp128][Fop] (row k, D
         # columns; row one_col holds the bias and column one_col of Z counts as 1).  by_k: `part` comes back as [Kp][D], row one_col = d_bias
         self.by_k, self.one_col = False, -1
-        # with a matcher job (folded_match_job) the producer forms T before its Z sweep, the sweep leaves <T[run(g)], keep X[u]> per node
-        # (e_part) and backward's <dZ, X> sweep becomes a scaling by the matcher's score gradient (m = (ds, s, apply_exp)):
-        self.fwd, self.e_part, self.m = None, None, None
+        # with a matcher job (fwd: the FoldJob of folded_match_job) the producer forms T before its Z sweep and the sweep leaves
+        # <T[run(g)], keep X[u]> per node (e_part); backward's <dZ, X> sweep then becomes a scaling by the matcher's score gradient ds
+        # (with the scores s and its apply_exp, left here by the matcher's backward)
+        self.fwd, self.e_part = None, None
+        self.ds, self.s, self.apply_exp = None, None, 0
+
+    @property
+    def carried_T(self):
+        """the producer's Z sweep carried T: e_part is there and the job holds what sums the scores from it (FoldJob.score)"""
+        return self.e_part is not None and self.fwd is not None and self.fwd.score is not None
+
+    @property
+    def dz_implicit(self):
+        """the matcher's backward left its score gradient: the producer reads 'dZ[g]' as ds_g T[run(g)], no dZ tensor exists"""
+        return self.e_part is not None and self.ds is not None
+
+    def edot_args(self, zgid):
+        """the seven trailing edot arguments of txe_gat_collapse_bwd_fused (all absent unless dz_implicit)"""
+        if not self.dz_implicit:
+            return None, None, None, 0, None, None, None
+        return ptr(self.e_part), ptr(self.ds), ptr(self.s), int(self.apply_exp), ptr(self.fwd.T), ptr(self.fwd.run_id), ptr(zgid)
+
+
+_NO_LINK = FoldLink()  # (read only) what _gat_collapse_bwd_fused reads when nobody consumed Z: no weight-gradient part, no edot arguments
 
 
 def walk_plan(csr):
@@ -609,12 +653,13 @@ def walk_plan(csr):
 _WALK_PLANS = {}       # id of a CSR's rowptr_in tensor -> (weak reference to it, the plan)
 
 
-def _gat_collapse_bwd_fused(csr, st, sp, pos, rpos, pw, vocab, feat_p, attn_p, attn_slope, d_hg, act_slope, chain=None, link=None):
+def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, feat_p, attn_p, attn_slope, d_hg, act_slope, chain=None, link=None):
     """txe_gat_collapse_bwd_fused: the folded layer's parameter gradients AND the layer below's d_Y in one sweep (no d_X).
     link given: d_hg IS dZ [G, Kp] (the consumer of Z folded hg = Z W^T into its own products, FoldLink)."""
     N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
     a12, alpha, coef, wsum, gid, Z, hg = st.cl
-    edot = link is not None and link.e_part is not None and link.m is not None     # the <dZ, X> sweep was done in forward (FoldLink)
+    lk = link or _NO_LINK
+    edot = lk.dz_implicit                           # the <dZ, X> sweep was done in forward (FoldLink)
     if d_hg is None:
         if not edot:
             raise RuntimeError("folded output layer: no gradient arrived for the graph vector")
@@ -632,19 +677,17 @@ def _gat_collapse_bwd_fused(csr, st, sp, pos, rpos, pw, vocab, feat_p, attn_p, a
     ws = _ws(wsb, st.X)
     def run(phases):
         call("txe_gat_collapse_bwd_fused", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
-             ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(pos if pos is not None else rpos), v, ptr(st.Wp), ptr(st.W),
+             ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(st.pos if st.pos is not None else rpos), v, ptr(st.Wp), ptr(st.W),
              ptr(st.al), ptr(st.ar), st.D, feat_p, ptr(st.mask), attn_slope, attn_p, st.seed + 1, ptr(pw), ptr(a12), ptr(alpha), ptr(coef),
              ptr(wsum), ptr(gid), ptr(Z), ptr(hg), st.D, ptr(d_hg), ld, act_slope if act_slope else 1.0, ptr(sp.Y), sp.Fp, sp.H, sp.D,
              attn_slope, attn_p, sp.seed + 1, ptr(sp.alpha), ptr(d_Yp), sp.Fp, sp.Fp - Fe, ptr(dz), ptr(dW), ptr(dal), ptr(dar), ptr(dP),
-             ptr(d_pw), phases | (512 if edot else 0) | (1024 if _NO_EGO_WALK else 0), ptr(link.part) if (link is not None and link.S > 0) else None,
-             link.S if link is not None else 0, *((ptr(link.e_part), ptr(link.m[0]), ptr(link.m[1]), int(link.m[2]), ptr(link.fwd["T"]),
-                                                  ptr(link.fwd["run_id"]), ptr(zgid)) if edot else (None, None, None, 0, None, None, None)),
-             ptr(plan), chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
+             ptr(d_pw), phases | (512 if edot else 0) | (1024 if _NO_EGO_WALK else 0), ptr(lk.part) if lk.S > 0 else None,
+             lk.S, *lk.edot_args(zgid), ptr(plan), chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
     zgid = torch.empty(max(N, 1), dtype=torch.int32, device=st.X.device) if edot else None
     plan = walk_plan(csr) if (sp.H == 4 and not _NO_EGO_WALK and not _NO_WALK_PLAN) else None
     last = 8 | (64 if chain is not None else 0)     # (with a chain the final reductions are left to the bottom layer's launch)
     if chain is not None:
-        chain.keep += [ws, d_hg, st, sp, zgid] + ([link.part, link.fwd, link.m] if link is not None else [])
+        chain.keep += [ws, d_hg, st, sp, zgid] + ([link.part, link.fwd, link.ds, link.s] if link is not None else [])
     if link is not None:                            # dZ given: no product left in this layer's backward, nothing for a second stream
         if ld != st.Kp and not edot:
             raise RuntimeError("folded graph vector: dZ must have the padded row pitch")
@@ -675,7 +718,7 @@ class GATStackFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, csr, cfg, h, pos, rpos, pw, *params):
-        need = getattr(cfg, "grad_enabled", True) and any(ctx.needs_input_grad)     # (see apply_stack)
+        need = cfg.grad_enabled and any(ctx.needs_input_grad)      # (see apply_stack)
         z_only = (cfg.final == "collapse_z")        # 'collapse' that stops at Z: returns (Z [G, Kp], the output layer's packed weights)
         collapse = (cfg.final == "collapse") or z_only
         table = _use_table(h, need, cfg.feat_p) and not (collapse and cfg.n_layers == 1)
@@ -701,11 +744,10 @@ class GATStackFunction(torch.autograd.Function):
                 st = _GatLayerState()
                 st.W, st.al, st.ar, st.P = (_f32(p) for p in params[4 * l:4 * l + 4])
                 st.H, st.D, st.Kh = cfg.heads[l], cfg.out_dims[l], kh
-                st.Pd = 0 if st.P is None else st.P.shape[1]
+                st.Pd, st.pos = (0, None) if st.P is None else (st.P.shape[1], pos)
                 st.Kp = pure("txe_gat_padded_k", st.Kh, st.Pd)
                 st.Fp = pure("txe_gat_padded_f", st.H, st.D)
                 st.seed = cfg.seed + 16 * l
-                st.X = None
                 states.append(st)
                 kh = st.H * st.D
             h = ref                                  # (allocation reference from here on; the features travel as `src`)
@@ -716,18 +758,16 @@ class GATStackFunction(torch.autograd.Function):
                 # (a layer that is not the folded one: only its GEMMs read X, so X is stored with the dropout applied -- by the
                 #  preparation (raw features, position columns) and by the aggregation of the layer below (_drops_output))
                 states[0].vx = (not table) and _virtual_x_ok(states[0], src, ld_h, N, need, collapse and L == 1)
-                _gat_layers_prepare([(st, (src if l == 0 else None), (ld_h if l == 0 else 0), pos if st.P is not None else None,
-                                      _x_dropped_ok(cfg, states, l, collapse))
+                _gat_layers_prepare([(st, (src if l == 0 else None), (ld_h if l == 0 else 0), _x_dropped_ok(cfg, states, l, collapse))
                                      for l, st in enumerate(states) if not (table and l == 0)], cfg.feat_p)
             fused_a12 = None
             for l, st in enumerate(states):
                 last = (l == L - 1)
                 F = st.H * st.D
                 if last and collapse:
-                    res = _gat_collapse_fwd(csr, st, src if l == 0 else None, ld_h if l == 0 else 0, pos if st.P is not None else None,
-                                            rpos, pwf, cfg.feat_p, cfg.attn_p, cfg.attn_slope, a12=fused_a12, z_only=z_only,
-                                            fold_job=getattr(cfg, "fold_job", None) if (z_only and need) else None,
-                                            link=getattr(cfg, "link", None))
+                    res = _gat_collapse_fwd(csr, st, src if l == 0 else None, ld_h if l == 0 else 0, rpos, pwf, cfg.feat_p, cfg.attn_p,
+                                            cfg.attn_slope, a12=fused_a12, z_only=z_only,
+                                            fold_job=cfg.fold_job if (z_only and need) else None, link=cfg.link)
                     if z_only:
                         res = (res, st.Wp)
                         ctx.mark_non_differentiable(st.Wp)
@@ -747,13 +787,13 @@ class GATStackFunction(torch.autograd.Function):
                         and not _NO_FUSED_LOGITS):
                     # the folded output layer is prepared first: its keep mask and folded attention rows feed this layer's epilogue
                     sn = states[l + 1]
-                    _gat_layer_prepare(sn, None, 0, pos if sn.P is not None else None, cfg.feat_p)
+                    _gat_layer_prepare(sn, None, 0, cfg.feat_p)
                     fused_a12 = _empty((N, 2), h)
                     nxt = (sn, fused_a12)
                 # (the layer above reads its input through plain GEMM operands: this layer's aggregation applies that layer's dropout)
-                out_drop = states[l + 1] if (not last and nxt is None and getattr(states[l + 1], "x_dropped", False)) else None
-                _gat_layer_fwd(csr, st, src if l == 0 else None, ld_h if l == 0 else 0, pos if st.P is not None else None, out, ld_out,
-                               cfg.feat_p, cfg.attn_p, cfg.attn_slope, out_mode, cfg.act_slope or 1.0, need, nxt, out_drop)
+                out_drop = states[l + 1] if (not last and nxt is None and states[l + 1].x_dropped) else None
+                _gat_layer_fwd(csr, st, src if l == 0 else None, ld_h if l == 0 else 0, out, ld_out, cfg.feat_p, cfg.attn_p, cfg.attn_slope,
+                               out_mode, cfg.act_slope or 1.0, need, nxt, out_drop)
                 if not need:
                     st.Y = st.mask = st.Wp = None
                     if l > 0:
@@ -769,19 +809,19 @@ class GATStackFunction(torch.autograd.Function):
                     call("txe_head_mean_fwd", ptr(out), H, D, N, ptr(res), _lib.stream_ptr())
             else:
                 res = out.view(N, H, D)
-        ctx.csr, ctx.cfg, ctx.pos, ctx.states = csr, cfg, pos, (states if need else None)
+        ctx.csr, ctx.cfg, ctx.states = csr, cfg, (states if need else None)
         ctx.rpos, ctx.pwf, ctx.pw_shape = rpos, pwf, (pw.shape if pwf is not None else None)
         ctx.h_req = ctx.needs_input_grad[2]
         ctx.param_ids, ctx.pw_id = [id(p) for p in params], id(pw)
-        ctx.link = getattr(cfg, "link", None) if z_only else None
-        note_route("stack", cfg.final + ("+edot" if (z_only and ctx.link is not None and ctx.link.e_part is not None) else ""))
+        ctx.link = cfg.link if z_only else None
+        note_route("stack", cfg.final + ("+edot" if (ctx.link is not None and ctx.link.carried_T) else ""))
         if _CAPTURE is not None:
             _CAPTURE.append((csr, cfg, states))
         return res
 
     @staticmethod
     def backward(ctx, d_res, *_unused):
-        csr, cfg, pos, states = ctx.csr, ctx.cfg, ctx.pos, ctx.states
+        csr, cfg, states = ctx.csr, ctx.cfg, ctx.states
         if states is None:
             raise RuntimeError(_BACKWARD_TWICE)
         L = cfg.n_layers
@@ -789,7 +829,7 @@ class GATStackFunction(torch.autograd.Function):
         z_only = (cfg.final == "collapse_z")
         collapse = (cfg.final == "collapse") or z_only
         link = ctx.link if z_only else None
-        edot = link is not None and link.e_part is not None and link.m is not None
+        edot = link is not None and link.dz_implicit
         if d_res is None and not edot:
             # (collapse_z does not materialise absent gradients: Z took no part in the loss -- nothing to propagate, and the saved
             #  state can go)
@@ -823,20 +863,20 @@ class GATStackFunction(torch.autograd.Function):
                 if collapse and l == L - 1:
                     if l > 0 and _fused_bwd_ok(csr, st, states[l - 1]):
                         d_Y_ready, dW, dal, dar, dP, d_pw = _gat_collapse_bwd_fused(
-                            csr, st, states[l - 1], pos if st.P is not None else None, ctx.rpos, ctx.pwf, cfg.vocab, cfg.feat_p, cfg.attn_p,
-                            cfg.attn_slope, d_res, cfg.act_slope if act_on else None, chain, link=(ctx.link or FoldLink()) if z_only else None)
+                            csr, st, states[l - 1], ctx.rpos, ctx.pwf, cfg.vocab, cfg.feat_p, cfg.attn_p, cfg.attn_slope, d_res,
+                            cfg.act_slope if act_on else None, chain, link=(ctx.link or FoldLink()) if z_only else None)
                     elif z_only:
                         raise RuntimeError("collapse_z was requested for a stack whose fused backward does not apply (folded_graph_vector_ok)")
                     else:
-                        d_X, dW, dal, dar, dP, d_pw = _gat_collapse_bwd(csr, st, pos if st.P is not None else None, ctx.rpos, ctx.pwf, cfg.vocab,
-                                                                        cfg.feat_p, cfg.attn_p, cfg.attn_slope, d_res, act_on, cfg.act_slope)
+                        d_X, dW, dal, dar, dP, d_pw = _gat_collapse_bwd(csr, st, ctx.rpos, ctx.pwf, cfg.vocab, cfg.feat_p, cfg.attn_p,
+                                                                        cfg.attn_slope, d_res, act_on, cfg.act_slope)
                 elif d_Y_ready is not None:
-                    d_X, dW, dal, dar, dP = _gat_dense_bwd(st, pos if st.P is not None else None, cfg.vocab, cfg.feat_p, d_Y_ready, need_dh,
-                                                           act_on, cfg.act_slope, chain, defer=l > 0)
+                    d_X, dW, dal, dar, dP = _gat_dense_bwd(st, cfg.vocab, cfg.feat_p, d_Y_ready, need_dh, act_on, cfg.act_slope, chain,
+                                                           defer=l > 0)
                     d_Y_ready = None
                 else:
-                    d_X, dW, dal, dar, dP = _gat_layer_bwd(csr, st, pos if st.P is not None else None, cfg.vocab, cfg.feat_p, cfg.attn_p,
-                                                           cfg.attn_slope, d_pre, ld_dpre, need_dh, act_on, cfg.act_slope, chain, defer=l > 0)
+                    d_X, dW, dal, dar, dP = _gat_layer_bwd(csr, st, cfg.vocab, cfg.feat_p, cfg.attn_p, cfg.attn_slope, d_pre, ld_dpre, need_dh,
+                                                           act_on, cfg.act_slope, chain, defer=l > 0)
                 grads[4 * l:4 * l + 4] = [dW, dal, dar, dP]
                 if _GRAD_READY is not None:               # (tensors, ids of the parameters they are the gradients of)
                     last_c = collapse and l == L - 1
@@ -865,10 +905,26 @@ class GCNConfig:
         self.drop_ps = [float(p) for p in drop_ps]
         self.seed = int(seed)
         self.n_layers = len(self.out_dims)
+        # 'layers' (N x Fo), or what DeferredNodeOutput._collapse sets on a copy: 'collapse' / 'collapse_z' with its FoldLink (see GATConfig)
+        self.final, self.grad_enabled, self.link, self.fold_job = "layers", True, None, None
+
+
+class GcnFolded(typing.NamedTuple):
+    """what the folded GCN output layer's forward keeps for its backward (_GcnLayerState.cl): as in GatFolded"""
+    coef: torch.Tensor
+    wsum: torch.Tensor
+    gid: torch.Tensor
+    Z: torch.Tensor
 
 
 class _GcnLayerState:
     __slots__ = ("X", "Wp", "mask", "W", "b", "P", "Kh", "Pd", "Kp", "Fo", "Fop", "seed", "cl", "x_dropped")
+
+    def __init__(self):
+        self.X = self.Wp = self.mask = self.W = self.b = self.P = None
+        self.Kh = self.Pd = self.Kp = self.Fo = self.Fop = self.seed = 0
+        self.cl = None              # GcnFolded: the output layer folded behind the readout
+        self.x_dropped = False
 
 
 class GCNStackFunction(torch.autograd.Function):
@@ -880,10 +936,10 @@ class GCNStackFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, csr, cfg, h, pos, rpos, pw, *params):
-        z_only = (getattr(cfg, "final", None) == "collapse_z")   # 'collapse' that stops at Z: returns (Z [G, Kp], the output layer's packed weights)
-        collapse = (getattr(cfg, "final", None) == "collapse") or z_only
+        z_only = (cfg.final == "collapse_z")        # 'collapse' that stops at Z: returns (Z [G, Kp], the output layer's packed weights)
+        collapse = (cfg.final == "collapse") or z_only
         L = cfg.n_layers
-        need = getattr(cfg, "grad_enabled", True) and any(ctx.needs_input_grad)     # (see apply_stack)
+        need = cfg.grad_enabled and any(ctx.needs_input_grad)      # (see apply_stack)
         table = _use_table(h, need, cfg.drop_ps[0]) and not (collapse and L == 1)
         if isinstance(h, GatheredRows) and not table:
             h = h.tensor()
@@ -910,7 +966,6 @@ class GCNStackFunction(torch.autograd.Function):
                 st.Kp = pure("txe_gat_padded_k", st.Kh, st.Pd)
                 st.Fop = pure("txe_gcn_padded_f", st.Fo)
                 st.seed = cfg.seed + 16 * l
-                st.X = None
                 states.append(st)
                 kh = st.Fo
             # every layer's input buffer now; ONE launch prepares the whole stack (layer inputs' position / padding columns, packed weights,
@@ -954,11 +1009,10 @@ class GCNStackFunction(torch.autograd.Function):
                     call("txe_gcn_collapse_fwd", ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.graph_off), N, G, ptr(st.X), st.Kh, st.Pd,
                          ptr(st.Wp), st.Fo, ptr(st.b), cfg.drop_ps[l], ptr(st.mask), ptr(norm), ptr(rpos), ptr(pwf), ptr(coef), ptr(wsum),
                          ptr(gid), ptr(Z), ptr(out), st.Fo, ptr(ws), wsb, st_)
-                    st.cl = (coef, wsum, gid, Z)
+                    st.cl = GcnFolded(coef, wsum, gid, Z)
                     if z_only:
-                        link = getattr(cfg, "link", None)
-                        if link is not None:
-                            link.by_k, link.one_col = True, (st.Kh + st.Pd if st.b is not None else -1)
+                        if cfg.link is not None:
+                            cfg.link.by_k, cfg.link.one_col = True, (st.Kh + st.Pd if st.b is not None else -1)
                         out = (Z, st.Wp)
                         ctx.mark_non_differentiable(st.Wp)
                         ctx.set_materialize_grads(False)
@@ -972,9 +1026,8 @@ class GCNStackFunction(torch.autograd.Function):
                          ptr(pos) if T2 is not None else None, N, st.Fop, ptr(hw), st.Fop, st_)
                     st.mask = st.Wp = None
                 else:
-                    dropped = getattr(st, "x_dropped", False)
-                    call("txe_gcn_dense_fwd", ptr(st.X), N, st.Kh, st.Pd, ptr(st.Wp), st.Fo, 0.0 if dropped else cfg.drop_ps[l],
-                         None if dropped else ptr(st.mask), ptr(hw), ptr(tws), tws.numel(), st_)
+                    call("txe_gcn_dense_fwd", ptr(st.X), N, st.Kh, st.Pd, ptr(st.Wp), st.Fo, 0.0 if st.x_dropped else cfg.drop_ps[l],
+                         None if st.x_dropped else ptr(st.mask), ptr(hw), ptr(tws), tws.numel(), st_)
                     _launch_pending_prefetch()
                 if last:
                     out, ld_out = _empty((N, st.Fo), h), st.Fo
@@ -988,8 +1041,8 @@ class GCNStackFunction(torch.autograd.Function):
                     if l > 0:
                         st.X = None
         ctx.csr, ctx.cfg, ctx.pos, ctx.norm = csr, cfg, pos, norm
-        ctx.link = getattr(cfg, "link", None) if z_only else None
-        note_route("stack", "collapse_z" if z_only else ("collapse" if collapse else "layers"))
+        ctx.link = cfg.link if z_only else None
+        note_route("stack", cfg.final)
         if _CAPTURE is not None:
             _CAPTURE.append((csr, cfg, states))
         ctx.states = states if need else None
@@ -1004,13 +1057,13 @@ class GCNStackFunction(torch.autograd.Function):
         if states is None:
             raise RuntimeError(_BACKWARD_TWICE)
         L = cfg.n_layers
-        z_only = (getattr(cfg, "final", None) == "collapse_z")
+        z_only = (cfg.final == "collapse_z")
         if d_out is None:                          # (collapse_z does not materialise absent gradients: Z took no part in the loss)
             ctx.states = None
             return (None,) * (6 + 3 * L)
         d_out = _f32(d_out)
         grads = [None] * (3 * L)
-        collapse = (getattr(cfg, "final", None) == "collapse") or z_only
+        collapse = (cfg.final == "collapse") or z_only
         d_pw = None
         with _lib.on_device(d_out.device):
             st_ = _lib.stream_ptr()
@@ -1070,7 +1123,7 @@ class GCNStackFunction(torch.autograd.Function):
                 ws2 = _ws(wsb2, d_out)
                 call("txe_gcn_dense_bwd", ptr(st.X), N, st.Kh, st.Pd, ptr(pos if st.P is not None else None), cfg.vocab, ptr(st.Wp), st.Fo,
                      cfg.drop_ps[l], ptr(st.mask), ptr(d_hw), int(need_dh), int(act_on), (cfg.act_slopes[l - 1] if act_on else 1.0),
-                     ptr(d_X), ptr(dW), ptr(dP), int(getattr(st, "x_dropped", False)), ptr(ws2), wsb2, st_)
+                     ptr(d_X), ptr(dW), ptr(dP), int(st.x_dropped), ptr(ws2), wsb2, st_)
                 grads[3 * l:3 * l + 3] = [dW, d_b, dP]
                 if l > 0:
                     d_pre, ld_dpre = d_X, st.Kp
@@ -1186,6 +1239,39 @@ class LinearFunction(torch.autograd.Function):
 # ================================================================================================================
 # Bilinear match (BIM / LBM) -- pairwise form of training, model.py:86
 # ================================================================================================================
+class QueryPrefetch:
+    """bilinear_query_prefetch's token: V [G, l] = e2 W^T, the tensors it was asked for with their versions at that moment, the second
+    stream (`stream`: where V is written once launched there, else None) and the operands of the launch"""
+    __slots__ = ("V", "e2", "e2_version", "W", "W_version", "stream", "launched", "e2c", "ld2", "Wf", "side")
+
+    def __init__(self, e2, W, e2c, ld2, Wf, V, side):
+        self.V, self.e2, self.e2_version, self.W, self.W_version = V, e2, e2._version, W, W._version
+        self.e2c, self.ld2, self.Wf, self.side = e2c, ld2, Wf, side
+        self.stream, self.launched = side, False
+
+    def matches(self, e2, W, G, l):
+        """is V still the projection of these very tensors, unwritten since, for G pairs of l columns?"""
+        return (self.e2 is e2 and self.e2_version == e2._version and self.W is W and self.W_version == W._version
+                and tuple(self.V.shape) == (G, l))
+
+    def launch(self, on_side=True):
+        if self.launched:
+            return
+        self.launched = True
+        V, e2c, Wf, side, device = self.V, self.e2c, self.Wf, self.side, self.e2.device
+        if on_side:
+            _order(torch.cuda.current_stream(device), side)
+        with _lib.on_device(device), torch.cuda.stream(side if on_side else torch.cuda.current_stream(device)):
+            call("txe_bilinear_query_project", ptr(e2c), self.ld2, V.shape[0], V.shape[1], e2c.shape[1], ptr(Wf), ptr(V), _lib.stream_ptr())
+        if on_side:
+            # V was allocated on the caller's stream and is written on the second one: tell the caching allocator, so that a token
+            # that is never consumed (rejected by forward, an exception in between) cannot hand V's block to a main-stream tensor
+            # while the projection is still writing it; the same for the operands it reads
+            for t in (V, e2c, Wf):
+                t.record_stream(side)
+        self.stream = side if on_side else None
+
+
 def bilinear_query_prefetch(e2, W):
     """V = e2 W^T of the query-side match (BilinearPairFunction), launched on the second stream: it depends on the queries and the
     matcher's weight only, so it can run under the encoder (TaxoExpan.forward calls this before graph_propagate).  Returns a token for
@@ -1194,28 +1280,7 @@ def bilinear_query_prefetch(e2, W):
         return None
     e2c, ld2 = _rows(e2)
     Wf = _f32(W).reshape(W.shape[-2], W.shape[-1])
-    G, r = e2c.shape
-    l = Wf.shape[0]
-    main, side = torch.cuda.current_stream(e2.device), _side_stream(e2.device)
-    V = _empty((G, l), e2c)
-    tok = dict(V=V, e2=e2, e2_version=e2._version, W=W, W_version=W._version, stream=side, e2c=e2c, launched=False)
-
-    def launch(on_side=True):
-        if tok["launched"]:
-            return
-        tok["launched"] = True
-        if on_side:
-            _order(torch.cuda.current_stream(e2.device), side)
-        with _lib.on_device(e2.device), torch.cuda.stream(side if on_side else torch.cuda.current_stream(e2.device)):
-            call("txe_bilinear_query_project", ptr(e2c), ld2, G, l, r, ptr(Wf), ptr(V), _lib.stream_ptr())
-        if on_side:
-            # V was allocated on the caller's stream and is written on the second one: tell the caching allocator, so that a token
-            # that is never consumed (rejected by forward, an exception in between) cannot hand V's block to a main-stream tensor
-            # while the projection is still writing it; the same for the operands it reads
-            for t in (V, e2c, Wf):
-                t.record_stream(side)
-        tok["stream"] = side if on_side else None
-    tok["launch"] = launch
+    tok = QueryPrefetch(e2, W, e2c, ld2, Wf, _empty((e2c.shape[0], Wf.shape[0]), e2c), _side_stream(e2.device))
     # launched by the encoder behind its first projection GEMM (_launch_pending_prefetch): started at the very beginning its workgroups
     # take slots before the persistent first-layer projection's, whose late starters then finish late
     del _pending_prefetch[:]                    # (a token nobody launched holds no device work: dropping it is safe)
@@ -1228,7 +1293,7 @@ _pending_prefetch = []
 
 def _launch_pending_prefetch():
     while _pending_prefetch:
-        _pending_prefetch.pop()["launch"]()
+        _pending_prefetch.pop().launch()
 
 
 class BilinearPairFunction(torch.autograd.Function):
@@ -1250,13 +1315,11 @@ class BilinearPairFunction(torch.autograd.Function):
         query_side = not ctx.needs_input_grad[1]
         with _lib.on_device(e1.device):
             if query_side:
-                ready = (pre is not None and pre["e2"] is e2_in and pre["e2_version"] == e2_in._version and pre["W"] is W
-                         and pre["W_version"] == W._version and tuple(pre["V"].shape) == (G, l))
-                if ready:
-                    U = pre["V"]
-                    pre["launch"](on_side=False)                 # (nobody started it: in line, on this stream)
-                    if pre["stream"] is not None:
-                        _order(pre["stream"], torch.cuda.current_stream())
+                if pre is not None and pre.matches(e2_in, W, G, l):
+                    U = pre.V
+                    pre.launch(on_side=False)                    # (nobody started it: in line, on this stream)
+                    if pre.stream is not None:
+                        _order(pre.stream, torch.cuda.current_stream())
                     call("txe_bilinear_query_dot", ptr(e1), ld1, ptr(U), G, l, int(apply_exp), ptr(s), _lib.stream_ptr())
                 else:
                     U = _empty((max(G, 1), l), e1)          # V = e2 W^T
@@ -1520,19 +1583,46 @@ def folded_match_job(e2, rows, run_off, Wm):
             V, T = _empty((max(U, 1), l), Wp), _empty((max(U, 1), Kp), Wp)
             call("txe_bilinear_folded_fwd", None, Kp, G if G is not None else 1, Kp, ptr(Wp), Kp, l, ptr(Q), ldq, r, ptr(roff), ptr(n_runs), U, first_row,
                  ptr(Wmf), 0, ptr(V), ptr(T), None, 1, 0, -1, _lib.stream_ptr())
-        fw = dict(e2=e2, rows=rows, run_off_in=run_off, Wm=Wm, Wm_version=Wm._version, Wp=Wp, Q=Q, ldq=ldq, roff=roff, n_runs=n_runs, U=U,
-                  first_row=first_row, V=V, T=T, run_id=(run_id if rows is None else None))
-        return fw
+        return FoldJob(e2, rows, run_off, Wm, Wp, Q, ldq, roff, n_runs, U, first_row, V, T, run_id if rows is None else None)
     return job
 
 
-def _fold_job_run_ids(fw, G, ref):
-    """graph -> run for the given-runs form (the stacked form's run detection has produced it)"""
-    if fw["run_id"] is None:
-        rid = torch.empty(max(G, 1), dtype=torch.int32, device=ref.device)
-        call("txe_runs_expand", ptr(fw["roff"]), fw["U"], G, ptr(rid), _lib.stream_ptr())
-        fw["run_id"] = rid
-    return fw["run_id"]
+class FoldScore(typing.NamedTuple):
+    """what txe_gat_collapse_fold_scores needs to sum the matcher's scores from FoldLink.e_part, left by the stack whose Z sweep filled it:
+    graph offsets, nodes, graphs, the folded layer's Kh / Pd, the readout's coef [N] / wsum [G], the feature dropout and whether it is on"""
+    graph_off: torch.Tensor
+    N: int
+    G: int
+    Kh: int
+    Pd: int
+    coef: torch.Tensor
+    wsum: torch.Tensor
+    feat_p: float
+    masked: int
+
+
+class FoldJob:
+    """what folded_match_job's callable has formed: the tensors it was built for (queries e2 or rows + run_off, the matcher's Wm and its
+    version, the output layer's Wp) and the query-side half of BilinearFoldedRunsFunction.forward -- Q / ldq, run offsets roff, n_runs, U
+    runs, first_row, V [U, l], T [U, Kp], graph -> run map run_id; score: the FoldScore of the Z sweep that carried T, else None"""
+    __slots__ = ("e2", "rows", "run_off", "Wm", "Wm_version", "Wp", "Q", "ldq", "roff", "n_runs", "U", "first_row", "V", "T", "run_id", "score")
+
+    def __init__(self, e2, rows, run_off, Wm, Wp, Q, ldq, roff, n_runs, U, first_row, V, T, run_id):
+        self.e2, self.rows, self.run_off, self.Wm, self.Wm_version, self.Wp = e2, rows, run_off, Wm, Wm._version, Wp
+        self.Q, self.ldq, self.roff, self.n_runs, self.U, self.first_row, self.V, self.T = Q, ldq, roff, n_runs, U, first_row, V, T
+        self.run_id, self.score = run_id, None
+
+    def matches(self, Wp, Wm, e2, rows, run_off, G):
+        """was the job run for these very tensors, Wm unwritten since (and, runs found in the stacked e2, for G rows)?"""
+        return (self.Wp is Wp and self.Wm is Wm and self.Wm_version == Wm._version and self.e2 is e2
+                and self.rows is rows and self.run_off is run_off and (rows is not None or self.U == G))
+
+    def run_ids(self, G):
+        """graph -> run for the given-runs form (the stacked form's run detection has produced it)"""
+        if self.run_id is None:
+            self.run_id = torch.empty(max(G, 1), dtype=torch.int32, device=self.T.device)
+            call("txe_runs_expand", ptr(self.roff), self.U, G, ptr(self.run_id), _lib.stream_ptr())
+        return self.run_id
 
 
 class BilinearFoldedRunsFunction(torch.autograd.Function):
@@ -1549,11 +1639,10 @@ class BilinearFoldedRunsFunction(torch.autograd.Function):
         l, r = Wmf.shape
         if l != D:
             raise RuntimeError("bilinear matcher: l_dim does not match the graph vector")
-        fw = link.fwd
-        ready = (fw is not None and fw["Wp"] is Wp and fw["Wm"] is Wm and fw["Wm_version"] == Wm._version and fw["e2"] is e2
-                 and fw["rows"] is rows and fw["run_off_in"] is run_off and (rows is not None or fw["U"] == G))
+        job = link.fwd
+        ready = job is not None and job.matches(Wp, Wm, e2, rows, run_off, G)
         if ready:                                   # the stack asked for the runs, V and T before its Z sweep (folded_match_job)
-            Q, ldq, run_off, n_runs, U, first_row, V, T = (fw[k] for k in ("Q", "ldq", "roff", "n_runs", "U", "first_row", "V", "T"))
+            Q, ldq, run_off, n_runs, U, first_row, V, T = job.Q, job.ldq, job.roff, job.n_runs, job.U, job.first_row, job.V, job.T
         else:
             link.fwd = link.e_part = None           # (whatever rode in the sweep belongs to other queries / weights)
             if rows is None:
@@ -1566,13 +1655,14 @@ class BilinearFoldedRunsFunction(torch.autograd.Function):
             V, T = _empty((max(U, 1), l), Z), _empty((max(U, 1), Kp), Z)
         s = _empty((G,), Z)
         # 'edot': the stack ran the matcher's job and its Z sweep carried T; 'job': it ran the job only; 'inline': V / T formed here
-        note_route("fold", "edot" if (ready and link.e_part is not None and "score" in fw) else ("job" if ready else "inline"))
+        edot = ready and link.carried_T
+        note_route("fold", "edot" if edot else ("job" if ready else "inline"))
         with _lib.on_device(Z.device):
-            if ready and link.e_part is not None and "score" in fw:
+            if edot:
                 # T rode in the stack's Z sweep: the scores are sums of its per-node dot products over each graph's few nodes, no sweep over Z
-                goff, n_, g_, kh_, pd_, coef_, wsum_, fp_, masked_ = fw["score"]
-                call("txe_gat_collapse_fold_scores", ptr(goff), n_, g_, kh_, pd_, ptr(coef_), ptr(wsum_), ptr(link.e_part), fp_, masked_, int(apply_exp),
-                     ptr(s), _lib.stream_ptr())
+                sc = job.score
+                call("txe_gat_collapse_fold_scores", ptr(sc.graph_off), sc.N, sc.G, sc.Kh, sc.Pd, ptr(sc.coef), ptr(sc.wsum), ptr(link.e_part),
+                     sc.feat_p, sc.masked, int(apply_exp), ptr(s), _lib.stream_ptr())
             else:
                 call("txe_bilinear_folded_fwd", ptr(Z), Kp, G, Kp, ptr(Wp), Wp.stride(0), l, ptr(Q), ldq, r, ptr(run_off), ptr(n_runs), U, first_row,
                      ptr(Wmf), int(apply_exp), ptr(V), ptr(T), ptr(s), 2 if ready else 3, int(link.by_k), int(link.one_col), _lib.stream_ptr())
@@ -1585,7 +1675,7 @@ class BilinearFoldedRunsFunction(torch.autograd.Function):
         G, Kp = Z.shape
         l, r = Wmf.shape
         ds = _f32(ds.reshape(-1))
-        edot = link.e_part is not None              # the stack reads "dZ[g]" as dsl_g T[run(g)] (FoldLink): no dZ tensor exists
+        edot = link.carried_T                       # the stack reads "dZ[g]" as dsl_g T[run(g)] (FoldLink): no dZ tensor exists
         dZ = None if edot else _empty((G, Kp), Z)
         dT, dV = _empty((max(U, 1), Kp), Z), _empty((max(U, 1), l), Z)
         dWm, dWf = _empty((l, r), Z), (_empty((Kp, l), Z) if link.by_k else _empty((l, Kp), Z))
@@ -1594,7 +1684,7 @@ class BilinearFoldedRunsFunction(torch.autograd.Function):
                  ptr(V), ptr(T), ptr(s), ptr(ds), ptr(dZ), Kp, ptr(dT), ptr(dV), ptr(dWm), ptr(dWf), int(link.by_k), int(link.one_col),
                  _lib.stream_ptr())
         link.part, link.S = dWf, 1
-        link.m = (ds, s, apply_exp) if link.e_part is not None else None
+        link.ds, link.s, link.apply_exp = (ds, s, apply_exp) if edot else (None, None, 0)
         return dZ, None, None, None, dWm.reshape(wshape), None, None, None, None
 
 

@@ -64,11 +64,10 @@ def _device_branches(kind, states, src, dst, masks):
     for l, st in enumerate(states):
         if kind == "PGAT":
             H, F_ = st.H, st.H * st.D
-            cl = getattr(st, "cl", None)
-            if l < L - 1 or cl is None:                               # (model_zoo._NO_FOLD: the output layer runs unfolded, like the others)
+            if l < L - 1 or st.cl is None:                            # (model_zoo._NO_FOLD: the output layer runs unfolded, like the others)
                 a1, a2 = st.Y[:, F_:F_ + H].cpu().numpy(), st.Y[:, F_ + H:F_ + 2 * H].cpu().numpy()
             else:
-                a12 = cl[0].cpu().numpy()
+                a12 = st.cl.a12.cpu().numpy()
                 a1, a2 = a12[:, 0:1], a12[:, 1:2]
             z = a1[src] + a2[dst]                                     # float32 + float32, like the kernels
             masks[l]["e_pos"] = torch.from_numpy(z > 0).unsqueeze(-1)
@@ -124,14 +123,13 @@ def _expected_routes(prop, form):
 def _graph_vectors_from_capture(prop, states, model, D):
     """hg [G, D] from the folded output layer's saved Z (nothing in the step is touched: no hook, no materialisation)"""
     st = states[-1]
-    if getattr(st, "cl", None) is None:
+    if st.cl is None:
         return None
+    Z = st.cl.Z.detach()
     if prop == "PGAT":
-        Z = st.cl[5].detach()
-        if st.cl[6] is not None:
-            return st.cl[6].detach().cpu().numpy()
+        if st.cl.hg is not None:
+            return st.cl.hg.detach().cpu().numpy()
         return (Z.double() @ st.Wp[:D].detach().double().t()).float().cpu().numpy()
-    Z = st.cl[3].detach()
     return (Z.double() @ st.Wp[:Z.shape[1], :D].double() + st.b.detach().double()).float().cpu().numpy()
 
 
@@ -280,7 +278,7 @@ def test_fused_stack_intermediates_match_reference_goldens(name):
         else:                                                                                # folded one-head output layer
             assert cfg.final in ("collapse", "collapse_z") and st.cl is not None
             alpha = torch.empty_like(want_alpha)
-            alpha[eid.cpu()] = st.cl[1].cpu().reshape(-1, 1)
+            alpha[eid.cpu()] = st.cl.alpha.cpu().reshape(-1, 1)
             hn = g.ndata["h"].tensor().detach().cpu()[::step]                              # the same layer, unfolded: N x out_dim
             np.testing.assert_allclose(hn.numpy(), want_out.numpy(), rtol=1e-4, atol=2e-5, err_msg=f"layer {l} out (unfolded)")
         np.testing.assert_allclose(alpha.numpy(), want_alpha.numpy(), rtol=1e-4, atol=2e-6, err_msg=f"layer {l} alpha")

@@ -208,3 +208,65 @@ def test_the_expected_route_runs_and_agrees_with_the_oracle(c, monkeypatch):
             #  the step's gradient scale and to sqrt(G).  Wide sweeps found 2.7e-6 at G = 4,096, and 4e-7 of the largest gradient on EACH side of a 2e-4-sized attn_r -- the device nearer to float64 than the oracle)
             np.testing.assert_allclose(p.grad.cpu().numpy(), ref, rtol=2e-3,
                                        atol=3e-4 * float(np.abs(ref).max()) + 2e-6 * max(1.0, (c["G"] / 256.0) ** 0.5) + 1e-6 * gscale, err_msg=k)
+
+
+def test_a_stale_matcher_job_falls_back_to_the_inline_kernels(monkeypatch):
+    """The stack runs the matcher's job (ops.folded_match_job) and its Z sweep carries T; then the matcher's weight is written in place
+    (same values, another version) before the matcher runs.  ops.FoldJob.matches must refuse the job: the matcher forms V / T itself
+    ('inline'), drops what rode in the sweep, hands dZ back through autograd, and the stack's backward is the plain 'collapse' one.
+    Scores and every parameter gradient against the same seeded step without the write (route 'edot' / 'fused+edot': the same sums,
+    re-associated), to the tolerances test_the_expected_route_runs_and_agrees_with_the_oracle holds the device to.
+    The case: the smallest one with routes ('folded', 'collapse_z+edot', 'edot', 'fused+edot') -- PGAT, heads [4, 1], stacked queries,
+    G = 256 = 8 queries x 32 pairs (the smallest G that takes the stacked-runs route)."""
+    from taxoexpan_amd import TaxoExpan, model_zoo as mz, ops, synthetic as syn
+    c = dict(prop="PGAT", readout="WMR", match="LBM", heads=[4, 1], hidden=16, grad=True, queries="stacked", hook=None, G=256)
+    dev = torch.device("cuda:0")
+    nq, per = 8, 32
+    tax = syn.make_taxonomy(3000, 4700, 12, seed=8)
+    g, qf, _labels = syn.training_batch(tax, nq, per - 1, seed=5 + c["G"])
+    x = g.ndata.pop("x").to(dev)
+    pos = g.ndata["pos"].to(dev)
+    if _expected(c, int(x.shape[0])) != ("folded", "collapse_z+edot", "edot", "fused+edot"):
+        pytest.skip("the test route (TXE_TEST_ROUTE) switches the matcher's job in the Z sweep off")
+    torch.manual_seed(11)
+    model = TaxoExpan("PGAT", "WMR", "LBM", in_dim=12, hidden_dim=16, out_dim=24, pos_dim=4, num_layers=1, heads=[4, 1], feat_drop=0.0,
+                      attn_drop=0.0, hidden_drop=0.0, out_drop=0.0).to(dev).train()
+    monkeypatch.setattr(ops, "new_seed", lambda: 1234567 + c["G"])
+    Wm = model.match.W.weight
+    with torch.no_grad():
+        Wm.mul_(3.0)                                                 # (spread the scores, as the test above)
+    q = qf.to(dev)
+    target = torch.zeros(nq, dtype=torch.long, device=dev)
+
+    def step(stale):
+        model.zero_grad()
+        g.ndata["pos"] = pos
+        g.ndata["h"] = model.graph_propagate(g, x)
+        hv = model.readout(g, pos)
+        assert isinstance(hv, mz.DeferredGraphVector) and not hv.started() and hv.can_fold()
+        ops.ROUTES.clear()
+        if stale:
+            _Z, _Wp, link = hv._run_z(ops.folded_match_job(q, None, None, Wm))
+            assert ops.ROUTES["stack"] == "collapse_z+edot" and link.carried_T and link.fwd.matches(_Wp, Wm, q, None, None, c["G"])
+            with torch.no_grad():
+                Wm.mul_(1.0)                                         # values unchanged, version bumped
+            assert not link.fwd.matches(_Wp, Wm, q, None, None, c["G"])
+        s = hv.match_folded(Wm, model.match.apply_exp, q)
+        fold = ops.ROUTES["fold"]
+        torch.nn.functional.cross_entropy(s.reshape(nq, -1), target, reduction="sum").backward()
+        torch.cuda.synchronize()
+        if stale:
+            assert link.fwd is None and link.e_part is None and not link.dz_implicit
+        return (s.detach().cpu().numpy(), {k: p.grad.cpu().numpy() for k, p in model.named_parameters()}, fold, ops.ROUTES["stack_bwd"])
+    s_ref, g_ref, fold_ref, bwd_ref = step(False)
+    assert (fold_ref, bwd_ref) == ("edot", "fused+edot")
+    s, grads, fold, bwd = step(True)
+    assert fold == "inline"
+    assert bwd == "collapse"
+    print("stale job: max |ds|", float(np.abs(s - s_ref).max()), "of", float(np.abs(s_ref).max()),
+          {k: float(np.abs(grads[k] - g_ref[k]).max() / max(np.abs(g_ref[k]).max(), 1e-30)) for k in g_ref})
+    np.testing.assert_allclose(s, s_ref, rtol=1e-4, atol=2e-5 * float(np.abs(s_ref).max()))
+    gscale = max(float(np.abs(v).max()) for v in g_ref.values())
+    for k, ref in g_ref.items():                                     # (that test's gradient rule)
+        np.testing.assert_allclose(grads[k], ref, rtol=2e-3,
+                                   atol=3e-4 * float(np.abs(ref).max()) + 2e-6 * max(1.0, (c["G"] / 256.0) ** 0.5) + 1e-6 * gscale, err_msg=k)

@@ -327,6 +327,87 @@ def test_matcher_route_decision_and_deferred_vector_protocol_on_the_host():
         ops._NO_MATCH_FOLD = prev
 
 
+def test_layer_states_have_every_field_from_the_start():
+    """ops._GatLayerState / _GcnLayerState: every slot is readable on a fresh state -- buffers and the folded layer's record `cl` None,
+    the flags False -- so nothing has to ask whether a field exists"""
+    from taxoexpan_amd import ops
+    for cls, flags in ((ops._GatLayerState, ("vx", "x_dropped", "prepared")), (ops._GcnLayerState, ("x_dropped",))):
+        st = cls()
+        for name in cls.__slots__:
+            getattr(st, name)                                                    # (AttributeError: a slot __init__ forgot)
+        assert all(getattr(st, f) is False for f in flags)
+        assert st.cl is None and all(getattr(st, b) is None for b in ("X", "Wp", "mask", "W", "P"))
+    st = ops._GatLayerState()
+    assert st.Y is None and st.alpha is None and st.Xt is None and st.pos is None
+    assert ops.GatFolded._fields == ("a12", "alpha", "coef", "wsum", "gid", "Z", "hg") and ops.GcnFolded._fields == ("coef", "wsum", "gid", "Z")
+    for cfg in (ops.GATConfig([4, 1], [8, 8], [2, 2], 5, 0.2, 0.01, 0.0, 0.0, "mean", 1), ops.GCNConfig([8, 8], 5, [0.01, None], [0.0, 0.0], 1)):
+        assert cfg.grad_enabled is True and cfg.link is None and cfg.fold_job is None
+    assert cfg.final == "layers"                                                 # (GCNConfig: the route string of an unfolded stack)
+
+
+def _fold_job(e2, rows, run_off, Wm, Wp, U):
+    """an ops.FoldJob as folded_match_job's callable builds it (that needs the device), on host tensors"""
+    from taxoexpan_amd import ops
+    Q = e2 if rows is None else rows
+    return ops.FoldJob(e2, rows, run_off, Wm, Wp, Q, Q.stride(0), run_off, None, U, int(rows is None), torch.zeros(U, 6), torch.zeros(U, 32), None)
+
+
+def test_fold_job_is_stale_after_a_write_to_the_matcher_weight_or_for_other_tensors():
+    """ops.FoldJob.matches: the very (Wp, Wm, e2, rows, run_off) objects, Wm unwritten since; the stacked form also the row count"""
+    Wp, Wm, e2 = torch.zeros(128, 32), torch.randn(1, 6, 4), torch.randn(8, 4)
+    job = _fold_job(e2, None, None, Wm, Wp, 8)
+    assert job.score is None and job.matches(Wp, Wm, e2, None, None, 8)
+    assert not job.matches(Wp, Wm, e2.clone(), None, None, 8)                    # equal values, another tensor
+    assert not job.matches(Wp.clone(), Wm, e2, None, None, 8)
+    assert not job.matches(Wp, Wm, e2, None, None, 16)                           # stacked form: runs found in other rows (U != G)
+    rows, off = torch.randn(2, 4), torch.tensor([0, 4, 8], dtype=torch.int32)
+    given = _fold_job(None, rows, off, Wm, Wp, 2)
+    assert given.matches(Wp, Wm, None, rows, off, 8) and given.matches(Wp, Wm, None, rows, off, 16)
+    assert not given.matches(Wp, Wm, None, rows, off.clone(), 8) and not given.matches(Wp, Wm, e2, None, None, 8)
+    Wm.mul_(1.0)                                                                 # same values, version bumped
+    assert not job.matches(Wp, Wm, e2, None, None, 8) and not given.matches(Wp, Wm, None, rows, off, 8)
+
+
+def test_query_prefetch_token_is_stale_after_a_write_to_either_operand():
+    """ops.QueryPrefetch.matches (bilinear_query_prefetch's token; nothing is launched here)"""
+    from taxoexpan_amd import ops
+    for write in ("e2", "W", None):
+        e2, W = torch.randn(8, 4), torch.randn(1, 6, 4)
+        tok = ops.QueryPrefetch(e2, W, e2, 4, W[0], torch.zeros(8, 6), None)
+        assert tok.matches(e2, W, 8, 6) and not tok.launched
+        assert not tok.matches(e2, W, 8, 5) and not tok.matches(e2, W, 7, 6)     # V of another shape
+        assert not tok.matches(e2.clone(), W, 8, 6) and not tok.matches(e2, W.clone(), 8, 6)
+        if write is not None:
+            (e2 if write == "e2" else W).add_(0.0)
+            assert not tok.matches(e2, W, 8, 6), write
+
+
+def test_fold_link_names_its_two_stages():
+    """ops.FoldLink: carried_T needs e_part AND a job with its score record; dz_implicit needs e_part AND the matcher's ds; without
+    the latter the fused backward gets the seven absent edot arguments"""
+    from taxoexpan_amd import ops
+    none7 = (None, None, None, 0, None, None, None)
+    link = ops.FoldLink()
+    assert not link.carried_T and not link.dz_implicit and link.edot_args(None) == none7
+    assert (link.part, link.S, link.by_k, link.one_col, link.fwd, link.e_part, link.ds, link.s) == (None, 0, False, -1, None, None, None, None)
+    job = _fold_job(torch.randn(8, 4), None, None, torch.randn(1, 6, 4), torch.zeros(128, 32), 8)
+    link.e_part = torch.zeros(20, 1)
+    assert not link.carried_T                                                    # no job
+    link.fwd = job
+    assert not link.carried_T                                                    # a job whose T did not ride in a sweep
+    job.score = ops.FoldScore(torch.zeros(9, dtype=torch.int32), 20, 8, 16, 4, torch.zeros(20), torch.zeros(8), 0.0, 0)
+    assert link.carried_T and not link.dz_implicit and link.edot_args(None) == none7
+    link.e_part = None
+    assert not link.carried_T
+    link.ds, link.s, link.apply_exp = torch.zeros(8), torch.zeros(8), 1
+    assert not link.dz_implicit and link.edot_args(None) == none7                # ds without e_part
+    link.e_part = torch.zeros(20, 1)
+    assert link.dz_implicit and link.carried_T
+    link.ds = None
+    assert not link.dz_implicit and link.edot_args(None) == none7
+    assert not ops._NO_LINK.dz_implicit and ops._NO_LINK.S == 0 and ops._NO_LINK.part is None
+
+
 def test_loss_tensor_backward_starts_from_a_unit_gradient_only_when_asked_plainly():
     """loss.LossTensor: `loss.backward()` hands autograd a cached constant 1 (on the device); anything else -- an explicit gradient,
     arithmetic on the loss, a host tensor -- is the ordinary torch path.  Here: the host-side mechanics (no GPU: the plain path)."""
