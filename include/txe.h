@@ -325,6 +325,23 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
                    void* stream);
 
+/* ---- retrieval stage of the two-stage test protocol (data_loader/dataset.py:316-330; csrc/txe_retrieve.hip) -------------------------
+ * txe_row_normalize: y[i] = x[i] / ||x[i]||_2 (fp32, any pitch, y apart from x): cosine similarity then is a plain dot product, formed by
+ * txe_score_block with apply_exp = 0.  A zero-norm or non-finite row becomes NaN and gives NaN similarities.
+ * txe_select_k: out_idx [nq][k] = per row of S [nq][G] (pitch ld_s; never written) the k columns with the largest value that the row's
+ * mask list does not name, best first, equal values by ascending column, NaN last (NaN takes the place of -inf; -0.0 == +0.0) -- the
+ * order of txe_topk_merge; -1 where the row has fewer than k unmasked columns.  out_key [nq][k] (may be NULL) = those values (NaN as
+ * -inf; -inf in the unused slots).  Masks: CSR, row q masks the columns mask_idx[mask_off[q] .. mask_off[q+1]) (any order, duplicates
+ * and empty lists allowed, a column outside [0, G) names nothing); both NULL = no masks.  With masks ws holds
+ * txe_select_k_ws_bytes(nq, G) bytes (a bitmap, rewritten by every call), else TXE_ERR_WORKSPACE; without, ws may be NULL.
+ * One workgroup per row, integer histograms and a sort on distinct keys: the result is a pure function of S and the masks.
+ * TXE_ERR_ARG (before any device work): k < 1 or k > 4096, a NULL S / out_idx, one of mask_off / mask_idx without the other, nq < 0,
+ * G < 1, ld_s < G. */
+int txe_row_normalize(const float* x, long long ld_x, int n, int d, float* y, long long ld_y, void* stream);
+size_t txe_select_k_ws_bytes(int nq, int G);
+int txe_select_k(const float* S, long long ld_s, int nq, int G, const int* mask_off, const int* mask_idx, int k, int* out_idx, float* out_key,
+                 void* ws, size_t ws_bytes, void* stream);
+
 /* ---- all-candidate scoring loop of the MLP matcher (model_zoo.py:285-298 under test_fast.py:121-123 / infer.py:97-99) ---------------
  * W1 = ffn[0].weight [H][l+r] = [W1a | W1b], b1, w2 = ffn[2].weight [H], b2 = ffn[2].bias [1].  A = hg W1a^T + b1 [G][H] comes from
  * txe_linear_fwd (x2 = NULL); then S[q][g] = b2 + sum_h w2[h] relu(A[g][h] + B[q][h]), B = Qf W1b^T, is evaluated on the VALU as

@@ -6,7 +6,8 @@ import numpy as np
 import torch
 
 from .graph import device_egonet_batch
-from .scoring import encode_candidates, fused_matcher_ok, prepare_matcher, rank_all_fused, topk_parents, topk_parents_fused
+from .scoring import (_retrieve_args, encode_candidates, fused_matcher_ok, prepare_matcher, rank_all_fused, retrieve_candidates, topk_parents,
+                      topk_parents_fused)
 
 
 def candidate_graphs(dtax, anchors, expand_factor, seed, batch_size=-1):
@@ -69,6 +70,80 @@ def _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock):
     return torch.cat(out) if out else torch.zeros(0, dtype=torch.int32, device=hg.device)
 
 
+def _retrieval_masks(dataset, queries, index):
+    """node2masks[q] (descendants, parents, q itself, roots: dataset.py:262-268) as candidate rows, CSR over the queries"""
+    off, idx = [0], []
+    for q in queries:
+        idx.extend(sorted(index[a] for a in dataset.node2masks[q] if a in index))
+        off.append(len(idx))
+    return np.asarray(off, dtype=np.int64), np.asarray(idx, dtype=np.int64)
+
+
+def _retrieved_groups(model, hg, qf, pos_off, pos_idx, ridx, larger_is_better, qblock):
+    """the retrieve-then-rank instances of dataset.py:316-330 as one labelled score vector: per query its positives (label 1) followed by
+    its k retrieved candidate rows `ridx` (label 0; a -1 slot scores worst, so it never counts against a positive).  Only these pairs
+    are scored: the prepared matcher's gathered route for BIM / LBM / MLP, model.match on the gathered rows for anything else.
+    Returns (score [B] fp32, label [B] int32, ret_dst [Q, k] = where each retrieved slot sits in them)."""
+    dev = hg.device
+    Q, k = ridx.shape
+    pos_off = np.asarray(pos_off, dtype=np.int64)
+    cnt = np.diff(pos_off)
+    n_pos = int(pos_off[-1])
+    goff_h = pos_off + np.arange(Q + 1, dtype=np.int64) * k
+    B = int(goff_h[-1])
+    if B >= 2 ** 31:
+        raise ValueError("retrieve: positives + queries x k must stay below 2^31 pairs")
+    up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev, non_blocking=True)
+    pos_dst = up(np.arange(n_pos, dtype=np.int64) + np.repeat(np.arange(Q, dtype=np.int64), cnt) * k, torch.int64)
+    ret_dst = up((goff_h[:-1] + cnt)[:, None] + np.arange(k, dtype=np.int64)[None, :], torch.int64)
+    rows = torch.empty(B, dtype=torch.int64, device=dev)
+    rows[pos_dst] = up(pos_idx, torch.int64)
+    rows[ret_dst.reshape(-1)] = ridx.reshape(-1).clamp(min=0).long()
+    label = torch.zeros(B, dtype=torch.int32, device=dev)
+    label[pos_dst] = 1
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    block = max(1, min(int(qblock) if qblock else 1024, Q, max(1, 2 ** 20 // (k + 1))))     # <= ~1 M gathered candidate rows per block
+    fused = fused_matcher_ok(model.match)
+    if fused:
+        pm = prepare_matcher(model.match, hg)
+        Qp = pm.queries(qf)
+        goff = up(goff_h, torch.int32)
+    else:
+        qid = up(np.repeat(np.arange(Q, dtype=np.int64), cnt + k), torch.int64)
+    for q0 in range(0, Q, block):
+        q1 = min(q0 + block, Q)
+        lo, hi = int(goff_h[q0]), int(goff_h[q1])
+        if fused:
+            pm.positives(Qp[q0:q1], goff[q0:q1 + 1] - lo, rows[lo:hi], score[lo:hi])
+        else:
+            score[lo:hi] = model.match(hg[rows[lo:hi]], qf[qid[lo:hi]]).reshape(-1)
+    flat = ret_dst.reshape(-1)
+    worst = torch.full((), -float("inf") if larger_is_better else float("inf"), device=dev)
+    score[flat] = torch.where(ridx.reshape(-1) < 0, worst, score[flat])
+    return score, label, ret_dst
+
+
+def _best_retrieved(score, ret_dst, ridx, topk, larger_is_better):
+    """the `topk` best of every query's retrieved rows by matcher score, best first, equal scores by ascending candidate row, NaN last
+    (the order of topk_parents): int32 [Q, min(topk, k)] candidate rows, -1 where fewer were retrieved"""
+    from . import ops
+    key = score[ret_dst]
+    key = key if larger_is_better else -key
+    key = torch.where(torch.isnan(key), torch.full_like(key, -float("inf")), key).contiguous()
+    empty = 0x7fffffff
+    idx = torch.where(ridx >= 0, ridx, torch.full_like(ridx, empty)).contiguous()
+    kk = min(int(topk), idx.shape[1])
+    if idx.shape[0] == 0 or kk < 1:
+        return idx[:, :0]
+    if kk <= 8:
+        return ops.topk_merge(key, idx, kk)[0]
+    o1 = torch.sort(idx, dim=1, stable=True).indices                       # columns ascending (empty slots last), then keys descending
+    idx, key = torch.gather(idx, 1, o1), torch.gather(key, 1, o1)
+    o2 = torch.sort(key, dim=1, descending=True, stable=True).indices
+    idx = torch.gather(idx, 1, o2)[:, :kk]                                  # (an empty slot: key -inf, the largest column -- last)
+    return torch.where(idx == empty, torch.full_like(idx, -1), idx)
+
+
 def _case_rows(dataset, queries, pos_off, ranks, top, metric_names):
     """the case-study table of test_fast.py:112-147: per test query its name, true parents, predicted top-5 parents and every
     metric evaluated on that query's ranks alone (`metric([ranks])`, model/metric.py:62-90), as strings"""
@@ -88,14 +163,23 @@ def _case_rows(dataset, queries, pos_off, ranks, top, metric_names):
 
 
 def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0, batch_size=-1, case=None, metric_names=CASE_METRICS,
-             topk=5):
+             topk=5, retrieve=None):
     """dataset: taxoexpan_amd.dataset.MaskedGraphDataset in 'validation' or 'test' mode.  Returns (metrics dict, ranks int32
     [n_positives], pos_off [Q+1], queries list).  Queries whose true parents are not candidate positions are skipped, like the
     reference's rearrange() would fail on them.
     case: test_fast.py's `-c` -- a path (the TSV of :142-147 is written) or a list (the rows are appended): per query its name, true
     parents, the `topk` predicted parents (best first: descending score when larger_is_better, i.e. the info_nce losses, ascending
-    otherwise; ties in candidate order like Python's stable sort) and the metrics of `metric_names` on that query alone."""
+    otherwise; ties in candidate order like Python's stable sort) and the metrics of `metric_names` on that query alone.
+    retrieve: None = every positive against ALL candidates, unmasked (test_fast.py; `dataset.test_topk` is ignored).  retrieve=k
+    (1 <= k <= 4096, else ValueError before any launch) = the retrieve-then-rank protocol of dataset.py:316-330 (`-k`): a query's
+    instance is its true parents plus the k candidates nearest to it by cosine distance of `dataset.node_features` among those
+    node2masks[q] does not name (scoring.retrieve_candidates); only those pairs are scored, a rank is 1 + the retrieved candidates
+    strictly better (metric.obtain_ranks' grouped ranking), `case` lists the best `topk` of the retrieved rows only, and the metrics
+    dict gains n_retrieved = k.  Deviations from the reference: exact distance ties break by ascending candidate id (there: the
+    iteration order of a Python set), and the selection compares fp32 similarities of normalised rows instead of numpy's 1 - cos."""
     device = torch.device(device)
+    if retrieve is not None:
+        retrieve = _retrieve_args(retrieve, None, None)[0]
     cand = sorted(dataset.all_positions)                                    # test_fast.py:93
     index = {a: i for i, a in enumerate(cand)}
     dtax = dataset.device_taxonomy(device)
@@ -113,10 +197,27 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     pos_idx = np.concatenate(pos_lists).astype(np.int64) if pos_lists else np.zeros(0, dtype=np.int64)
     qf = dataset.node_features[torch.as_tensor(queries, dtype=torch.long)].to(device)
     with torch.no_grad():
-        ranks = _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock)
+        if retrieve is None:
+            ranks = _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock)
+        else:
+            from .metric import _device_group_ranks
+            cf = dataset.node_features[torch.as_tensor(cand, dtype=torch.long)].to(device)     # the rows `kv` holds (dataset.py:227-229)
+            ridx = retrieve_candidates(qf, cf, retrieve, *_retrieval_masks(dataset, queries, index)) if queries else \
+                torch.zeros((0, retrieve), dtype=torch.int32, device=device)
+            if queries:
+                score, label, ret_dst = _retrieved_groups(model, hg, qf, pos_off, pos_idx, ridx, larger_is_better, qblock)
+                ranks = _device_group_ranks(score, label, 1 if larger_is_better else 0)[0][:len(pos_idx)]
+            else:
+                ranks = torch.zeros(0, dtype=torch.int32, device=device)
         if case is not None:                                               # test_fast.py:112-147
             cand_ids = torch.as_tensor(np.asarray(cand, dtype=np.int64), device=device)
-            top = _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock).cpu().tolist()
+            if retrieve is None:
+                top = _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock).cpu().tolist()
+            elif queries:
+                best = _best_retrieved(score, ret_dst, ridx, topk, larger_is_better).cpu().tolist()
+                top = [[cand[i] for i in row if i >= 0] for row in best]
+            else:
+                top = []
             rows = _case_rows(dataset, queries, pos_off, ranks, top, metric_names)
             if isinstance(case, list):
                 case.extend(rows)
@@ -131,18 +232,25 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
                    hit_at_3=_per_query_means(ranks <= 3, pos_off), hit_at_5=_per_query_means(ranks <= 5, pos_off),
                    mrr_scaled_10=_per_query_means(1.0 / torch.ceil(r / 10.0), pos_off), n_queries=len(queries),
                    n_candidates=len(cand))
+    if retrieve is not None:
+        metrics["n_retrieved"] = retrieve
     return metrics, ranks, pos_off, queries
 
 
 def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-1, save=None, topk=5, normalize=False, qblock=1024,
-          seed=0):
+          seed=0, retrieve=None):
     """infer.py:77-159: the `topk` best parents of every NEW term.  dataset: MaskedGraphDataset in 'test' mode (infer.py:43-57);
     new_taxons: path of the `<name>\t<v0 v1 ...>` file (infer.py:23-38) or an already loaded (vocab, array) pair.  Candidates are ALL
     nodes of the dataset's graph (infer.py:80-82 iterates `test_dataset.graph.nodes()`, not `all_positions`), in node order; best =
     descending score for the info_nce losses, ascending otherwise (infer.py:100-106), ties in candidate order like Python's stable
-    sort.  Returns [(query, [parent vocab entries])]; `save` writes infer.py's TSV (header `Query\tPredicted parents`)."""
+    sort.  Returns [(query, [parent vocab entries])]; `save` writes infer.py's TSV (header `Query\tPredicted parents`).
+    retrieve=k (infer.py's `-k`; 1 <= k <= 4096, else ValueError before any launch): the candidates of each new term are its k
+    cosine-nearest graph nodes (the new-term vectors against `dataset.node_features`; no masks, a new term has none), and the `topk`
+    best parents are chosen among them by matcher score.  Exact distance ties break by ascending node position."""
     from .dataset import load_new_taxons
     device = torch.device(device)
+    if retrieve is not None:
+        retrieve = _retrieve_args(retrieve, None, None)[0]
     vocab, nf = load_new_taxons(new_taxons, normalize) if isinstance(new_taxons, (str, bytes)) or hasattr(new_taxons, "__fspath__") else new_taxons
     anchors = np.asarray(list(dataset.graph.nodes), dtype=np.int64)
     dtax = dataset.device_taxonomy(device)
@@ -154,7 +262,17 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     qf = torch.as_tensor(np.asarray(nf), dtype=torch.float32).to(device)
     cand_ids = torch.as_tensor(anchors, device=device)
     with torch.no_grad():
-        picks = _best_parents(model, hg, qf, cand_ids, topk, larger, qblock).cpu().tolist()
+        if retrieve is None:
+            picks = _best_parents(model, hg, qf, cand_ids, topk, larger, qblock).cpu().tolist()
+        elif qf.shape[0] == 0 or len(anchors) == 0:
+            picks = [[] for _ in range(qf.shape[0])]
+        else:
+            cf = dataset.node_features[torch.as_tensor(anchors, dtype=torch.long)].to(device)
+            ridx = retrieve_candidates(qf, cf, retrieve)
+            score, _label, ret_dst = _retrieved_groups(model, hg, qf, np.zeros(qf.shape[0] + 1, dtype=np.int64), np.zeros(0, dtype=np.int64),
+                                                       ridx, larger, qblock)
+            best = _best_retrieved(score, ret_dst, ridx, topk, larger).cpu().tolist()
+            picks = [[int(anchors[i]) for i in row if i >= 0] for row in best]
     model.train(was_training)
     out = [(q, [dataset.vocab[i] for i in row]) for q, row in zip(vocab, picks)]
     if save is not None:

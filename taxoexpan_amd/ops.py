@@ -1955,6 +1955,72 @@ def topk_merge(keys, idx, k):
     return out_i, out_k
 
 
+SELECT_K_MAX = 4096     # txe_select_k keeps its survivors in LDS
+
+
+def normalized_rows(x, pack=True):
+    """x / ||x||_2 per row (txe_row_normalize) as a BilinearPrepared: rows zero-padded to whole 32-column k-tiles and, on the split
+    route (pack), their bf16 planes packed once -- the candidate side of a cosine_block loop; `.full[:n]` is the padded query side.  A
+    zero-norm or non-finite row becomes NaN."""
+    _need_cuda(x)
+    x, ld = _rows(x)
+    n, d = x.shape
+    rp = (d + 31) // 32 * 32
+    full = torch.zeros((max(n, 1), rp), dtype=torch.float32, device=x.device)
+    planes = None
+    with _lib.on_device(x.device):
+        call("txe_row_normalize", ptr(x), ld, n, d, ptr(full), rp, _lib.stream_ptr())
+        if pack and not _NO_SPLIT_GEMM and n >= 1:
+            planes = torch.empty(pure("txe_split_packed_bytes", n, rp), dtype=torch.uint8, device=x.device)
+            call("txe_split_pack", ptr(full), rp, n, rp, 1, ptr(planes), _lib.stream_ptr())
+    return BilinearPrepared(full, n, d, rp, planes, full._version)
+
+
+def cosine_block(Qn, Cn, out):
+    """out [nq, G] = Qn Cn^T on the score GEMM (txe_score_block, no exp): Qn = rows of normalized_rows(queries).full (padded like the
+    candidates), Cn = normalized_rows(candidates)"""
+    _need_cuda(Qn, Cn.full, out)
+    assert Qn.dtype == torch.float32 and Qn.stride(1) == 1 and Qn.stride(0) == Cn.rp and out.dtype == torch.float32 and out.stride(1) == 1
+    nq, G, K = Qn.shape[0], Cn.G, Cn.rp
+    assert out.shape == (nq, G)
+    with _lib.on_device(Qn.device):
+        tws = _tail_ws(Qn)
+        up = _planes(Cn, K)
+        sws, swb = _score_sws(nq, G, K, Qn, up is not None)
+        call("txe_score_block", ptr(Qn), Cn.rp, nq, ptr(Cn.full), Cn.rp, G, K, 0, ptr(out), out.stride(0), ptr(tws), tws.numel(), ptr(sws), swb,
+             ptr(up), _lib.stream_ptr())
+    return out
+
+
+def select_k(S, k, mask_off=None, mask_idx=None, want_keys=False, out=None):
+    """per row of S [nq, G] (fp32, unit column stride, any row pitch; not written) the k unmasked columns with the largest value, best
+    first, equal values by ascending column, NaN last; -1 where fewer than k exist (txe_select_k).  Masks: CSR on the device, int32
+    mask_off [nq + 1] indexing into mask_idx.  Returns idx int32 [nq, k], or (idx, keys fp32 [nq, k]) with want_keys."""
+    _need_cuda(S, mask_off, mask_idx)
+    k = int(k)
+    if not 1 <= k <= SELECT_K_MAX:
+        raise ValueError(f"select_k: 1 <= k <= {SELECT_K_MAX}, got {k}")
+    if (mask_off is None) != (mask_idx is None):
+        raise ValueError("select_k: mask_off and mask_idx go together")
+    assert S.dim() == 2 and S.dtype == torch.float32 and S.stride(1) == 1 and S.shape[1] >= 1 and (S.shape[0] <= 1 or S.stride(0) >= S.shape[1])
+    nq, G = S.shape
+    idx = out if out is not None else torch.empty((nq, k), dtype=torch.int32, device=S.device)
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.shape == (nq, k)
+    keys = _empty((nq, k), S) if want_keys else None
+    if mask_idx is not None and mask_idx.numel() == 0:
+        mask_off = mask_idx = None                         # nothing is masked: no bitmap
+    if nq > 0:
+        if mask_off is not None:
+            assert mask_off.dtype == torch.int32 and mask_idx.dtype == torch.int32 and mask_off.numel() == nq + 1
+            assert mask_off.is_contiguous() and mask_idx.is_contiguous()
+        with _lib.on_device(S.device):
+            wsb = pure("txe_select_k_ws_bytes", nq, G) if mask_off is not None else 0
+            ws = _ws(wsb, S) if wsb else None
+            call("txe_select_k", ptr(S), S.stride(0) if nq > 1 else max(S.stride(0), G), nq, G, ptr(mask_off), ptr(mask_idx), k, ptr(idx),
+                 ptr(keys), ptr(ws), wsb, _lib.stream_ptr())
+    return (idx, keys) if want_keys else idx
+
+
 def rank_finalize(pos_off, thr, counts, larger_is_better=True, out=None):
     """ranks (int32) from the fused counts: positives never count against each other (metric.py:7-31).  out: int32 [>= n_pos]"""
     _need_cuda(thr)

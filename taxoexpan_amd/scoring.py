@@ -535,6 +535,108 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
     return candidate_ids.to(dev)[idx.long()]
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# retrieval stage (data_loader/dataset.py:316-330): the k unmasked candidates nearest to a query by cosine distance
+# ---------------------------------------------------------------------------------------------------------------
+RETRIEVE_K_MAX = 4096                        # ops.SELECT_K_MAX: the select kernel keeps its survivors in LDS
+RETRIEVE_BLOCK_BYTES = 256 * 2 ** 20         # one [block, G] similarity block stays at or below this
+
+
+def _retrieve_args(k, mask_off, mask_idx, n_queries=None, n_candidates=None):
+    """the argument rules of retrieve_candidates / host_retrieve / host_select_k, checked before anything runs; the masks come back as
+    host int64 arrays (or None, None)"""
+    import numpy as np
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= RETRIEVE_K_MAX:
+        raise ValueError(f"retrieval: 1 <= k <= {RETRIEVE_K_MAX}, got {k!r}")
+    if (mask_off is None) != (mask_idx is None):
+        raise ValueError("retrieval: masks are a CSR -- mask_off [Q + 1] and mask_idx go together")
+    if mask_off is None:
+        return int(k), None, None
+    off = np.asarray(torch.as_tensor(mask_off).cpu(), dtype=np.int64).reshape(-1)
+    idx = np.asarray(torch.as_tensor(mask_idx).cpu(), dtype=np.int64).reshape(-1)
+    if n_queries is not None and off.shape[0] != n_queries + 1:
+        raise ValueError(f"retrieval: mask_off holds {off.shape[0]} entries for {n_queries} queries (Q + 1 wanted)")
+    if off.shape[0] < 1 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != idx.shape[0] or idx.shape[0] >= 2 ** 31:
+        raise ValueError("retrieval: mask_off must rise from 0 to len(mask_idx)")
+    if n_candidates is not None and idx.size and (idx.min() < 0 or idx.max() >= n_candidates):
+        raise ValueError("retrieval: mask_idx names a column outside the candidates")
+    return int(k), off, idx
+
+
+def host_select_k(S, k, mask_off=None, mask_idx=None):
+    """numpy restatement of txe_select_k: per row of S the k unmasked columns with the largest value, best first, equal values by
+    ascending column, NaN last (as -inf); int32 [nq, k], -1 where fewer than k unmasked columns exist.  S is compared in the dtype
+    it comes in."""
+    import numpy as np
+    S = np.asarray(S)
+    k, off, idx = _retrieve_args(k, mask_off, mask_idx, S.shape[0], S.shape[1])
+    out = np.full((S.shape[0], k), -1, dtype=np.int32)
+    for q in range(S.shape[0]):
+        keep = np.ones(S.shape[1], dtype=bool)
+        if off is not None:
+            keep[idx[off[q]:off[q + 1]]] = False                 # masks applied by list
+        cols = np.flatnonzero(keep)
+        key = S[q, cols].astype(np.float64)
+        key[np.isnan(key)] = -np.inf
+        best = cols[np.argsort(-key, kind="stable")[:k]]          # stable: equal keys (-0.0 == +0.0 too) keep ascending column order
+        out[q, :len(best)] = best
+    return out
+
+
+def host_retrieve(query_features, candidate_features, k, mask_off=None, mask_idx=None, block=None):
+    """retrieve_candidates on the host, in float64 (the sampler.host_draw pattern: the tests' reference and any CPU caller's route):
+    cosine similarities of the normalised rows, masks applied by list, best first, exact ties by ascending candidate row, NaN last.
+    `block` is accepted for symmetry and changes nothing."""
+    import numpy as np
+    Qf = np.asarray(torch.as_tensor(query_features).detach().cpu(), dtype=np.float64)
+    Cf = np.asarray(torch.as_tensor(candidate_features).detach().cpu(), dtype=np.float64)
+    k, off, idx = _retrieve_args(k, mask_off, mask_idx, Qf.shape[0], Cf.shape[0])
+    if Cf.shape[0] == 0 or Qf.shape[0] == 0:
+        return np.full((Qf.shape[0], k), -1, dtype=np.int32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Qn = Qf / np.linalg.norm(Qf, axis=1, keepdims=True)
+        Cn = Cf / np.linalg.norm(Cf, axis=1, keepdims=True)
+        S = Qn @ Cn.T
+    return host_select_k(S, k, off, idx)
+
+
+def retrieve_candidates(query_features, candidate_features, k, mask_off=None, mask_idx=None, block=None):
+    """The retrieval stage of the reference's two-stage test protocol (data_loader/dataset.py:316-330, `-k` of test_fast.py / infer.py) on
+    the device: idx int32 [Q, k] = for every query the k candidate rows nearest by cosine distance that its mask list does not name,
+    nearest first, -1 where fewer than k unmasked candidates exist.  mask_off [Q + 1] / mask_idx: CSR of masked candidate rows per query
+    (any order, duplicates allowed); both None: nothing is masked.
+    Rows are normalised once (txe_row_normalize), a block of queries is one score GEMM without exp (the fp32-accurate bf16-pipe product
+    of the scoring loop) and one masked select-k launch (txe_select_k).  block: queries per launch; default: as many as keep the
+    [block, G] similarity block at or below 256 MB -- a [Q, G] matrix for all queries is never allocated.
+    Deviations from the reference: exact distance ties break by ascending candidate row (the reference: iteration order of a Python set),
+    and the selection runs on fp32 similarities of normalised rows, not on numpy's 1 - cos: the same order wherever two distances differ
+    by more than fp32 rounding.  ValueError (before any launch): k < 1, k > 4096, masks without offsets or offsets without masks."""
+    G = int(candidate_features.shape[0])
+    Q = int(query_features.shape[0])
+    k, off, idx = _retrieve_args(k, mask_off, mask_idx, Q, G)
+    ops._need_cuda(query_features, candidate_features)
+    dev = candidate_features.device
+    out = torch.full((Q, k), -1, dtype=torch.int32, device=dev)
+    if Q == 0 or G == 0:
+        return out
+    Cn = ops.normalized_rows(candidate_features)
+    Qn = ops.normalized_rows(query_features, pack=False).full
+    ld = (G + 3) // 4 * 4
+    if block is None:
+        block = RETRIEVE_BLOCK_BYTES // (4 * ld)
+    block = max(1, min(int(block), Q))
+    moff = midx = None
+    if off is not None and idx.size:
+        moff = torch.as_tensor(off, dtype=torch.int32).to(dev, non_blocking=True)
+        midx = torch.as_tensor(idx, dtype=torch.int32).to(dev, non_blocking=True)
+    S = torch.empty((block, ld), dtype=torch.float32, device=dev)
+    for q0 in range(0, Q, block):
+        q1 = min(q0 + block, Q)
+        Sb = ops.cosine_block(Qn[q0:q1], Cn, S[:q1 - q0, :G])
+        ops.select_k(Sb, k, None if moff is None else moff[q0:q1 + 1], midx, out=out[q0:q1])
+    return out
+
+
 def topk_parents(S, candidate_ids, k=5, larger_is_better=True):
     """infer.py:100-106 / test_fast.py:125-131: the k best candidate positions per query -- `sorted(enumerate(scores), key=-score)[:k]`
     (descending score for info_nce, ascending otherwise).  Python's sort is stable, so equal scores come out in ascending candidate
