@@ -112,24 +112,26 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
                       const float* attn_l, const float* attn_r, int H, int D, float feat_drop_p, const unsigned* mask, const float* d_Y,
                       int need_dh, int act_on, float act_slope, float* d_X, float* dW, float* d_attn_l, float* d_attn_r, float* dP,
                       int x_dropped, const void* Xt, int phases, void* chain, void* ws, size_t ws_bytes, void* stream);
-/* phases | 16 and need_dh: d_X = d_Y Wp (the whole input gradient of a layer above the first) runs on the bf16 matrix pipe in fp32
+/* phases | TXE_DENSE_DX_SPLIT and need_dh: d_X = d_Y Wp (the whole input gradient of a layer above the first) runs on the bf16 matrix pipe in fp32
  * accuracy, dropout mask and leaky' factor applied in its store loop; its packed operands live behind the workspace:
  * ws_bytes >= txe_gat_dense_ws_bytes + txe_gat_dense_bwd_split_ws_bytes, else TXE_ERR_WORKSPACE.  Without the bit: the fp32 MFMA,
  * whatever the size of the buffer -- the route is the caller's explicit choice. */
 size_t txe_gat_dense_bwd_split_ws_bytes(int n_nodes, int Kh, int Pd, int H, int D);
-/* phases: 7 = all of it; 1 | 2 | 4 = d_X | the weight-gradient product (split-K partial slices) | the reductions that finish dW,
- * d_attn, dP -- 1 and 2 are independent, 4 needs both.
+/* phases: TXE_DENSE_ALL = all of it; TXE_DENSE_DX | TXE_DENSE_DW | TXE_DENSE_REDUCE = d_X | the weight-gradient product (split-K partial
+ * slices) | the reductions that finish dW, d_attn, dP -- DX and DW are independent, REDUCE needs both.
  * chain (may be NULL): TXE_TAIL_CHAIN_BYTES of HOST memory, zero-filled = empty, owned by the caller for one backward pass.  The last
  * reduction launch of a layer ("phase B": dW / d_attn from the split-K slices, dP, d_pw) only finishes parameter gradients, so a
- * caller may DEFER it with phases | 64: the job is described in the chain instead of launched (its workspace and outputs must stay
- * alive), and the next call WITHOUT 64 that gets the chain -- the bottom layer's -- launches its own phase B and every deferred one
- * together.  txe_gat_tail_flush launches what a chain still holds. */
+ * caller may DEFER it with phases | TXE_PH_DEFER: the job is described in the chain instead of launched (its workspace and outputs must
+ * stay alive), and the next call WITHOUT the bit that gets the chain -- the bottom layer's -- launches its own phase B and every deferred
+ * one together.  txe_gat_tail_flush launches what a chain still holds. */
+enum { TXE_DENSE_DX = 1, TXE_DENSE_DW = 2, TXE_DENSE_REDUCE = 4, TXE_DENSE_ALL = 7, TXE_DENSE_DX_SPLIT = 16,
+       TXE_PH_DEFER = 64 /* txe_gat_dense_bwd and txe_gat_collapse_bwd_fused */ };
 #define TXE_TAIL_CHAIN_BYTES 1024
 int txe_gat_tail_flush(void* chain, void* stream);
 int txe_zero_cols(float* x, long long ld, int n_rows, int c0, int c1, void* stream);
 /* 1 when txe_gat_dense_bwd forms d_X with the streaming position-column kernel (a first PGAT layer: need_dh == 0, the columns behind
- * Kh fit 64 -- model_zoo.py:214-215): phase 1 is then ONE pass over d_Y at HBM speed that also leaves dP's per-class partial sums,
- * and belongs in line on the caller's stream (phases = 7), not beside the weight-gradient product on a second one. */
+ * Kh fit 64 -- model_zoo.py:214-215): TXE_DENSE_DX is then ONE pass over d_Y at HBM speed that also leaves dP's per-class partial sums,
+ * and belongs in line on the caller's stream (phases = TXE_DENSE_ALL), not beside the weight-gradient product on a second one. */
 int txe_gat_dx_streams(int Kh, int Pd, int need_dh);
 
 /* Eval-mode first GATLayer of a batch whose node features are rows of a feature table (test_fast.py:149-179 / infer.py:82-95
@@ -151,7 +153,7 @@ int txe_gat_aggregate_table_fwd(const int* rowptr_in, const int* col_src, int n_
  * nx_a12 != NULL (optional fused epilogue, needs 16-byte aligned rows): `out` is the padded input X' [N][nx_kp] of the NEXT, one-head
  * GATLayer (ld_out == nx_kp, its position / padding columns already in place, nx_mask = its feature keep bits or NULL), and the
  * folded attention logits of that layer are formed on the way out: nx_a12[v][r] = <dropout(X'[v]), nx_wa[r]> (nx_wa [2][nx_kp] =
- * rows D, D+1 of its packed weights) -- txe_gat_collapse_fwd then runs with a12_ready = 1.
+ * rows D, D+1 of its packed weights) -- txe_gat_collapse_fwd then runs with TXE_FOLD_A12_READY.
  * nx_a12 == NULL with nx_mask != NULL and nx_feat_drop_p > 0: `out` is the padded input of the NEXT GATLayer (ld_out == nx_kp, 16-byte
  * rows) and that layer's feature dropout is applied to the rows written (out = dropout(leaky_relu(aggregated))): its GEMMs then read a
  * plain operand (txe_gat_prepare_desc.x_dropped). */
@@ -401,59 +403,68 @@ size_t txe_gat_collapse_ws_bytes(int n_nodes, int n_edges, int G, int Kh, int Pd
 /* ws_bytes >= txe_gat_collapse_ws_bytes + txe_gat_collapse_split_ws_bytes: txe_gat_collapse_fwd forms hg = Z W^T on the bf16 matrix pipe in
  * fp32 accuracy (txe_gemm_nt_split below) */
 size_t txe_gat_collapse_split_ws_bytes(int G, int Kh, int Pd, int D);
-int txe_gat_collapse_fwd(const int* rowptr_in, const int* col_src, const int* rowptr_out, const int* col_dst, const int* pos_out,
-                         const int* graph_off, int n_nodes, int n_edges, int G, const float* X, int Kh, int Pd, const float* Wp, int D,
-                         float feat_drop_p, const unsigned* mask, float attn_slope, float attn_drop_p, unsigned long long seed,
-                         const int* pos, const float* pw, float* a12, int a12_ready /* bit 0: a12 holds the logits already; bit 1: hg = Z W^T on
-                         the bf16 matrix pipe -- ws_bytes >= txe_gat_collapse_ws_bytes + txe_gat_collapse_split_ws_bytes, else TXE_ERR_WORKSPACE */,
-                         float* alpha, float* coef, float* wsum, int* gid, float* Z,
-                         float* hg, long long ld_hg /* hg NULL: stop at Z (the consumer folds hg = Z W^T: txe_bilinear_folded_*) */,
-                         const float* Tf, const int* zrow, float* e_part /* all NULL, or (with hg NULL): see phases | 512 below */, void* ws,
-                         size_t ws_bytes, void* stream);
+/* The arguments of the folded-layer entry points, grouped by what they are; every fact lives in one struct.  Plain structs of borrowed
+ * device pointers and scalars: the caller keeps what they point to alive and may fill them once per forward pass for all the calls of a step. */
+struct txe_graph_batch {       /* the batch of graphs: both CSR orders, graph_off [G + 1] = first node of every graph */
+    const int *rowptr_in, *col_src, *rowptr_out, *col_dst, *pos_out, *graph_off; int n_nodes, n_edges, G;
+};
+struct txe_gat_fold_layer {    /* the folded GAT layer: its inputs, then what forward writes and the backward calls read */
+    const float* X; int Kh, Pd; const int* pos; int vocab /* backward only */; const float *Wp, *W, *attn_l, *attn_r /* W, attn_*: backward only */;
+    int D; float feat_drop_p; const unsigned* mask; float attn_slope, attn_drop_p; unsigned long long seed; const float* pw;
+    float *a12, *alpha, *coef, *wsum; int* gid; float *Z, *hg; long long ld_hg;   /* hg NULL: forward stops at Z (the consumer folds hg = Z W^T) */
+};
+struct txe_fold_match {        /* the folded matcher's share (txe_bilinear_folded_*): Tf [runs][Kp], zrow [G] graph -> its row of Tf, e_part
+                                * [N][txe_gat_collapse_e_tiles]; backward adds the matcher's score gradient m_ds [G], its scores m_s [G], whether it
+                                * exponentiates, and zgid [N] scratch.  A NULL struct (or NULL pointers in it): no matcher rides along */
+    float* e_part; const float *m_ds, *m_s; int m_exp; const float* Tf; const int* zrow; int* zgid;
+};
+/* flags: A12_READY: a12 holds the logits already; HG_SPLIT: hg = Z W^T on the bf16 matrix pipe -- ws_bytes >= txe_gat_collapse_ws_bytes +
+ * txe_gat_collapse_split_ws_bytes, else TXE_ERR_WORKSPACE. */
+enum { TXE_FOLD_A12_READY = 1, TXE_FOLD_HG_SPLIT = 2 };
+/* match (may be NULL; needs layer->hg == NULL): Tf, zrow and e_part all given -- see TXE_FUSED_EDOT below */
+int txe_gat_collapse_fwd(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const struct txe_fold_match* match,
+                         int flags, void* ws, size_t ws_bytes, void* stream);
 int txe_gat_collapse_e_tiles(int n_nodes, int G, int Kh, int Pd);   /* floats per node of e_part; 0: this batch cannot form it */
 /* the folded matcher's scores from e_part: s_g = [exp] <Z_g, Tf[zrow[g]]> = [exp] (scale / S_g) sum_{u in g} coef_u e_u -- no sweep over Z
  * (masked: the layer's keep mask was applied, i.e. scale = 1 / (1 - feat_drop_p)) */
 int txe_gat_collapse_fold_scores(const int* graph_off, int n_nodes, int G, int Kh, int Pd, const float* coef, const float* wsum, const float* e_part,
                                  float feat_drop_p, int masked, int apply_exp, float* s, void* stream);
-int txe_gat_collapse_bwd(const int* rowptr_in, const int* col_src, const int* rowptr_out, const int* col_dst, const int* pos_out,
-                         const int* graph_off, int n_nodes, int n_edges, int G, const float* X, int Kh, int Pd, const int* pos, int vocab,
-                         const float* Wp, const float* W, const float* attn_l, const float* attn_r, int D, float feat_drop_p,
-                         const unsigned* mask, float attn_slope, float attn_drop_p, unsigned long long seed, const float* pw,
-                         const float* a12, const float* alpha, const float* coef, const float* wsum, const int* gid, const float* Z,
-                         const float* hg, long long ld_hg, const float* d_hg, long long ld_dhg, int act_on, float act_slope, float* d_X, float* dW, float* d_attn_l,
-                         float* d_attn_r, float* dP, float* d_pw, void* ws, size_t ws_bytes, void* stream);
+struct txe_gat_fold_grads { float *dW, *d_attn_l, *d_attn_r, *dP, *d_pw; };   /* the folded layer's parameter gradients */
+int txe_gat_collapse_bwd(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const float* d_hg, long long ld_dhg,
+                         int act_on, float act_slope, float* d_X, const struct txe_gat_fold_grads* grads, void* ws, size_t ws_bytes, void* stream);
 
 /* txe_gat_collapse_bwd FUSED with txe_gat_aggregate_bwd of the GATLayer below it (one HBM sweep instead of three): the
  * gradient of the folded layer's input is formed on the fly from X, dZ and the attention-logit gradients while the layer below's
  * source-side sweep runs, and never stored.  Extra inputs: that layer's projection output Yp [N][ld_yp] = [ft | a1 | a2] (Hp heads x
- * Dp, Hp*Dp == Kh), its attention alpha_p [E][Hp] (destination-CSR order), slope / dropout / seed, the slope of the activation between
- * the layers (1 = none).  Output instead of d_X: d_Yp [N][ld_dyp] = [d_ft | d_a1 | d_a2 | n_pad zeros]; dz_p [E][Hp] scratch.
- * phases: 15 = all of it; 1 | 2 | 4 | 8 = dZ GEMM | dW GEMM partials (independent of 1 and 4: a second stream may run it under the sweeps)
- * | sweeps + first reduction stage | final reductions -- separate calls share the workspace; 8 | 64 with a chain defers the final
- * reductions (see txe_gat_dense_bwd).  | 128 (on EVERY call of one backward pass: the workspace layout depends on it): the dW product
- * runs beside other kernels on a second stream and is cut into at most 2 fat k-slices, which leave those kernels their wave slots.
- * | 256: the caller folded hg = Z W^T into the consumer of Z (txe_bilinear_folded_*; txe_gat_collapse_fwd with hg == NULL stops at Z):
- * `d_hg` IS dZ [G][Kp] (ld_dhg == Kp), hg may be NULL, phases 1 and 2 do not run, and the main part of dW comes from the caller as
- * dw_slices slices [D][Kp] at dw_main (summed in order; 0 slices: none) -- this call adds the attention rows' part.
- * | 512 (with | 256): the <dZ, X> sweep was formed in forward -- txe_gat_collapse_fwd with Tf [runs][Kp], zrow [G] (graph -> its row of Tf) and
- * e_part [N][txe_gat_collapse_e_tiles] given leaves <Tf[zrow[g]], keep X[u]> there; with the folded matcher's dZ[g] = dsl_g Tf[zrow[g]] backward
- * needs only its score gradient m_ds [G], its scores m_s [G], whether it exponentiates (m_exp), and Tf / zrow again: the fused sweep reads its
- * "dZ[g]" rows as Tf[zrow[g]] with dsl_g folded into the node coefficients -- d_hg may be NULL, dZ is never formed.
+ * Dp, Hp*Dp == Kh), its attention alpha_p [E][Hp] (destination-CSR order), slope / dropout / seed (struct txe_gat_fold_below), the slope of
+ * the activation between the layers (act_slope, 1 = none).  Output instead of d_X: d_Yp [N][ld_dyp] = [d_ft | d_a1 | d_a2 | n_pad zeros];
+ * dz_p [E][Hp] scratch.
+ * phases: TXE_FUSED_ALL = all of it; TXE_FUSED_DZ | _DW | _SWEEP | _REDUCE = dZ GEMM | dW GEMM partials (independent of DZ and SWEEP: a
+ * second stream may run it under the sweeps) | sweeps + first reduction stage (needs DZ) | final reductions (needs DW and SWEEP) --
+ * separate calls share the workspace; TXE_FUSED_REDUCE | TXE_PH_DEFER with a chain defers the final reductions (see txe_gat_dense_bwd).
+ * | TXE_FUSED_DW_BESIDE (on EVERY call of one backward pass: the workspace layout depends on it): the dW product runs beside other
+ * kernels on a second stream and is cut into at most 2 fat k-slices, which leave those kernels their wave slots.
+ * | TXE_FUSED_DZ_GIVEN: the caller folded hg = Z W^T into the consumer of Z (txe_bilinear_folded_*; txe_gat_collapse_fwd with hg == NULL
+ * stops at Z): `d_hg` IS dZ [G][Kp] (ld_dhg == Kp), hg may be NULL, DZ and DW do not run, and the main part of dW comes from the caller
+ * as dw_slices slices [D][Kp] at dw_main (summed in order; 0 slices: none) -- this call adds the attention rows' part.
+ * | TXE_FUSED_EDOT (with DZ_GIVEN): the <dZ, X> sweep was formed in forward -- txe_gat_collapse_fwd with a txe_fold_match leaves
+ * <Tf[zrow[g]], keep X[u]> in e_part; with the folded matcher's dZ[g] = dsl_g Tf[zrow[g]] backward needs only the rest of that struct:
+ * the fused sweep reads its "dZ[g]" rows as Tf[zrow[g]] with dsl_g folded into the node coefficients -- d_hg may be NULL, dZ is never
+ * formed.
+ * | TXE_FUSED_NO_EGO_WALK: the source-side sweep does not walk egonets from registers, whatever the head count (the A/B switch).
  * txe_gat_fused_bwd_supported: 1 if the shape qualifies (Hp in {1,2,4}, Hp*Dp % 16 == 0, <= 128 columns behind the feature part). */
 int txe_gat_fused_bwd_supported(int Kh, int Pd, int Hp, int Dp);
 size_t txe_gat_collapse_bwd_fused_ws_bytes(int n_nodes, int n_edges, int G, int Kh, int Pd, int D, int vocab, int Hp);
-int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const int* rowptr_out, const int* col_dst, const int* pos_out,
-                               const int* graph_off, int n_nodes, int n_edges, int G, const float* X, int Kh, int Pd, const int* pos,
-                               int vocab, const float* Wp, const float* W, const float* attn_l, const float* attn_r, int D,
-                               float feat_drop_p, const unsigned* mask, float attn_slope, float attn_drop_p, unsigned long long seed,
-                               const float* pw, const float* a12, const float* alpha, const float* coef, const float* wsum,
-                               const int* gid, const float* Z, const float* hg, long long ld_hg, const float* d_hg, long long ld_dhg,
-                               float act_slope, const float* Yp, long long ld_yp, int Hp, int Dp, float attn_slope_p,
-                               float attn_drop_p_p, unsigned long long seed_p, const float* alpha_p, float* d_Yp, long long ld_dyp,
-                               int n_pad, float* dz_p, float* dW, float* d_attn_l, float* d_attn_r, float* dP, float* d_pw, int phases,
-                               const float* dw_main, int dw_slices, const float* e_part, const float* m_ds, const float* m_s, int m_exp,
-                               const float* Tf, const int* zrow, int* zgid /* [N] scratch */, const int* walk_plan, void* chain, void* ws,
-                               size_t ws_bytes, void* stream);
+enum { TXE_FUSED_DZ = 1, TXE_FUSED_DW = 2, TXE_FUSED_SWEEP = 4, TXE_FUSED_REDUCE = 8, TXE_FUSED_ALL = 15, TXE_FUSED_DW_BESIDE = 128,
+       TXE_FUSED_DZ_GIVEN = 256, TXE_FUSED_EDOT = 512, TXE_FUSED_NO_EGO_WALK = 1024 };
+struct txe_gat_fold_below {    /* the GATLayer below the folded one */
+    const float* Yp; long long ld_yp; int Hp, Dp; float attn_slope_p, attn_drop_p_p; unsigned long long seed_p; const float* alpha_p;
+    float* d_Yp; long long ld_dyp; int n_pad; float* dz_p;
+};
+int txe_gat_collapse_bwd_fused(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const struct txe_gat_fold_below* below,
+                               const struct txe_fold_match* match /* NULL without TXE_FUSED_EDOT */, const struct txe_gat_fold_grads* grads,
+                               const float* d_hg, long long ld_dhg, float act_slope, int phases, const float* dw_main, int dw_slices,
+                               const int* walk_plan, void* chain, void* ws, size_t ws_bytes, void* stream);
 /* walk_plan (optional, NULL = none): the batch's plan from txe_egonet_walk_plan -- what the egonet-walking sweep otherwise works out from
  * the CSR arrays in every workgroup of every step (hub, roles, CSR positions, list order of each graph) done once per batch of graphs:
  * the sweep's staging is then two dependent trips instead of eight.  Same results bit for bit.  plan: txe_egonet_walk_plan_bytes(n_nodes)
@@ -466,14 +477,14 @@ int txe_egonet_walk_plan(const int* rowptr_in, const int* col_src, const int* ro
  * hg[g] = (sum_{u in g} c_u Xd[u]) W + b with c_u = norm_u sum_{v: u->v} w_v norm_v / S_g (graph constants).  X / Wp / mask as for
  * txe_gcn_dense_*; norm from txe_gcn_norm; forward keeps coef [N], wsum [G], gid [N], Z [G][Kp]. */
 size_t txe_gcn_collapse_ws_bytes(int n_nodes, int G, int Kh, int Pd, int Fo, int vocab);
-int txe_gcn_collapse_fwd(const int* rowptr_out, const int* col_dst, const int* graph_off, int n_nodes, int G, const float* X, int Kh, int Pd,
-                         const float* Wp, int Fo, const float* bias, float drop_p, const unsigned* mask, const float* norm, const int* pos,
-                         const float* pw, float* coef, float* wsum, int* gid, float* Z, float* hg, long long ld_hg, void* ws,
-                         size_t ws_bytes, void* stream);
-int txe_gcn_collapse_bwd(const int* rowptr_in, const int* col_src, const int* graph_off, int n_nodes, int G, const float* X, int Kh, int Pd,
-                         const int* pos, int vocab, const float* Wp, int Fo, float drop_p, const unsigned* mask, const float* norm,
-                         const float* pw, const float* coef, const float* wsum, const int* gid, const float* Z, const float* d_hg,
-                         long long ld_dhg, int act_on, float act_slope, float* d_X, float* dW, float* d_b, float* dP, float* d_pw,
+struct txe_gcn_fold_layer {    /* the folded GCN layer (the batch is a txe_graph_batch; pos_out and n_edges are not read) */
+    const float* X; int Kh, Pd; const int* pos; int vocab /* backward only */; const float* Wp; int Fo; const float* bias; float drop_p;
+    const unsigned* mask; const float *norm, *pw; float *coef, *wsum; int* gid; float *Z, *hg; long long ld_hg;   /* hg NULL: forward stops at Z */
+};
+struct txe_gcn_fold_grads { float *dW, *d_b, *dP, *d_pw; };
+int txe_gcn_collapse_fwd(const struct txe_graph_batch* batch, const struct txe_gcn_fold_layer* layer, void* ws, size_t ws_bytes, void* stream);
+int txe_gcn_collapse_bwd(const struct txe_graph_batch* batch, const struct txe_gcn_fold_layer* layer, const float* d_hg, long long ld_dhg,
+                         int act_on, float act_slope, float* d_X, const struct txe_gcn_fold_grads* grads,
                          int dz_given /* d_hg IS dZ [G][Kp]: no product, dW / d_b not written (txe_bilinear_folded_*, wf_by_k) */, void* ws,
                          size_t ws_bytes, void* stream);
 

@@ -6,6 +6,11 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libtxe.so")
 TAIL_CHAIN_BYTES = 1024        # TXE_TAIL_CHAIN_BYTES of include/txe.h
+# the `phases` bits of txe_gat_dense_bwd / txe_gat_collapse_bwd_fused and the `flags` of txe_gat_collapse_fwd (the header's TXE_* enums)
+DENSE_DX, DENSE_DW, DENSE_REDUCE, DENSE_ALL, DENSE_DX_SPLIT, PH_DEFER = 1, 2, 4, 7, 16, 64
+FUSED_DZ, FUSED_DW, FUSED_SWEEP, FUSED_REDUCE, FUSED_ALL = 1, 2, 4, 8, 15
+FUSED_DW_BESIDE, FUSED_DZ_GIVEN, FUSED_EDOT, FUSED_NO_EGO_WALK = 128, 256, 512, 1024
+FOLD_A12_READY, FOLD_HG_SPLIT = 1, 2
 
 P, I, L, F, D, U64, SZ = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_size_t
 
@@ -96,22 +101,20 @@ SIGNATURES = {
     "txe_build_csr": (I, [P, P, I, I, P, P, P, P, P, P, P, SZ, P]),
     "txe_rank_block": (I, [P, L, I, I, P, P, P, I, P, P]),
     "txe_gat_collapse_ws_bytes": (SZ, [I, I, I, I, I, I, I]),
-    "txe_gat_collapse_fwd": (I, [P, P, P, P, P, P, I, I, I, P, I, I, P, I, F, P, F, F, U64, P, P, P, I, P, P, P, P, P, P, L, P, P, P, P, SZ, P]),
+    "txe_gat_collapse_fwd": (I, [P, P, P, I, P, SZ, P]),
     "txe_gat_collapse_e_tiles": (I, [I, I, I, I]),
     "txe_gat_collapse_fold_scores": (I, [P, I, I, I, I, P, P, P, F, I, I, P, P]),
-    "txe_gat_collapse_bwd": (I, [P, P, P, P, P, P, I, I, I, P, I, I, P, I, P, P, P, P, I, F, P, F, F, U64, P, P, P, P, P, P, P, P, L, P, L, I, F,
-                                 P, P, P, P, P, P, P, SZ, P]),
+    "txe_gat_collapse_bwd": (I, [P, P, P, L, I, F, P, P, P, SZ, P]),
     "txe_gat_layers_prepare": (I, [P, I, P]),
     "txe_gat_fused_bwd_supported": (I, [I, I, I, I]),
     "txe_gat_collapse_bwd_fused_ws_bytes": (SZ, [I, I, I, I, I, I, I, I]),
-    "txe_gat_collapse_bwd_fused": (I, [P, P, P, P, P, P, I, I, I, P, I, I, P, I, P, P, P, P, I, F, P, F, F, U64, P, P, P, P, P, P, P, P, L, P, L,
-                                       F, P, L, I, I, F, F, U64, P, P, L, I, P, P, P, P, P, P, I, P, I, P, P, P, I, P, P, P, P, P, P, SZ, P]),
+    "txe_gat_collapse_bwd_fused": (I, [P, P, P, P, P, P, L, F, I, P, I, P, P, P, SZ, P]),
     "txe_gat_dense_fwd_split_src": (I, [P, L, P, P, P, F, I, I, I, P, I, I, P, P, P, SZ, P]),
     "txe_egonet_walk_plan_bytes": (SZ, [I]),
     "txe_egonet_walk_plan": (I, [P, P, P, P, P, P, I, I, P, P]),
     "txe_gcn_collapse_ws_bytes": (SZ, [I, I, I, I, I, I]),
-    "txe_gcn_collapse_fwd": (I, [P, P, P, I, I, P, I, I, P, I, P, F, P, P, P, P, P, P, P, P, P, L, P, SZ, P]),
-    "txe_gcn_collapse_bwd": (I, [P, P, P, I, I, P, I, I, P, I, P, I, F, P, P, P, P, P, P, P, P, L, I, F, P, P, P, P, P, I, P, SZ, P]),
+    "txe_gcn_collapse_fwd": (I, [P, P, P, SZ, P]),
+    "txe_gcn_collapse_bwd": (I, [P, P, P, L, I, F, P, P, I, P, SZ, P]),
     "txe_egonet_ws_bytes": (SZ, [I]),
     "txe_egonet_offsets": (I, [P, P, P, P, P, I, I, U64, I, P, P, SZ, P]),
     "txe_egonet_fill": (I, [P, P, P, P, P, P, I, I, U64, I, P, P, P, P, P, P, P, P, P, P]),
@@ -152,6 +155,51 @@ class GcnPrepareDesc(C.Structure):
     """struct txe_gcn_prepare_desc (include/txe.h)"""
     _fields_ = [("h", P), ("ld_h", L), ("n_nodes", I), ("Kh", I), ("pos", P), ("P", P), ("Pd", I), ("X", P), ("W", P), ("Fo", I), ("Wp", P),
                 ("drop_p", F), ("seed", U64), ("mask", P), ("x_dropped", I), ("bias_row", P)]
+
+
+class GraphBatch(C.Structure):
+    """struct txe_graph_batch"""
+    _fields_ = [("rowptr_in", P), ("col_src", P), ("rowptr_out", P), ("col_dst", P), ("pos_out", P), ("graph_off", P), ("n_nodes", I),
+                ("n_edges", I), ("G", I)]
+
+
+class GatFoldLayer(C.Structure):
+    """struct txe_gat_fold_layer"""
+    _fields_ = [("X", P), ("Kh", I), ("Pd", I), ("pos", P), ("vocab", I), ("Wp", P), ("W", P), ("attn_l", P), ("attn_r", P), ("D", I),
+                ("feat_drop_p", F), ("mask", P), ("attn_slope", F), ("attn_drop_p", F), ("seed", U64), ("pw", P), ("a12", P), ("alpha", P),
+                ("coef", P), ("wsum", P), ("gid", P), ("Z", P), ("hg", P), ("ld_hg", L)]
+
+
+class FoldMatch(C.Structure):
+    """struct txe_fold_match"""
+    _fields_ = [("e_part", P), ("m_ds", P), ("m_s", P), ("m_exp", I), ("Tf", P), ("zrow", P), ("zgid", P)]
+
+
+class GatFoldGrads(C.Structure):
+    """struct txe_gat_fold_grads"""
+    _fields_ = [("dW", P), ("d_attn_l", P), ("d_attn_r", P), ("dP", P), ("d_pw", P)]
+
+
+class GatFoldBelow(C.Structure):
+    """struct txe_gat_fold_below"""
+    _fields_ = [("Yp", P), ("ld_yp", L), ("Hp", I), ("Dp", I), ("attn_slope_p", F), ("attn_drop_p_p", F), ("seed_p", U64), ("alpha_p", P),
+                ("d_Yp", P), ("ld_dyp", L), ("n_pad", I), ("dz_p", P)]
+
+
+class GcnFoldLayer(C.Structure):
+    """struct txe_gcn_fold_layer"""
+    _fields_ = [("X", P), ("Kh", I), ("Pd", I), ("pos", P), ("vocab", I), ("Wp", P), ("Fo", I), ("bias", P), ("drop_p", F), ("mask", P),
+                ("norm", P), ("pw", P), ("coef", P), ("wsum", P), ("gid", P), ("Z", P), ("hg", P), ("ld_hg", L)]
+
+
+class GcnFoldGrads(C.Structure):
+    """struct txe_gcn_fold_grads"""
+    _fields_ = [("dW", P), ("d_b", P), ("dP", P), ("d_pw", P)]
+
+
+def ref(desc):
+    """a descriptor struct (or None) as a pointer argument; the caller keeps the struct, and what it points to, alive over the call"""
+    return None if desc is None else C.addressof(desc)
 
 
 _ERR = {-1: "TXE_ERR_ARG", -2: "TXE_ERR_LAUNCH", -3: "TXE_ERR_WORKSPACE"}

@@ -4,11 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define TXE_OK 0
-#define TXE_ERR_ARG -1
-#define TXE_ERR_LAUNCH -2
-#define TXE_ERR_WORKSPACE -3
-#define TXE_TAIL_CHAIN_BYTES 1024     /* include/txe.h */
+#include "../../include/txe.h"     // the C ABI: error codes, descriptor structs, phase bits; every definition is checked against its prototype
 
 #define TXE_WAVE 64
 #define TXE_NUM_XCD 8

@@ -29,5 +29,3 @@ void cl_attn_bwd_launch(bool fold, const int* rowptr_in, const int* col_src, con
                         hipStream_t s);
 
 }  // namespace txe
-
-extern "C" int txe_gat_collapse_e_tiles(int n_nodes, int G, int Kh, int Pd);      // txe_fold.hip (include/txe.h)

@@ -879,12 +879,21 @@ int txe_gat_collapse_fold_scores(const int* graph_off, int n_nodes, int G, int K
     return TXE_OK;
 }
 
-int txe_gat_collapse_fwd(const int* rowptr_in, const int* col_src, const int* rowptr_out, const int* col_dst, const int* pos_out,
-                         const int* graph_off, int n_nodes, int n_edges, int G, const float* X, int Kh, int Pd, const float* Wp, int D,
-                         float feat_drop_p, const unsigned* mask, float attn_slope, float attn_drop_p, unsigned long long seed,
-                         const int* pos, const float* pw, float* a12, int a12_ready, float* alpha, float* coef, float* wsum, int* gid,
-                         float* Z, float* hg, long long ld_hg, const float* Tf, const int* zrow, float* e_part, void* ws, size_t ws_bytes,
-                         void* stream) {
+int txe_gat_collapse_fwd(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const struct txe_fold_match* match,
+                         int flags, void* ws, size_t ws_bytes, void* stream) {
+    if (!batch || !layer) return TXE_ERR_ARG;
+    const int *rowptr_in = batch->rowptr_in, *col_src = batch->col_src, *rowptr_out = batch->rowptr_out, *col_dst = batch->col_dst,
+              *pos_out = batch->pos_out, *graph_off = batch->graph_off, *pos = layer->pos;
+    const int n_nodes = batch->n_nodes, n_edges = batch->n_edges, G = batch->G, Kh = layer->Kh, Pd = layer->Pd, D = layer->D;
+    const float *X = layer->X, *Wp = layer->Wp, *pw = layer->pw, *Tf = match ? match->Tf : nullptr;
+    const unsigned* mask = layer->mask;
+    const float feat_drop_p = layer->feat_drop_p, attn_slope = layer->attn_slope, attn_drop_p = layer->attn_drop_p;
+    const unsigned long long seed = layer->seed;
+    float *a12 = layer->a12, *alpha = layer->alpha, *coef = layer->coef, *wsum = layer->wsum, *Z = layer->Z, *hg = layer->hg,
+          *e_part = match ? match->e_part : nullptr;
+    int* gid = layer->gid;
+    const int* zrow = match ? match->zrow : nullptr;
+    const long long ld_hg = layer->ld_hg;
     if (n_nodes < 0 || n_edges < 0 || G < 0 || Kh < 1 || Pd < 0 || D < 1 || !rowptr_in || !rowptr_out || !graph_off || !X || !Wp || !a12 ||
         !alpha || !coef || !wsum || !gid || !Z || !ws || (pw && !pos))
         return TXE_ERR_ARG;
@@ -901,7 +910,7 @@ int txe_gat_collapse_fwd(const int* rowptr_in, const int* col_src, const int* ro
     const unsigned* dummy_mask = reinterpret_cast<const unsigned*>(X);     // never dereferenced by the <false> instantiations
     if (n_nodes > 0) {
         const int nb = (n_nodes + 3) / 4;
-        if (!(a12_ready & 1)) {    // (the producer of X may already have formed them: txe_gat_aggregate_fwd's fused epilogue)
+        if (!(flags & TXE_FOLD_A12_READY)) {    // (the producer of X may already have formed them: txe_gat_aggregate_fwd's fused epilogue)
             ProfScope prof(mk ? "cl_logits_kernel<true>" : "cl_logits_kernel<false>", s, 4.0 * n_nodes * (double)Kp, 1);
             if (mk) hipLaunchKernelGGL(cl_logits_kernel<true>, dim3(nb < 2048 ? nb : 2048), dim3(256), 0, s, X, Kp, n_nodes, mk, mask_ld, fs, wa, a12);
             else hipLaunchKernelGGL(cl_logits_kernel<false>, dim3(nb < 2048 ? nb : 2048), dim3(256), 0, s, X, Kp, n_nodes, dummy_mask, mask_ld, fs, wa, a12);
@@ -918,7 +927,7 @@ int txe_gat_collapse_fwd(const int* rowptr_in, const int* col_src, const int* ro
                                     e_part);
     if (rc_z) return rc_z;
     if (!hg) return TXE_OK;          // (the caller folds hg = Z W^T into what consumes it: txe_bilinear_folded_*)
-    if (G > 0 && (a12_ready & 2)) {
+    if (G > 0 && (flags & TXE_FOLD_HG_SPLIT)) {
         if (ws_bytes < p.total + collapse_split_bytes(G, D, Kt)) return TXE_ERR_WORKSPACE;            // (the route is the caller's choice, not the buffer's size)
         // hg = Z W^T on the bf16 matrix pipe (txe_gemm_split.h): Z and the weight rows packed behind the workspace's own regions
         char* sw = (char*)ws + p.total;
@@ -939,13 +948,19 @@ int txe_gat_collapse_fwd(const int* rowptr_in, const int* col_src, const int* ro
 
 // d_hg [G][D] -> d_X [N][Kp] (first Kh columns through leaky' of X when act_on: they are d(pre-activation) of the previous
 // layer), dW [D][Kt], d_attn_l / d_attn_r [D], dP [vocab][Pd] (Pd > 0), d_pw [vocab] (pw != NULL).
-int txe_gat_collapse_bwd(const int* rowptr_in, const int* col_src, const int* rowptr_out, const int* col_dst, const int* pos_out,
-                         const int* graph_off, int n_nodes, int n_edges, int G, const float* X, int Kh, int Pd, const int* pos, int vocab,
-                         const float* Wp, const float* W, const float* attn_l, const float* attn_r, int D, float feat_drop_p,
-                         const unsigned* mask, float attn_slope, float attn_drop_p, unsigned long long seed, const float* pw,
-                         const float* a12, const float* alpha, const float* coef, const float* wsum, const int* gid, const float* Z,
-                         const float* hg, long long ld_hg, const float* d_hg, long long ld_dhg, int act_on, float act_slope, float* d_X, float* dW, float* d_attn_l,
-                         float* d_attn_r, float* dP, float* d_pw, void* ws, size_t ws_bytes, void* stream) {
+int txe_gat_collapse_bwd(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const float* d_hg, long long ld_dhg,
+                         int act_on, float act_slope, float* d_X, const struct txe_gat_fold_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+    if (!batch || !layer || !grads) return TXE_ERR_ARG;
+    const int *rowptr_in = batch->rowptr_in, *col_src = batch->col_src, *rowptr_out = batch->rowptr_out, *pos_out = batch->pos_out,
+              *graph_off = batch->graph_off, *pos = layer->pos, *gid = layer->gid;
+    const int n_nodes = batch->n_nodes, n_edges = batch->n_edges, G = batch->G, Kh = layer->Kh, Pd = layer->Pd, D = layer->D, vocab = layer->vocab;
+    const float *X = layer->X, *Wp = layer->Wp, *W = layer->W, *attn_l = layer->attn_l, *attn_r = layer->attn_r, *pw = layer->pw, *a12 = layer->a12,
+                *alpha = layer->alpha, *coef = layer->coef, *wsum = layer->wsum, *Z = layer->Z, *hg = layer->hg;
+    const unsigned* mask = layer->mask;
+    const float feat_drop_p = layer->feat_drop_p, attn_slope = layer->attn_slope, attn_drop_p = layer->attn_drop_p;
+    const unsigned long long seed = layer->seed;
+    const long long ld_hg = layer->ld_hg;
+    float *dW = grads->dW, *d_attn_l = grads->d_attn_l, *d_attn_r = grads->d_attn_r, *dP = grads->dP, *d_pw = grads->d_pw;
     if (n_nodes < 0 || n_edges < 0 || G < 0 || Kh < 1 || Pd < 0 || D < 1 || !rowptr_in || !rowptr_out || !graph_off || !X || !Wp || !W ||
         !attn_l || !attn_r || !a12 || !alpha || !coef || !wsum || !gid || !Z || !hg || !d_hg || !d_X || !dW || !d_attn_l || !d_attn_r || !ws)
         return TXE_ERR_ARG;
@@ -1124,10 +1139,16 @@ size_t txe_gcn_collapse_ws_bytes(int n_nodes, int G, int Kh, int Pd, int Fo, int
 
 // X [N][Kp], Wp [Kp128][Fop], mask as for txe_gcn_dense_*; norm [N] (txe_gcn_norm); bias [Fo] or NULL; pw == NULL: MeanReadout.
 // Saved for backward: coef [N], wsum [G], gid [N], Z [G][Kp].  hg [G][Fo] (row stride ld_hg).
-int txe_gcn_collapse_fwd(const int* rowptr_out, const int* col_dst, const int* graph_off, int n_nodes, int G, const float* X, int Kh, int Pd,
-                         const float* Wp, int Fo, const float* bias, float drop_p, const unsigned* mask, const float* norm, const int* pos,
-                         const float* pw, float* coef, float* wsum, int* gid, float* Z, float* hg, long long ld_hg, void* ws,
-                         size_t ws_bytes, void* stream) {
+int txe_gcn_collapse_fwd(const struct txe_graph_batch* batch, const struct txe_gcn_fold_layer* layer, void* ws, size_t ws_bytes, void* stream) {
+    if (!batch || !layer) return TXE_ERR_ARG;
+    const int *rowptr_out = batch->rowptr_out, *col_dst = batch->col_dst, *graph_off = batch->graph_off, *pos = layer->pos;
+    const int n_nodes = batch->n_nodes, G = batch->G, Kh = layer->Kh, Pd = layer->Pd, Fo = layer->Fo;
+    const float *X = layer->X, *Wp = layer->Wp, *bias = layer->bias, *norm = layer->norm, *pw = layer->pw;
+    const unsigned* mask = layer->mask;
+    const float drop_p = layer->drop_p;
+    float *coef = layer->coef, *wsum = layer->wsum, *Z = layer->Z, *hg = layer->hg;
+    int* gid = layer->gid;
+    const long long ld_hg = layer->ld_hg;
     if (n_nodes < 0 || G < 0 || Kh < 1 || Pd < 0 || Fo < 1 || !rowptr_out || !graph_off || !X || !Wp || !norm || !coef || !wsum || !gid || !Z ||
         !ws || (pw && !pos))
         return TXE_ERR_ARG;
@@ -1163,11 +1184,16 @@ int txe_gcn_collapse_fwd(const int* rowptr_out, const int* col_dst, const int* g
 }
 
 // d_hg [G][Fo] -> d_X [N][Kp] (layout of txe_gcn_dense_bwd), dW [Kt][Fo], d_b [Fo] (or NULL), dP, d_pw.
-int txe_gcn_collapse_bwd(const int* rowptr_in, const int* col_src, const int* graph_off, int n_nodes, int G, const float* X, int Kh, int Pd,
-                         const int* pos, int vocab, const float* Wp, int Fo, float drop_p, const unsigned* mask, const float* norm,
-                         const float* pw, const float* coef, const float* wsum, const int* gid, const float* Z, const float* d_hg,
-                         long long ld_dhg, int act_on, float act_slope, float* d_X, float* dW, float* d_b, float* dP, float* d_pw, int dz_given,
-                         void* ws, size_t ws_bytes, void* stream) {
+int txe_gcn_collapse_bwd(const struct txe_graph_batch* batch, const struct txe_gcn_fold_layer* layer, const float* d_hg, long long ld_dhg,
+                         int act_on, float act_slope, float* d_X, const struct txe_gcn_fold_grads* grads, int dz_given, void* ws, size_t ws_bytes,
+                         void* stream) {
+    if (!batch || !layer || !grads) return TXE_ERR_ARG;
+    const int *rowptr_in = batch->rowptr_in, *col_src = batch->col_src, *graph_off = batch->graph_off, *pos = layer->pos, *gid = layer->gid;
+    const int n_nodes = batch->n_nodes, G = batch->G, Kh = layer->Kh, Pd = layer->Pd, Fo = layer->Fo, vocab = layer->vocab;
+    const float *X = layer->X, *Wp = layer->Wp, *norm = layer->norm, *pw = layer->pw, *coef = layer->coef, *wsum = layer->wsum, *Z = layer->Z;
+    const unsigned* mask = layer->mask;
+    const float drop_p = layer->drop_p;
+    float *dW = grads->dW, *d_b = grads->d_b, *dP = grads->dP, *d_pw = grads->d_pw;
     // dz_given: `d_hg` IS dZ [G][Kp] (ld_dhg == Kp) -- whoever consumed Z folded hg = Z W + b into its own products (txe_bilinear_folded_*,
     // wf_by_k) and formed dW / d_b itself: no product here, dW / d_b are not written
     if (n_nodes < 0 || G < 0 || Kh < 1 || Pd < 0 || Fo < 1 || !rowptr_in || !graph_off || !X || !Wp || !norm || !coef || !wsum || !gid || !Z ||

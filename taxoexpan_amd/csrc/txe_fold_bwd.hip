@@ -913,7 +913,7 @@ __global__ __launch_bounds__(256) void gat_attn_bwd_reduce_a_kernel(const AttnBw
     reduce_a_job(bid - nb_attn, a);
 }
 
-// phases | 128 of the folded layer's backward entries: the weight-gradient product runs on a second stream BESIDE the caller's dZ product
+// phases | TXE_FUSED_DW_BESIDE of the folded layer's backward entries: the weight-gradient product runs on a second stream BESIDE the caller's dZ product
 // and sweeps (every call of one backward pass carries the bit: the workspace layout depends on it).  Few fat k-slices then -- 2 instead
 // of the 7 that fill the machine: ~140 workgroups leave the kernels on the caller's stream their wave slots (cl_bwd_dot 73 -> 61 us,
 // step -11 us on the 4,096-egonet batch) and the product still ends under the fused sweep (one slice: it does not -- sweep 139 -> 204 us)
@@ -974,29 +974,40 @@ size_t txe_gat_collapse_bwd_fused_ws_bytes(int n_nodes, int n_edges, int G, int 
 // that layer's projection output Yp [N][ld_yp] = [ft | a1 | a2] (Hp heads of Dp columns, Hp*Dp == Kh), its attention alpha_p [E][Hp]
 // (destination-CSR order), attention slope / dropout / seed.  Instead of d_X it returns that layer's d_Yp [N][ld_dyp] =
 // [d_ft | d_a1 | d_a2 | n_pad zero columns] directly; dz_p [E][Hp] is scratch.  act_slope: slope of the activation between the two
-// layers (1 = none).  dP / d_pw / dW / d_attn as txe_gat_collapse_bwd.  phases: 15 = everything; or, for a caller that overlaps the
-// independent weight-gradient GEMM with the sweeps on a second stream, separate calls with 1 (dZ GEMM), 2 (dW GEMM partials: needs
-// only d_hg and Z), 4 (sweeps + first reduction stage: needs 1), 8 (final reductions: needs 2 and 4) and the same workspace.
-// phases | 1024: the source-side sweep does not walk egonets from registers (gat_fused_bwd_kernel for every head count: the A/B switch).
-int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const int* rowptr_out, const int* col_dst, const int* pos_out,
-                               const int* graph_off, int n_nodes, int n_edges, int G, const float* X, int Kh, int Pd, const int* pos,
-                               int vocab, const float* Wp, const float* W, const float* attn_l, const float* attn_r, int D,
-                               float feat_drop_p, const unsigned* mask, float attn_slope, float attn_drop_p, unsigned long long seed,
-                               const float* pw, const float* a12, const float* alpha, const float* coef, const float* wsum,
-                               const int* gid, const float* Z, const float* hg, long long ld_hg, const float* d_hg, long long ld_dhg,
-                               float act_slope, const float* Yp, long long ld_yp, int Hp, int Dp, float attn_slope_p,
-                               float attn_drop_p_p, unsigned long long seed_p, const float* alpha_p, float* d_Yp, long long ld_dyp,
-                               int n_pad, float* dz_p, float* dW, float* d_attn_l, float* d_attn_r, float* dP, float* d_pw, int phases,
-                               const float* dw_main, int dw_slices, const float* e_part, const float* m_ds, const float* m_s, int m_exp,
-                               const float* Tf, const int* zrow, int* zgid, const int* walk_plan, void* chain, void* ws, size_t ws_bytes,
-                               void* stream) {
-    // phases | 512 (with | 256): the <dZ, X> sweep was done in forward (txe_gat_collapse_fwd's e_part); m_ds / m_s [G]: the folded matcher's
+// layers (1 = none).  dP / d_pw / dW / d_attn as txe_gat_collapse_bwd.  phases: TXE_FUSED_ALL = everything; or, for a caller that overlaps the
+// independent weight-gradient GEMM with the sweeps on a second stream, separate calls with _DZ (dZ GEMM), _DW (dW GEMM partials: needs
+// only d_hg and Z), _SWEEP (sweeps + first reduction stage: needs DZ), _REDUCE (final reductions: needs DW and SWEEP) and the same workspace.
+// phases | TXE_FUSED_NO_EGO_WALK: the source-side sweep does not walk egonets from registers (gat_fused_bwd_kernel for every head count: the A/B switch).
+int txe_gat_collapse_bwd_fused(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const struct txe_gat_fold_below* below,
+                               const struct txe_fold_match* match, const struct txe_gat_fold_grads* grads, const float* d_hg, long long ld_dhg,
+                               float act_slope, int phases, const float* dw_main, int dw_slices, const int* walk_plan, void* chain, void* ws,
+                               size_t ws_bytes, void* stream) {
+    if (!batch || !layer || !below || !grads) return TXE_ERR_ARG;
+    const int *rowptr_in = batch->rowptr_in, *col_src = batch->col_src, *rowptr_out = batch->rowptr_out, *col_dst = batch->col_dst,
+              *pos_out = batch->pos_out, *graph_off = batch->graph_off, *pos = layer->pos, *gid = layer->gid;
+    const int n_nodes = batch->n_nodes, n_edges = batch->n_edges, G = batch->G, Kh = layer->Kh, Pd = layer->Pd, D = layer->D, vocab = layer->vocab;
+    const float *X = layer->X, *Wp = layer->Wp, *W = layer->W, *attn_l = layer->attn_l, *attn_r = layer->attn_r, *pw = layer->pw, *a12 = layer->a12,
+                *alpha = layer->alpha, *coef = layer->coef, *wsum = layer->wsum, *Z = layer->Z, *hg = layer->hg;
+    const unsigned* mask = layer->mask;
+    const float feat_drop_p = layer->feat_drop_p, attn_slope = layer->attn_slope, attn_drop_p = layer->attn_drop_p;
+    const unsigned long long seed = layer->seed, seed_p = below->seed_p;
+    const long long ld_hg = layer->ld_hg, ld_yp = below->ld_yp, ld_dyp = below->ld_dyp;
+    const float *Yp = below->Yp, *alpha_p = below->alpha_p;
+    const int Hp = below->Hp, Dp = below->Dp, n_pad = below->n_pad;
+    const float attn_slope_p = below->attn_slope_p, attn_drop_p_p = below->attn_drop_p_p;
+    float *d_Yp = below->d_Yp, *dz_p = below->dz_p;
+    float *dW = grads->dW, *d_attn_l = grads->d_attn_l, *d_attn_r = grads->d_attn_r, *dP = grads->dP, *d_pw = grads->d_pw;
+    const float *e_part = match ? match->e_part : nullptr, *m_ds = match ? match->m_ds : nullptr, *m_s = match ? match->m_s : nullptr,
+                *Tf = match ? match->Tf : nullptr;
+    const int m_exp = match ? match->m_exp : 0, *zrow = match ? match->zrow : nullptr;
+    int* zgid = match ? match->zgid : nullptr;
+    // phases | TXE_FUSED_EDOT (with | TXE_FUSED_DZ_GIVEN): the <dZ, X> sweep was done in forward (txe_gat_collapse_fwd's e_part); m_ds / m_s [G]: the folded matcher's
     // score gradient and scores, m_exp: it exponentiates -- see cl_fold_dc_kernel
-    // phases | 256: `d_hg` IS dZ [G][Kp] (ld_dhg its row pitch) -- whoever consumed Z folded hg = Z W^T into its own product
+    // phases | TXE_FUSED_DZ_GIVEN: `d_hg` IS dZ [G][Kp] (ld_dhg its row pitch) -- whoever consumed Z folded hg = Z W^T into its own product
     // (txe_bilinear_folded_*) and hands back dZ and the main part of dW as dw_slices slices [D][Kp] at dw_main (summed in order; 0: none)
-    const bool dz_given = (phases & 256) != 0;
+    const bool dz_given = (phases & TXE_FUSED_DZ_GIVEN) != 0;
     if (n_nodes < 0 || n_edges < 0 || G < 0 || Kh < 1 || Pd < 0 || D < 1 || !rowptr_in || !rowptr_out || !graph_off || !X || !Wp || !W ||
-        !attn_l || !attn_r || !a12 || !alpha || !coef || !wsum || !gid || !Z || (!hg && !dz_given) || (!d_hg && !(phases & 512)) || !dW || !d_attn_l || !d_attn_r ||
+        !attn_l || !attn_r || !a12 || !alpha || !coef || !wsum || !gid || !Z || (!hg && !dz_given) || (!d_hg && !(phases & TXE_FUSED_EDOT)) || !dW || !d_attn_l || !d_attn_r ||
         !ws || !Yp || !alpha_p || !d_Yp || !dz_p || n_pad < 0 || dw_slices < 0 || (dw_slices > 0 && !dw_main))
         return TXE_ERR_ARG;
     if (!txe_gat_fused_bwd_supported(Kh, Pd, Hp, Dp)) return TXE_ERR_ARG;
@@ -1005,7 +1016,7 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
     if (feat_drop_p < 0.f || feat_drop_p >= 1.f || attn_drop_p < 0.f || attn_drop_p >= 1.f || attn_drop_p_p < 0.f || attn_drop_p_p >= 1.f)
         return TXE_ERR_ARG;
     const int Kt = Kh + Pd, Kp = round_up(Kt, 32), F = Hp * Dp;
-    FusedWs fw = plan_fused_ws(ws, n_nodes, n_edges, G, Kh, Kp, D, Pd, vocab, Hp, (phases & 128) ? DW_BESIDE_SPLITS : 0);
+    FusedWs fw = plan_fused_ws(ws, n_nodes, n_edges, G, Kh, Kp, D, Pd, vocab, Hp, (phases & TXE_FUSED_DW_BESIDE) ? DW_BESIDE_SPLITS : 0);
     CollapseWs& p = fw.c;
     if (ws_bytes < fw.total) return TXE_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -1015,11 +1026,11 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
     const float* wa = Wp + (long long)D * Kp;
     const unsigned* dummy_mask = reinterpret_cast<const unsigned*>(X);
     int rc;
-    if (dz_given) phases &= ~3;
+    if (dz_given) phases &= ~(TXE_FUSED_DZ | TXE_FUSED_DW);
     const float* const dZv = dz_given ? d_hg : (const float*)p.dZ;
     const long long ld_dz = dz_given ? ld_dhg : (long long)Kp;
     if (dz_given && ld_dz != Kp) return TXE_ERR_ARG;               // (the sweeps walk dZ rows with the padded pitch)
-    if (phases & 1) {   // dZ = d_hg W
+    if (phases & TXE_FUSED_DZ) {   // dZ = d_hg W
         VMat A = vmat_plain(d_hg, ld_dhg, G, D);
         VMat B = vmat_plain(Wp, Kp, D, Kp);
         Epi E = epi_plain(p.dZ, Kp, Kp);
@@ -1028,7 +1039,7 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
         if (rc) return rc;
     }
     const long long split_stride = (long long)D * Kp;
-    if (phases & 2) {   // dW (main part, split-K partial slices) = d_hg^T Z
+    if (phases & TXE_FUSED_DW) {   // dW (main part, split-K partial slices) = d_hg^T Z
         VMat A = vmat_plain(d_hg, ld_dhg, G, D);
         VMat B = vmat_plain(Z, Kp, G, Kp);
         Epi E = epi_plain(p.part, Kp, Kp);
@@ -1040,10 +1051,10 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
     const int S = dz_given ? dw_slices : (G > 0 ? p.splits : 0);
     const float* const partv = dz_given ? dw_main : (const float*)p.part;
     const int nblk = (G > 0 && n_nodes > 0) ? fw.nblocks : 0;
-    if ((phases & 4) && G > 0 && n_nodes > 0) {
+    if ((phases & TXE_FUSED_SWEEP) && G > 0 && n_nodes > 0) {
 
         FoldDcArgs fdc{};
-        if (phases & 512) {
+        if (phases & TXE_FUSED_EDOT) {
             if (!dz_given || !e_part || !m_ds || !m_s || !Tf || !zrow || !zgid) return TXE_ERR_ARG;
             const int nt_e = txe_gat_collapse_e_tiles(n_nodes, G, Kh, Pd);
             if (nt_e <= 0) return TXE_ERR_ARG;
@@ -1054,15 +1065,15 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
                                d_hg, ld_dhg, dz_given ? Z : hg, dz_given ? (long long)Kp : ld_hg, p.dS, 4.0 * ((n_nodes + (double)G) * Kp + 2.0 * G * D), s);
         if (rc) return rc;
         }
-        cl_attn_bwd_launch((phases & 512) != 0, rowptr_in, col_src, rowptr_out, pos_out, graph_off, G, a12, attn_slope, alpha, attn_drop_p, as, seed, pos,
+        cl_attn_bwd_launch((phases & TXE_FUSED_EDOT) != 0, rowptr_in, col_src, rowptr_out, pos_out, graph_off, G, a12, attn_slope, alpha, attn_drop_p, as, seed, pos,
                            pw, p.dc, p.dS, p.dz, p.da1, p.da2, p.dwv, fdc, s);
         {
             FusedBwdArgs a;
             memset(&a, 0, sizeof(a));
-            a.rowptr_out = rowptr_out; a.col_dst = col_dst; a.pos_out = pos_out; a.gid = (phases & 512) ? (const int*)zgid : gid; a.pos = pos ? pos : gid;
+            a.rowptr_out = rowptr_out; a.col_dst = col_dst; a.pos_out = pos_out; a.gid = (phases & TXE_FUSED_EDOT) ? (const int*)zgid : gid; a.pos = pos ? pos : gid;
             a.n_nodes = n_nodes;
             a.X = X; a.Kp = Kp; a.Kh = Kh; a.Pd = Pd; a.mask = mk ? mk : dummy_mask; a.mask_ld = mask_ld; a.fscale = fs;
-            a.dZ = (phases & 512) ? Tf : dZv; a.cn = p.cn; a.da1 = p.da1; a.da2 = p.da2; a.wa = wa; a.act_slope = act_slope; a.vocab = vocab > 0 ? vocab : 1;
+            a.dZ = (phases & TXE_FUSED_EDOT) ? Tf : dZv; a.cn = p.cn; a.da1 = p.da1; a.da2 = p.da2; a.wa = wa; a.act_slope = act_slope; a.vocab = vocab > 0 ? vocab : 1;
             a.Y = Yp; a.ld_y = ld_yp; a.H = Hp; a.D = Dp; a.alpha = alpha_p; a.drop_p = attn_drop_p_p;
             a.drop_scale = 1.f / (1.f - attn_drop_p_p); a.seed = seed_p;
             a.d_Y = d_Yp; a.ld_dy = ld_dyp; a.dal = fw.dal; a.dwa_part = fw.dwa_part; a.ppart = fw.ppart;
@@ -1072,7 +1083,7 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
             const int nvec = F / 16, ni = (nvec + 63) / 64, nwh = 4 / Hp;
             // algorithmic bytes: read X' (own row + once per out-edge is an L2 matter), dZ, Y; write d_Y
             char name[64];
-            const bool ego = Hp == 4 && !(phases & 1024);            // one head per wave: the egonet-walking variant (generic graphs inside)
+            const bool ego = Hp == 4 && !(phases & TXE_FUSED_NO_EGO_WALK);            // one head per wave: the egonet-walking variant (generic graphs inside)
             if (ego) snprintf(name, sizeof(name), "gat_fused_bwd_ego_kernel<%s, %d>", mk ? "true" : "false", ni);
             else snprintf(name, sizeof(name), "gat_fused_bwd_kernel<%s, %d, %d>", mk ? "true" : "false", ni, nwh);
             ProfScope prof(name, s, 4.0 * (n_nodes * ((double)Kp + 2.0 * F) + (double)G * Kp), 1);
@@ -1095,7 +1106,7 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
     // ---- the layer below's attention backward (edge level, from the sweep's raw d alpha) + phase A: d_wa = sum of the per-workgroup
     //      partials; readout position-weight partial sums -- one launch ----
     const int nseg = n_nodes > 0 ? p.seg_blocks : 0;
-    if (phases & 4) {
+    if (phases & TXE_FUSED_SWEEP) {
     TailA ta;
     memset(&ta, 0, sizeof(ta));
     ta.nb_s1a = 0;
@@ -1106,14 +1117,14 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
     AttnBwdArgs aa{rowptr_in, col_src, rowptr_out, pos_out, graph_off, G, Yp, ld_yp, Hp, F, attn_slope_p, alpha_p, (const float*)fw.dal, dz_p, d_Yp,
                    ld_dyp, n_pad};
     const int nb_attn = attn ? (G + FA_GRAPHS - 1) / FA_GRAPHS : 0;
-    const bool ego = Hp == 4 && !(phases & 1024) && attn;
+    const bool ego = Hp == 4 && !(phases & TXE_FUSED_NO_EGO_WALK) && attn;
     HubFixArgs hf{graph_off, gid, rowptr_out, col_dst, n_nodes, fw.npw, fw.nblocks, F, fw.hpart, d_Yp, ld_dyp};
     const int nb_fix = ego ? fw.nblocks - 1 : 0;
     ProfScope prof("gat_attn_bwd_reduce_a_kernel", s, attn ? 4.0 * (n_edges * (4.0 * Hp + 2.0) + n_nodes * (4.0 * Hp + n_pad)) : 0.0, 1);
     hipLaunchKernelGGL(gat_attn_bwd_reduce_a_kernel, dim3(nb_fix + nb_attn + ta.nb_s1b + ta.nb_r), dim3(256), 0, s, aa, nb_attn, ta, hf, nb_fix);
     TXE_CHECK_LAUNCH();
     }
-    if (!(phases & 8)) return TXE_OK;
+    if (!(phases & TXE_FUSED_REDUCE)) return TXE_OK;
     // ---- phase B: dW = main + attn (x) d_wa, d_attn = <d_wa, W> (unfold);  dP (from the fused sweep's partials), d_pw ----
     TailB tb;
     memset(&tb, 0, sizeof(tb));
@@ -1124,7 +1135,7 @@ int txe_gat_collapse_bwd_fused(const int* rowptr_in, const int* col_src, const i
     tb.s2a = Seg2Args{fw.ppart, nblk, vocab * Pd, dP};
     tb.nb_2b = pw ? (vocab + 63) / 64 : 0;
     tb.s2b = Seg2Args{p.ppart2, nseg, vocab, d_pw};
-    return tail_b_submit(&tb, chain, (phases & 64) != 0, s);
+    return tail_b_submit(&tb, chain, (phases & TXE_PH_DEFER) != 0, s);
 }
 
 }  // extern "C"

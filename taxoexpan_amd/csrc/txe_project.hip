@@ -144,7 +144,7 @@ __device__ __forceinline__ void tail_b_job(int b, const TailB& a) {
 __global__ __launch_bounds__(256) void gat_bwd_reduce_b_kernel(const TailB a) { tail_b_job(blockIdx.x, a); }
 
 // Phase B of SEVERAL layers in one launch.  A layer's phase B only finishes parameter gradients (nothing downstream in the backward
-// pass reads them), so a caller may DEFER it (phases | 64) into a host-side chain and let the last layer's call launch them all:
+// pass reads them), so a caller may DEFER it (phases | TXE_PH_DEFER) into a host-side chain and let the last layer's call launch them all:
 // one ~17 us dispatch per stack instead of one per layer.
 constexpr int TAIL_CHAIN_MAX = 3;                       // deferred layers a chain holds (a fourth deferral flushes)
 struct TailChain { int n; int pad; TailB tb[TAIL_CHAIN_MAX]; };
@@ -579,11 +579,6 @@ int txe_gat_layer_prepare(const float* h, long long ld_h, int n_nodes, int Kh, c
 // folded attention rows, keep mask, the position-embedding / padding columns of its input -- depends on the parameters and on `pos`
 // only, never on the layer below's output, so the whole stack can be prepared before the first GEMM (one dispatch instead of one per
 // layer; the feature columns of the deeper layers' inputs are written later by the aggregation below them).
-struct txe_gat_prepare_desc {
-    const float* h; long long ld_h; int n_nodes, Kh; const int* pos; const float* P; int Pd; float* X;
-    const float *W, *attn_l, *attn_r; int H, D; float* Wp; float feat_drop_p; unsigned long long seed; unsigned* mask;
-    int x_dropped;
-};
 }  // extern "C"
 namespace txe {
 constexpr int PREP_MAXL = 4;
@@ -655,10 +650,6 @@ int txe_gat_layers_prepare(const struct txe_gat_prepare_desc* descs, int n_layer
 
 // The same for a GCNLayer (model_zoo.py:35-37): txe_gat_build_x + txe_gcn_pack_weights + txe_dropout_mask in one launch.
 // W [Kh+Pd][Fo] -> Wp [roundup(roundup(Kh+Pd,32),128)][roundup(Fo,32)]; mask may be NULL when drop_p == 0.
-struct txe_gcn_prepare_desc {
-    const float* h; long long ld_h; int n_nodes, Kh; const int* pos; const float* P; int Pd; float* X;
-    const float* W; int Fo; float* Wp; float drop_p; unsigned long long seed; unsigned* mask; int x_dropped; const float* bias_row;
-};
 }  // extern "C"
 namespace txe {
 static int fill_prep_gcn(PrepArgs& a, const txe_gcn_prepare_desc& d) {
@@ -863,8 +854,8 @@ int txe_gat_dense_fwd_split_src(const float* h, long long ld_h, const int* pos, 
 //                columns < Kh are multiplied by leaky'(X) when act_slope_on (X[:, :Kh] is then the activated output of the
 //                previous layer), all by the dropout factor.
 //   dW [F][Kt], d_attn_l / d_attn_r [F], dP [vocab][Pd].
-// phases: 7 = everything; 1 = d_X, 2 = the dW GEMM (independent of each other), 4 = the reductions that need both -- separate calls
-// share the workspace.  phases | 16: the full d_X product (need_dh) runs on the bf16 matrix pipe, its packed operands behind the workspace
+// phases: TXE_DENSE_ALL = everything; _DX = d_X, _DW = the dW GEMM (independent of each other), _REDUCE = the reductions that need both -- separate calls
+// share the workspace.  phases | TXE_DENSE_DX_SPLIT: the full d_X product (need_dh) runs on the bf16 matrix pipe, its packed operands behind the workspace
 // (ws_bytes >= txe_gat_dense_ws_bytes + txe_gat_dense_bwd_split_ws_bytes, else TXE_ERR_WORKSPACE); without the bit: the fp32 MFMA.
 int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* pos, int vocab, const float* Wp, const float* W,
                       const float* attn_l, const float* attn_r, int H, int D, float feat_drop_p, const unsigned* mask, const float* d_Y,
@@ -898,10 +889,10 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
         rc = dxpos_prepare(da);
         if (rc) return rc;
     }
-    if ((phases & 1) && stream_dx) {
+    if ((phases & TXE_DENSE_DX) && stream_dx) {
         rc = dxpos_launch(da, s);
         if (rc) return rc;
-    } else if ((phases & 1) && (phases & 16) && need_dh && n_nodes > 0) {
+    } else if ((phases & TXE_DENSE_DX) && (phases & TXE_DENSE_DX_SPLIT) && need_dh && n_nodes > 0) {
         if (ws_bytes < p.total + dense_bwd_split_bytes(n_nodes, Fp, Kt)) return TXE_ERR_WORKSPACE;     // (the route is the caller's choice, not the buffer's size)
         // the whole d_X = d_Y Wp on the bf16 pipe (txe_gemm_split.h): d_Y packed as the row operand, Wp -- given as the transpose of
         // the column operand -- packed from its columns; dropout mask and leaky' factor in the store loop (epi_store_one's arithmetic)
@@ -919,7 +910,7 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
         if (act_on) { e.act_src = X; e.ld_act = Kp; e.act_slope = act_slope; e.cols_act = Kh; }
         rc = gemm_nt_split_launch(sw, sw + ba, n_nodes, Kt, Fc, d_X, Kp, 2.0 * n_nodes * (double)Kt * Fe, s, &e);
         if (rc) return rc;
-    } else if ((phases & 1) && Kt - c0 > 0 && n_nodes > 0 && (need_dh || Pd > 0)) {
+    } else if ((phases & TXE_DENSE_DX) && Kt - c0 > 0 && n_nodes > 0 && (need_dh || Pd > 0)) {
         VMat A = vmat_plain(d_Y, Fp, n_nodes, Fp);
         VMat B = vmat_plain(Wp + c0, Kp, Fp, Kp - c0);
         Epi E = epi_plain(d_X + c0, Kp, Kh > c0 ? Kh - c0 : 0);
@@ -938,17 +929,17 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
     E.split_stride = (long long)Fp * Kp;
     E.alg_flops = 2.0 * Fe * (double)Kt * n_nodes;
     const int splits = p.splits;
-    if ((phases & 2) && Xt && x_dropped + (feat_drop_p == 0.f) > 0 && split_tn_eligible(Fp, Kp) && split_tn_fits(n_nodes, Fp) && n_nodes > 0) {
+    if ((phases & TXE_DENSE_DW) && Xt && x_dropped + (feat_drop_p == 0.f) > 0 && split_tn_eligible(Fp, Kp) && split_tn_fits(n_nodes, Fp) && n_nodes > 0) {
         // the same slices on the bf16 pipe (txe_gemm_split.h): X packed contraction-major by the forward pass, d_Y split in the loader
         const int ks = round_up((n_nodes + splits - 1) / splits, 16);
         rc = gemm_tn_split_launch(d_Y, Fp, Fp, Xt, Kp, n_nodes, splits, ks, p.part, Kp, E.split_stride, E.alg_flops, s);
         if (rc) return rc;
-    } else if (phases & 2) {
+    } else if (phases & TXE_DENSE_DW) {
         if (!X) return TXE_ERR_ARG;
         rc = gemm_tn(A, B, E, Fp, Kp, n_nodes, splits, s);
         if (rc) return rc;
     }
-    if (!(phases & 4)) return TXE_OK;
+    if (!(phases & TXE_DENSE_REDUCE)) return TXE_OK;
     const int S = n_nodes > 0 ? splits : 0;
     // ---- phase A: dP partials (dP[c][j] = sum_{pos[m]==c} d_X[m][Kh+j]) and d_wa = the extension rows of dWp ----
     const int nseg = (Pd > 0 && n_nodes > 0) ? (stream_dx ? dxpos_blocks(n_nodes) : p.seg_blocks) : 0;
@@ -969,7 +960,7 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
                       d_attn_l, d_attn_r};
     tb.nb_2a = Pd > 0 ? (vocab * Pd + 63) / 64 : 0;
     tb.s2a = Seg2Args{p.ppart, nseg, vocab * Pd, dP};
-    return tail_b_submit(&tb, chain, (phases & 64) != 0, s);
+    return tail_b_submit(&tb, chain, (phases & TXE_PH_DEFER) != 0, s);
 }
 
 // launches whatever a chain of deferred phase-B jobs still holds (a stack whose last call deferred too); chain == NULL: nothing

@@ -354,7 +354,7 @@ class GatFolded(typing.NamedTuple):
 
 class _GatLayerState:
     __slots__ = ("X", "Wp", "mask", "Y", "alpha", "W", "al", "ar", "P", "pos", "Kh", "Pd", "Kp", "Fp", "H", "D", "seed", "cl", "prepared",
-                 "x_dropped", "Xt", "vx")
+                 "x_dropped", "Xt", "vx", "desc")
 
     def __init__(self):
         self.X = self.Wp = self.mask = self.Y = self.alpha = self.Xt = None
@@ -362,6 +362,7 @@ class _GatLayerState:
         self.pos = None             # the nodes' positions if the layer has a position table P, else None
         self.Kh = self.Pd = self.Kp = self.Fp = self.H = self.D = self.seed = 0
         self.cl = None              # GatFolded: the output layer folded behind the readout
+        self.desc = None            # ... and its (_lib.GraphBatch, _lib.GatFoldLayer): raw addresses of the batch's and this state's tensors
         self.prepared = self.x_dropped = False
         self.vx = False             # X is NOT stored (a first layer on the bf16 pipe: the packs form dropout([h | Emb[pos]]) themselves)
 
@@ -419,6 +420,12 @@ def _gat_layer_prepare(st, h, ld_h, feat_p):
          st.H, st.D, ptr(st.Wp), feat_p, st.seed, ptr(st.mask), s)
 
 
+def _graph_batch(csr, N):
+    """the batch of graphs as the folded layers' entry points take it (raw addresses: csr owns the arrays)"""
+    return _lib.GraphBatch(rowptr_in=ptr(csr.rowptr_in), col_src=ptr(csr.col_src), rowptr_out=ptr(csr.rowptr_out), col_dst=ptr(csr.col_dst),
+                           pos_out=ptr(csr.pos_out), graph_off=ptr(csr.graph_off), n_nodes=N, n_edges=csr.n_edges, G=csr.n_graphs)
+
+
 def _gat_collapse_fwd(csr, st, h, ld_h, rpos, pw, feat_p, attn_p, attn_slope, a12=None, z_only=False, fold_job=None, link=None):
     """output layer (one head) folded behind the weighted-mean readout: hg [G, D] (txe_gat_collapse_fwd).
     a12 given: the layer is already prepared and the previous layer's aggregation has formed its attention logits.
@@ -436,39 +443,49 @@ def _gat_collapse_fwd(csr, st, h, ld_h, rpos, pw, feat_p, attn_p, attn_slope, a1
     if split_hg:                                         # room for Z and the weight rows as packed planes: hg = Z W^T on the bf16 pipe
         wsb += pure("txe_gat_collapse_split_ws_bytes", G, st.Kh, st.Pd, st.D)
     ws = _ws(wsb, st.X)
-    Tf = zrow = e_part = None
+    match = None
     if z_only and fold_job is not None and link is not None and N > 0 and G > 0 and not _NO_FOLD_EDOT:
         nt = pure("txe_gat_collapse_e_tiles", N, G, st.Kh, st.Pd)
         job = fold_job(st.Wp, st.D) if nt > 0 else None      # the matcher's runs, V and T, formed now: T rides in the Z sweep
         if job is not None:
-            Tf, zrow, e_part = job.T, job.run_ids(G), _empty((N, nt), st.X)
-            link.fwd, link.e_part = job, e_part
+            zrow = job.run_ids(G)
+            link.fwd, link.e_part = job, _empty((N, nt), st.X)
+            match = _lib.FoldMatch(Tf=ptr(job.T), zrow=ptr(zrow), e_part=ptr(link.e_part))
             job.score = FoldScore(csr.graph_off, N, G, st.Kh, st.Pd, coef, wsum, feat_p, int(st.mask is not None and feat_p > 0.0))
-    call("txe_gat_collapse_fwd", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
-         ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(st.Wp), st.D, feat_p, ptr(st.mask), attn_slope, attn_p, st.seed + 1,
-         ptr(rpos), ptr(pw), ptr(a12), int(ready) | (2 if split_hg else 0), ptr(alpha), ptr(coef), ptr(wsum), ptr(gid), ptr(Z), ptr(hg), st.D, ptr(Tf), ptr(zrow),
-         ptr(e_part), ptr(ws), wsb, _lib.stream_ptr())
+    # the descriptors hold raw addresses: st.cl (and st, csr) own the tensors, and both go when the state does
     st.cl = GatFolded(a12, alpha, coef, wsum, gid, Z, hg)
+    batch = _graph_batch(csr, N)
+    layer = _lib.GatFoldLayer(X=ptr(st.X), Kh=st.Kh, Pd=st.Pd, pos=ptr(rpos), Wp=ptr(st.Wp), W=ptr(st.W), attn_l=ptr(st.al), attn_r=ptr(st.ar),
+                              D=st.D, feat_drop_p=feat_p, mask=ptr(st.mask), attn_slope=attn_slope, attn_drop_p=attn_p, seed=st.seed + 1,
+                              pw=ptr(pw), a12=ptr(a12), alpha=ptr(alpha), coef=ptr(coef), wsum=ptr(wsum), gid=ptr(gid), Z=ptr(Z), hg=ptr(hg),
+                              ld_hg=st.D)
+    st.desc = (batch, layer)
+    call("txe_gat_collapse_fwd", _lib.ref(batch), _lib.ref(layer), _lib.ref(match),
+         (_lib.FOLD_A12_READY if ready else 0) | (_lib.FOLD_HG_SPLIT if split_hg else 0), ptr(ws), wsb, _lib.stream_ptr())
     return Z if z_only else hg
 
 
-def _gat_collapse_bwd(csr, st, rpos, pw, vocab, feat_p, attn_p, attn_slope, d_hg, act_on, act_slope):
-    N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
-    a12, alpha, coef, wsum, gid, Z, hg = st.cl
-    d_hg, ld = _rows(d_hg)
+def _gat_fold_grads(st, layer, rpos, pw, vocab):
+    """the folded layer's parameter-gradient tensors and their descriptor; sets what backward adds to the layer's: the vocabulary, and the
+    positions as the position table's gradient reads them (forward had the readout's)"""
     dW, dal, dar = torch.empty_like(st.W), torch.empty_like(st.al), torch.empty_like(st.ar)
     dP = torch.empty_like(st.P) if st.P is not None else None
     d_pw = torch.empty_like(pw) if pw is not None else None
+    layer.pos, layer.vocab = ptr(st.pos if st.pos is not None else rpos), max(vocab, pw.numel() if pw is not None else 0)
+    return (dW, dal, dar, dP, d_pw), _lib.GatFoldGrads(dW=ptr(dW), d_attn_l=ptr(dal), d_attn_r=ptr(dar), dP=ptr(dP), d_pw=ptr(d_pw))
+
+
+def _gat_collapse_bwd(csr, st, rpos, pw, vocab, d_hg, act_on, act_slope):
+    N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
+    batch, layer = st.desc
+    d_hg, ld = _rows(d_hg)
+    out, grads = _gat_fold_grads(st, layer, rpos, pw, vocab)
     d_X = _empty((N, st.Kp), st.X)
-    v = max(vocab, pw.numel() if pw is not None else 0)
-    wsb = pure("txe_gat_collapse_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(v, 8))
+    wsb = pure("txe_gat_collapse_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(layer.vocab, 8))
     ws = _ws(wsb, st.X)
-    call("txe_gat_collapse_bwd", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
-         ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(st.pos if st.pos is not None else rpos), v, ptr(st.Wp), ptr(st.W),
-         ptr(st.al), ptr(st.ar), st.D, feat_p, ptr(st.mask), attn_slope, attn_p, st.seed + 1, ptr(pw), ptr(a12), ptr(alpha), ptr(coef),
-         ptr(wsum), ptr(gid), ptr(Z), ptr(hg), st.D, ptr(d_hg), ld, int(act_on), act_slope if act_slope else 1.0, ptr(d_X), ptr(dW), ptr(dal), ptr(dar), ptr(dP),
-         ptr(d_pw), ptr(ws), wsb, _lib.stream_ptr())
-    return d_X, dW, dal, dar, dP, d_pw
+    call("txe_gat_collapse_bwd", _lib.ref(batch), _lib.ref(layer), ptr(d_hg), ld, int(act_on), act_slope if act_slope else 1.0, ptr(d_X),
+         _lib.ref(grads), ptr(ws), wsb, _lib.stream_ptr())
+    return (d_X,) + out
 
 
 def _gat_layer_fwd(csr, st, h, ld_h, out, ld_out, feat_p, attn_p, attn_slope, out_mode, act_slope, save, nxt=None, out_drop=None):
@@ -565,7 +582,7 @@ def _gat_dense_bwd(st, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chain=Non
              ptr(st.mask), ptr(d_Y), int(need_dh), int(act_on), act_slope if act_slope else 1.0, ptr(d_X), ptr(dW), ptr(dal), ptr(dar),
              ptr(dP), int(st.x_dropped), ptr(st.Xt), phases, chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
     # (a first PGAT layer's d_X -- position columns only -- is one HBM stream over d_Y, txe_dxpos.hip; every other d_X is a GEMM)
-    run(7 | (16 if split_dx else 0) | (64 if (defer and chain is not None) else 0))
+    run(_lib.DENSE_ALL | (_lib.DENSE_DX_SPLIT if split_dx else 0) | (_lib.PH_DEFER if (defer and chain is not None) else 0))
     if chain is not None:
         chain.keep += [ws, d_Y, st]
     return d_X, dW, dal, dar, dP
@@ -626,13 +643,14 @@ class FoldLink:
         return self.e_part is not None and self.ds is not None
 
     def edot_args(self, zgid):
-        """the seven trailing edot arguments of txe_gat_collapse_bwd_fused (all absent unless dz_implicit)"""
+        """the matcher's share of txe_gat_collapse_bwd_fused, a _lib.FoldMatch (None unless dz_implicit); zgid: [N] int32 scratch"""
         if not self.dz_implicit:
-            return None, None, None, 0, None, None, None
-        return ptr(self.e_part), ptr(self.ds), ptr(self.s), int(self.apply_exp), ptr(self.fwd.T), ptr(self.fwd.run_id), ptr(zgid)
+            return None
+        return _lib.FoldMatch(e_part=ptr(self.e_part), m_ds=ptr(self.ds), m_s=ptr(self.s), m_exp=int(self.apply_exp), Tf=ptr(self.fwd.T),
+                              zrow=ptr(self.fwd.run_id), zgid=ptr(zgid))
 
 
-_NO_LINK = FoldLink()  # (read only) what _gat_collapse_bwd_fused reads when nobody consumed Z: no weight-gradient part, no edot arguments
+_NO_LINK = FoldLink()  # (read only) what _gat_collapse_bwd_fused reads when nobody consumed Z: no weight-gradient part, no matcher's share
 
 
 def walk_plan(csr):
@@ -653,11 +671,11 @@ def walk_plan(csr):
 _WALK_PLANS = {}       # id of a CSR's rowptr_in tensor -> (weak reference to it, the plan)
 
 
-def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, feat_p, attn_p, attn_slope, d_hg, act_slope, chain=None, link=None):
+def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, attn_p, attn_slope, d_hg, act_slope, chain=None, link=None):
     """txe_gat_collapse_bwd_fused: the folded layer's parameter gradients AND the layer below's d_Y in one sweep (no d_X).
     link given: d_hg IS dZ [G, Kp] (the consumer of Z folded hg = Z W^T into its own products, FoldLink)."""
     N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
-    a12, alpha, coef, wsum, gid, Z, hg = st.cl
+    batch, layer = st.desc
     lk = link or _NO_LINK
     edot = lk.dz_implicit                           # the <dZ, X> sweep was done in forward (FoldLink)
     if d_hg is None:
@@ -666,48 +684,46 @@ def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, feat_p, attn_p, attn_s
         ld = st.Kp                                  # (edot: 'dZ[g]' is the matcher's ds_g T[run(g)], read from the link -- no tensor)
     else:
         d_hg, ld = _rows(d_hg)
-    dW, dal, dar = torch.empty_like(st.W), torch.empty_like(st.al), torch.empty_like(st.ar)
-    dP = torch.empty_like(st.P) if st.P is not None else None
-    d_pw = torch.empty_like(pw) if pw is not None else None
-    Fe = sp.H * sp.D + 2 * sp.H
+    out, grads = _gat_fold_grads(st, layer, rpos, pw, vocab)
     d_Yp = _empty((N, sp.Fp), st.X)
     dz = _empty((max(E, 1) * sp.H,), st.X)
-    v = max(vocab, pw.numel() if pw is not None else 0)
-    wsb = pure("txe_gat_collapse_bwd_fused_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(v, 8), sp.H)
-    ws = _ws(wsb, st.X)
-    def run(phases):
-        call("txe_gat_collapse_bwd_fused", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
-             ptr(csr.graph_off), N, E, G, ptr(st.X), st.Kh, st.Pd, ptr(st.pos if st.pos is not None else rpos), v, ptr(st.Wp), ptr(st.W),
-             ptr(st.al), ptr(st.ar), st.D, feat_p, ptr(st.mask), attn_slope, attn_p, st.seed + 1, ptr(pw), ptr(a12), ptr(alpha), ptr(coef),
-             ptr(wsum), ptr(gid), ptr(Z), ptr(hg), st.D, ptr(d_hg), ld, act_slope if act_slope else 1.0, ptr(sp.Y), sp.Fp, sp.H, sp.D,
-             attn_slope, attn_p, sp.seed + 1, ptr(sp.alpha), ptr(d_Yp), sp.Fp, sp.Fp - Fe, ptr(dz), ptr(dW), ptr(dal), ptr(dar), ptr(dP),
-             ptr(d_pw), phases | (512 if edot else 0) | (1024 if _NO_EGO_WALK else 0), ptr(lk.part) if lk.S > 0 else None,
-             lk.S, *lk.edot_args(zgid), ptr(plan), chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
+    below = _lib.GatFoldBelow(Yp=ptr(sp.Y), ld_yp=sp.Fp, Hp=sp.H, Dp=sp.D, attn_slope_p=attn_slope, attn_drop_p_p=attn_p, seed_p=sp.seed + 1,
+                              alpha_p=ptr(sp.alpha), d_Yp=ptr(d_Yp), ld_dyp=sp.Fp, n_pad=sp.Fp - (sp.H * sp.D + 2 * sp.H), dz_p=ptr(dz))
     zgid = torch.empty(max(N, 1), dtype=torch.int32, device=st.X.device) if edot else None
+    match = lk.edot_args(zgid)
     plan = walk_plan(csr) if (sp.H == 4 and not _NO_EGO_WALK and not _NO_WALK_PLAN) else None
-    last = 8 | (64 if chain is not None else 0)     # (with a chain the final reductions are left to the bottom layer's launch)
+    wsb = pure("txe_gat_collapse_bwd_fused_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(layer.vocab, 8), sp.H)
+    ws = _ws(wsb, st.X)
+    # one set of descriptors for every call of this backward pass: the calls differ in `phases` alone
+    args = (_lib.ref(batch), _lib.ref(layer), _lib.ref(below), _lib.ref(match), _lib.ref(grads), ptr(d_hg), ld, act_slope if act_slope else 1.0)
+    rest = (ptr(lk.part) if lk.S > 0 else None, lk.S, ptr(plan), chain.ptr if chain is not None else None, ptr(ws), wsb)
+    always = (_lib.FUSED_EDOT if edot else 0) | (_lib.FUSED_NO_EGO_WALK if _NO_EGO_WALK else 0)
+
+    def run(phases):
+        call("txe_gat_collapse_bwd_fused", *args, phases | always, *rest, _lib.stream_ptr())
+    last = _lib.FUSED_REDUCE | (_lib.PH_DEFER if chain is not None else 0)     # (with a chain the final reductions are left to the bottom layer's launch)
     if chain is not None:
         chain.keep += [ws, d_hg, st, sp, zgid] + ([link.part, link.fwd, link.ds, link.s] if link is not None else [])
     if link is not None:                            # dZ given: no product left in this layer's backward, nothing for a second stream
         if ld != st.Kp and not edot:
             raise RuntimeError("folded graph vector: dZ must have the padded row pitch")
-        run(4 | 256)
-        run(last | 256)
+        run(_lib.FUSED_SWEEP | _lib.FUSED_DZ_GIVEN)
+        run(last | _lib.FUSED_DZ_GIVEN)
     elif _NO_SIDE_STREAM:
-        run(7 | last)
+        run(_lib.FUSED_DZ | _lib.FUSED_DW | _lib.FUSED_SWEEP | last)
     else:
         # the folded layer's weight-gradient GEMM (MFMA-bound, needs only d_hg and Z) runs on a second stream under the HBM-bound
         # sweeps: complementary resources, and nothing downstream waits for it before the final reduction
-        # (| 128 on every call: the product beside other kernels takes few fat k-slices, and the workspace is laid out for them)
+        # (| FUSED_DW_BESIDE on every call: the product beside other kernels takes few fat k-slices, and the workspace is laid out for them)
         main, side = torch.cuda.current_stream(), _side_stream(st.X.device)
         _order(main, side)
         with torch.cuda.stream(side):
-            run(2 | 128)
-        run(1 | 128)
-        run(4 | 128)
+            run(_lib.FUSED_DW | _lib.FUSED_DW_BESIDE)
+        run(_lib.FUSED_DZ | _lib.FUSED_DW_BESIDE)
+        run(_lib.FUSED_SWEEP | _lib.FUSED_DW_BESIDE)
         _order(side, main)
-        run(last | 128)
-    return d_Yp, dW, dal, dar, dP, d_pw
+        run(last | _lib.FUSED_DW_BESIDE)
+    return (d_Yp,) + out
 
 
 class GATStackFunction(torch.autograd.Function):
@@ -773,7 +789,7 @@ class GATStackFunction(torch.autograd.Function):
                         ctx.mark_non_differentiable(st.Wp)
                         ctx.set_materialize_grads(False)    # (no zero "gradient" of the packed weights: a 4 MB fill per step)
                     if not need:
-                        st.cl = st.mask = st.Wp = st.X = None
+                        st.cl = st.desc = st.mask = st.Wp = st.X = None
                     break
                 if last:
                     out, ld_out = _empty((N, F), h), F
@@ -863,13 +879,12 @@ class GATStackFunction(torch.autograd.Function):
                 if collapse and l == L - 1:
                     if l > 0 and _fused_bwd_ok(csr, st, states[l - 1]):
                         d_Y_ready, dW, dal, dar, dP, d_pw = _gat_collapse_bwd_fused(
-                            csr, st, states[l - 1], ctx.rpos, ctx.pwf, cfg.vocab, cfg.feat_p, cfg.attn_p, cfg.attn_slope, d_res,
+                            csr, st, states[l - 1], ctx.rpos, ctx.pwf, cfg.vocab, cfg.attn_p, cfg.attn_slope, d_res,
                             cfg.act_slope if act_on else None, chain, link=(ctx.link or FoldLink()) if z_only else None)
                     elif z_only:
                         raise RuntimeError("collapse_z was requested for a stack whose fused backward does not apply (folded_graph_vector_ok)")
                     else:
-                        d_X, dW, dal, dar, dP, d_pw = _gat_collapse_bwd(csr, st, ctx.rpos, ctx.pwf, cfg.vocab, cfg.feat_p, cfg.attn_p,
-                                                                        cfg.attn_slope, d_res, act_on, cfg.act_slope)
+                        d_X, dW, dal, dar, dP, d_pw = _gat_collapse_bwd(csr, st, ctx.rpos, ctx.pwf, cfg.vocab, d_res, act_on, cfg.act_slope)
                 elif d_Y_ready is not None:
                     d_X, dW, dal, dar, dP = _gat_dense_bwd(st, cfg.vocab, cfg.feat_p, d_Y_ready, need_dh, act_on, cfg.act_slope, chain,
                                                            defer=l > 0)
@@ -918,12 +933,13 @@ class GcnFolded(typing.NamedTuple):
 
 
 class _GcnLayerState:
-    __slots__ = ("X", "Wp", "mask", "W", "b", "P", "Kh", "Pd", "Kp", "Fo", "Fop", "seed", "cl", "x_dropped")
+    __slots__ = ("X", "Wp", "mask", "W", "b", "P", "Kh", "Pd", "Kp", "Fo", "Fop", "seed", "cl", "x_dropped", "desc")
 
     def __init__(self):
         self.X = self.Wp = self.mask = self.W = self.b = self.P = None
         self.Kh = self.Pd = self.Kp = self.Fo = self.Fop = self.seed = 0
         self.cl = None              # GcnFolded: the output layer folded behind the readout
+        self.desc = None            # ... and its (_lib.GraphBatch, _lib.GcnFoldLayer), as in _GatLayerState
         self.x_dropped = False
 
 
@@ -1006,10 +1022,13 @@ class GCNStackFunction(torch.autograd.Function):
                     Z, out = _empty((max(G, 1), st.Kp), h), (None if z_only else _empty((G, st.Fo), h))
                     wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, 8)
                     ws = _ws(wsb, h)
-                    call("txe_gcn_collapse_fwd", ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.graph_off), N, G, ptr(st.X), st.Kh, st.Pd,
-                         ptr(st.Wp), st.Fo, ptr(st.b), cfg.drop_ps[l], ptr(st.mask), ptr(norm), ptr(rpos), ptr(pwf), ptr(coef), ptr(wsum),
-                         ptr(gid), ptr(Z), ptr(out), st.Fo, ptr(ws), wsb, st_)
-                    st.cl = GcnFolded(coef, wsum, gid, Z)
+                    st.cl = GcnFolded(coef, wsum, gid, Z)            # (owns what the descriptors point to, with st, csr and ctx)
+                    batch = _graph_batch(csr, N)
+                    layer = _lib.GcnFoldLayer(X=ptr(st.X), Kh=st.Kh, Pd=st.Pd, pos=ptr(rpos), Wp=ptr(st.Wp), Fo=st.Fo,
+                                              bias=ptr(st.b), drop_p=cfg.drop_ps[l], mask=ptr(st.mask), norm=ptr(norm), pw=ptr(pwf),
+                                              coef=ptr(coef), wsum=ptr(wsum), gid=ptr(gid), Z=ptr(Z), hg=ptr(out), ld_hg=st.Fo)
+                    st.desc = (batch, layer)
+                    call("txe_gcn_collapse_fwd", _lib.ref(batch), _lib.ref(layer), ptr(ws), wsb, st_)
                     if z_only:
                         if cfg.link is not None:
                             cfg.link.by_k, cfg.link.one_col = True, (st.Kh + st.Pd if st.b is not None else -1)
@@ -1017,7 +1036,7 @@ class GCNStackFunction(torch.autograd.Function):
                         ctx.mark_non_differentiable(st.Wp)
                         ctx.set_materialize_grads(False)
                     if not need:
-                        st.cl = st.mask = st.Wp = st.X = None
+                        st.cl = st.desc = st.mask = st.Wp = st.X = None
                     break
                 hw = _empty((N, st.Fop), h)
                 if table and l == 0:
@@ -1080,7 +1099,7 @@ class GCNStackFunction(torch.autograd.Function):
             for l in range(L - 1, -1, -1):
                 st = states[l]
                 if collapse and l == L - 1:
-                    coef, wsum, gid, Z = st.cl
+                    batch, layer = st.desc
                     G = csr.n_graphs
                     dh, ld = _rows(d_out)
                     act_on = l > 0 and cfg.act_slopes[l - 1] is not None
@@ -1096,14 +1115,13 @@ class GCNStackFunction(torch.autograd.Function):
                         d_b = torch.empty_like(st.b) if st.b is not None else None
                     dP = torch.empty_like(st.P) if st.P is not None else None
                     d_pw = torch.empty_like(ctx.pwf) if ctx.pwf is not None else None
-                    v = max(cfg.vocab, ctx.pwf.numel() if ctx.pwf is not None else 0)
-                    wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, max(v, 8))
+                    # (what backward adds to the layer's descriptor: the vocabulary, and the positions as the position table's gradient reads them)
+                    layer.pos, layer.vocab = ptr(pos if st.P is not None else ctx.rpos), max(cfg.vocab, ctx.pwf.numel() if ctx.pwf is not None else 0)
+                    wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, max(layer.vocab, 8))
                     ws = _ws(wsb, d_out)
-                    call("txe_gcn_collapse_bwd", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.graph_off), N, G, ptr(st.X), st.Kh, st.Pd,
-                         ptr(pos if st.P is not None else ctx.rpos), v, ptr(st.Wp), st.Fo, cfg.drop_ps[l], ptr(st.mask), ptr(norm),
-                         ptr(ctx.pwf), ptr(coef), ptr(wsum), ptr(gid), ptr(Z), ptr(dh), ld, int(act_on),
-                         (cfg.act_slopes[l - 1] if act_on else 1.0), ptr(d_X), None if z_only else ptr(dW), None if z_only else ptr(d_b),
-                         ptr(dP), ptr(d_pw), int(z_only), ptr(ws), wsb, st_)
+                    gdesc = _lib.GcnFoldGrads(dW=None if z_only else ptr(dW), d_b=None if z_only else ptr(d_b), dP=ptr(dP), d_pw=ptr(d_pw))
+                    call("txe_gcn_collapse_bwd", _lib.ref(batch), _lib.ref(layer), ptr(dh), ld, int(act_on),
+                         (cfg.act_slopes[l - 1] if act_on else 1.0), ptr(d_X), _lib.ref(gdesc), int(z_only), ptr(ws), wsb, st_)
                     grads[3 * l:3 * l + 3] = [dW, d_b, dP]
                     if l > 0:
                         d_pre, ld_dpre = d_X, st.Kp

@@ -19,6 +19,72 @@ def _header_decls():
     return decls
 
 
+def _header_text():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "txe.h")).read(), flags=re.S)
+
+
+def _header_structs():
+    """every `struct txe_* { ... };` of the header as an ordered list of (field, C type or "*" for a pointer)"""
+    structs = {}
+    for m in re.finditer(r"\bstruct\s+(txe_\w+)\s*\{(.*?)\}\s*;", _header_text(), flags=re.S):
+        fields = []
+        for stmt in (x.strip() for x in m.group(2).replace("\n", " ").split(";")):
+            if not stmt:
+                continue
+            first, *more = [d.strip() for d in stmt.split(",")]
+            ctype, name = re.match(r"(.*?)(\w+)$", first).groups()          # `const float *` + `W`, `int ` + `n_nodes`
+            base = ctype.replace("*", "").replace("const ", "").strip()
+            fields.append((name, "*" if "*" in ctype else base))
+            fields += [(d.lstrip("* "), "*" if d.startswith("*") else base) for d in more]      # `, *attn_l` / `, Kh`
+        structs[m.group(1)] = fields
+    return structs
+
+
+def _header_constants():
+    """every `NAME = value` of the header's enums and every `#define NAME value` with an integer value"""
+    text = _header_text()
+    vals = {k: int(v) for body in re.findall(r"\benum\s*\{(.*?)\}\s*;", text, flags=re.S) for k, v in re.findall(r"(TXE_\w+)\s*=\s*(-?\d+)", body)}
+    vals.update({k: int(v) for k, v in re.findall(r"#define\s+(TXE_\w+)\s+(-?\d+)\s*$", text, flags=re.M)})
+    return vals
+
+
+CMAP = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+        "unsigned long long": ctypes.c_ulonglong, "unsigned": ctypes.c_uint, "double": ctypes.c_double, "*": ctypes.c_void_p}
+
+
+def test_ctypes_structures_mirror_the_header_structs():
+    """every ctypes.Structure of _lib.py names a struct of include/txe.h in its docstring and has that struct's fields: same names, same
+    order, same C types (pointers as c_void_p) -- and every struct of the header has such a mirror"""
+    from taxoexpan_amd import _lib
+    structs = _header_structs()
+    mirrors = {}
+    for obj in vars(_lib).values():
+        if isinstance(obj, type) and issubclass(obj, ctypes.Structure) and obj is not ctypes.Structure:
+            mirrors[re.match(r"struct (txe_\w+)", obj.__doc__).group(1)] = obj
+    assert set(mirrors) == set(structs) and len(structs) >= 9, set(mirrors) ^ set(structs)
+    for name, fields in structs.items():
+        assert [(f, CMAP[t]) for f, t in fields] == [(f, t) for f, t in mirrors[name]._fields_], name
+    # (the parser itself: a pointer list, a scalar list and a two-word type)
+    gat = dict(structs["txe_gat_fold_layer"])
+    assert gat["attn_l"] == "*" and gat["Pd"] == "int" and gat["seed"] == "unsigned long long" and gat["gid"] == "*" and gat["ld_hg"] == "long long"
+    assert [f for f, _ in structs["txe_graph_batch"]] == ["rowptr_in", "col_src", "rowptr_out", "col_dst", "pos_out", "graph_off", "n_nodes", "n_edges", "G"]
+
+
+def test_phase_and_flag_names_match_the_header():
+    """the TXE_DENSE_* / TXE_FUSED_* / TXE_PH_* / TXE_FOLD_* bits of include/txe.h = the constants of the same names in _lib.py"""
+    from taxoexpan_amd import _lib
+    hdr = _header_constants()
+    names = [k for k in hdr if k.startswith(("TXE_DENSE_", "TXE_FUSED_", "TXE_PH_", "TXE_FOLD_"))]
+    assert len(names) == 17, names
+    for k in names:
+        assert getattr(_lib, k[4:]) == hdr[k], k
+    mine = [k for k in vars(_lib) if k.startswith(("DENSE_", "FUSED_", "PH_", "FOLD_"))]
+    assert sorted("TXE_" + k for k in mine) == sorted(names)
+    assert hdr["TXE_FUSED_ALL"] == hdr["TXE_FUSED_DZ"] | hdr["TXE_FUSED_DW"] | hdr["TXE_FUSED_SWEEP"] | hdr["TXE_FUSED_REDUCE"]
+    assert hdr["TXE_DENSE_ALL"] == hdr["TXE_DENSE_DX"] | hdr["TXE_DENSE_DW"] | hdr["TXE_DENSE_REDUCE"]
+    assert hdr["TXE_TAIL_CHAIN_BYTES"] == _lib.TAIL_CHAIN_BYTES and hdr["TXE_ERR_ARG"] == -1
+
+
 def test_library_builds_loads_and_exports_header_symbols():
     import __graft_entry__ as ge
     lib_path = ge.build()
@@ -68,7 +134,41 @@ def test_argument_validation_needs_no_gpu():
     assert lib.txe_gat_padded_k(250, 50) == 320 and lib.txe_gat_padded_f(4, 500) == 2048
     assert lib.txe_gat_aggregate_table_supported(4, 500, 2048, 3, 2080) == 1 and lib.txe_gat_aggregate_table_supported(5, 500, 2560, 3, 0) == 0
     assert lib.txe_gat_aggregate_table_fwd(None, None, 5, None, 2048, None, None, None, 3, 4, 500, 0.2, 0, 1.0, None, 0, None, 0, None, 0, None) == -1
-
+    # the folded layers' entry points: a NULL descriptor, then descriptors whose required pointers are NULL
+    ref = ctypes.addressof
+    batch, gat, gcn = _lib.GraphBatch(n_nodes=5, n_edges=8, G=2), _lib.GatFoldLayer(Kh=16, Pd=4, D=8), _lib.GcnFoldLayer(Kh=16, Pd=4, Fo=8)
+    below, grads, ggrads = _lib.GatFoldBelow(Hp=4, Dp=4), _lib.GatFoldGrads(), _lib.GcnFoldGrads()
+    b, g, c, lo, gr, cg = (ref(x) for x in (batch, gat, gcn, below, grads, ggrads))
+    for bb, ll in ((None, g), (b, None), (b, g)):
+        assert lib.txe_gat_collapse_fwd(bb, ll, None, 0, None, 0, None) == -1
+        assert lib.txe_gat_collapse_bwd(bb, ll, None, 8, 0, 1.0, None, gr, None, 0, None) == -1
+        assert lib.txe_gat_collapse_bwd_fused(bb, ll, lo, None, gr, None, 8, 1.0, _lib.FUSED_ALL, None, 0, None, None, None, 0, None) == -1
+    for bb, ll in ((None, c), (b, None), (b, c)):
+        assert lib.txe_gcn_collapse_fwd(bb, ll, None, 0, None) == -1
+        assert lib.txe_gcn_collapse_bwd(bb, ll, None, 8, 0, 1.0, None, cg, 0, None, 0, None) == -1
+    assert lib.txe_gat_collapse_bwd(b, g, None, 8, 0, 1.0, None, None, None, 0, None) == -1
+    assert lib.txe_gcn_collapse_bwd(b, c, None, 8, 0, 1.0, None, None, 0, None, 0, None) == -1
+    for lo_, gr_ in ((None, gr), (lo, None)):
+        assert lib.txe_gat_collapse_bwd_fused(b, g, lo_, None, gr_, None, 8, 1.0, _lib.FUSED_ALL, None, 0, None, None, None, 0, None) == -1
+    # ... and with every pointer in place (never read: host memory, and no workspace) the checks run in the old order: the fused
+    # backward refuses a (Kh, Pd, Hp, Dp) it does not support before it looks at the workspace, which is what all five refuse last
+    buf = (ctypes.c_float * 64)()
+    a = ref(buf)
+    batch = _lib.GraphBatch(a, a, a, a, a, a, 5, 8, 2)
+    gat = _lib.GatFoldLayer(X=a, Kh=16, Pd=4, pos=a, vocab=3, Wp=a, W=a, attn_l=a, attn_r=a, D=8, a12=a, alpha=a, coef=a, wsum=a, gid=a, Z=a, hg=a, ld_hg=8)
+    gcn = _lib.GcnFoldLayer(X=a, Kh=16, Pd=4, pos=a, vocab=3, Wp=a, Fo=8, norm=a, coef=a, wsum=a, gid=a, Z=a, hg=a, ld_hg=8)
+    grads, ggrads = _lib.GatFoldGrads(a, a, a, a, a), _lib.GcnFoldGrads(a, a, a, a)
+    b, g, c, gr, cg = (ref(x) for x in (batch, gat, gcn, grads, ggrads))
+    for Hp, Dp, want in ((3, 4, -1), (4, 8, -1), (4, 3, -1), (4, 4, -3)):     # 3 heads; Hp * Dp != Kh; Dp no multiple of 4; supported
+        assert lib.txe_gat_fused_bwd_supported(16, 4, Hp, Dp) == (want == -3)
+        below = _lib.GatFoldBelow(Yp=a, ld_yp=128, Hp=Hp, Dp=Dp, alpha_p=a, d_Yp=a, ld_dyp=128, n_pad=0, dz_p=a)
+        assert lib.txe_gat_collapse_bwd_fused(b, g, ref(below), None, gr, a, 8, 1.0, _lib.FUSED_ALL, None, 0, None, None, a, 0, None) == want
+    assert lib.txe_gat_collapse_fwd(b, g, None, 0, a, 0, None) == -3
+    assert lib.txe_gat_collapse_bwd(b, g, a, 8, 0, 1.0, a, gr, a, 0, None) == -3
+    assert lib.txe_gcn_collapse_fwd(b, c, a, 0, None) == -3
+    assert lib.txe_gcn_collapse_bwd(b, c, a, 8, 0, 1.0, a, cg, 0, a, 0, None) == -3
+    gat.feat_drop_p = gcn.drop_p = 1.0                                       # (a scalar out of range, read through the descriptor)
+    assert lib.txe_gat_collapse_fwd(b, g, None, 0, a, 0, None) == -1 and lib.txe_gcn_collapse_fwd(b, c, a, 0, None) == -1
 
 def test_host_rng_restatement_matches_library():
     """taxoexpan_amd/rng.py == the hash the kernels inline (evaluated on the host by the library)"""

@@ -384,11 +384,10 @@ def test_query_prefetch_token_is_stale_after_a_write_to_either_operand():
 
 def test_fold_link_names_its_two_stages():
     """ops.FoldLink: carried_T needs e_part AND a job with its score record; dz_implicit needs e_part AND the matcher's ds; without
-    the latter the fused backward gets the seven absent edot arguments"""
-    from taxoexpan_amd import ops
-    none7 = (None, None, None, 0, None, None, None)
+    the latter the fused backward gets no matcher's share (None), with it a _lib.FoldMatch that names every address"""
+    from taxoexpan_amd import ops, _lib
     link = ops.FoldLink()
-    assert not link.carried_T and not link.dz_implicit and link.edot_args(None) == none7
+    assert not link.carried_T and not link.dz_implicit and link.edot_args(None) is None
     assert (link.part, link.S, link.by_k, link.one_col, link.fwd, link.e_part, link.ds, link.s) == (None, 0, False, -1, None, None, None, None)
     job = _fold_job(torch.randn(8, 4), None, None, torch.randn(1, 6, 4), torch.zeros(128, 32), 8)
     link.e_part = torch.zeros(20, 1)
@@ -396,15 +395,20 @@ def test_fold_link_names_its_two_stages():
     link.fwd = job
     assert not link.carried_T                                                    # a job whose T did not ride in a sweep
     job.score = ops.FoldScore(torch.zeros(9, dtype=torch.int32), 20, 8, 16, 4, torch.zeros(20), torch.zeros(8), 0.0, 0)
-    assert link.carried_T and not link.dz_implicit and link.edot_args(None) == none7
+    assert link.carried_T and not link.dz_implicit and link.edot_args(None) is None
     link.e_part = None
     assert not link.carried_T
     link.ds, link.s, link.apply_exp = torch.zeros(8), torch.zeros(8), 1
-    assert not link.dz_implicit and link.edot_args(None) == none7                # ds without e_part
+    assert not link.dz_implicit and link.edot_args(None) is None                 # ds without e_part
     link.e_part = torch.zeros(20, 1)
     assert link.dz_implicit and link.carried_T
+    job.run_id, zgid = torch.zeros(8, dtype=torch.int32), torch.zeros(20, dtype=torch.int32)
+    m = link.edot_args(zgid)
+    assert isinstance(m, _lib.FoldMatch)
+    assert (m.e_part, m.m_ds, m.m_s, m.m_exp, m.Tf, m.zrow, m.zgid) == (link.e_part.data_ptr(), link.ds.data_ptr(), link.s.data_ptr(), 1,
+                                                                        job.T.data_ptr(), job.run_id.data_ptr(), zgid.data_ptr())
     link.ds = None
-    assert not link.dz_implicit and link.edot_args(None) == none7
+    assert not link.dz_implicit and link.edot_args(None) is None
     assert not ops._NO_LINK.dz_implicit and ops._NO_LINK.S == 0 and ops._NO_LINK.part is None
 
 
