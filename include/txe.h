@@ -578,6 +578,27 @@ int txe_adam_step(int n_tensors, float* const* params, const float* const* grads
                   float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1, double beta2, double eps,
                   double weight_decay, long long step, void* stream);
 
+/* The per-step device log of the training loop (what trainer.py:63-65 reads back with `loss.item()` every step; csrc/txe_steplog.hip):
+ * one call per step, enqueued between `loss.backward()` and `optimizer.step()`; nothing returns to the host.
+ *   loss_log[step]   = loss[0]                                     (fp32 device scalar)
+ *   gnorm2_log[step] = sum over every element g of every gradient tensor of (double)g * (double)g
+ *   acc[0] += (double)loss[0];  acc[1] += 1                        (the epoch's loss sum and its number of logged steps)
+ *   first_bad[0] = step  if first_bad[0] < 0 and loss[0] or any gradient element is not finite  (the owner initialises it to -1)
+ * grads is a HOST array of n_tensors DEVICE pointers (dense fp32, numel[t] elements; an empty tensor is skipped; n_tensors == 0 logs the
+ * loss alone); the table travels in the kernel argument.  Every workgroup squares and sums one run of TXE_STEP_LOG_CHUNK consecutive
+ * elements of one tensor in fp64 and stores its partial in ws; the workgroup that draws the last ticket of an integer counter adds the
+ * partials in a fixed order (no floating-point atomics anywhere): the logged value is a pure function of the gradients, bit-identical
+ * from run to run.  That workgroup also updates acc and first_bad with plain read-modify-writes: the calls of one log must be ordered
+ * on one stream.
+ * ws: txe_step_log_ws_bytes(n_chunks) bytes, n_chunks = sum over the tensors of ceil(numel[t] / TXE_STEP_LOG_CHUNK), 16-byte aligned;
+ * its first 16 bytes (the ticket) are ZEROED ONCE by the owner before the first call and left zero by every call.
+ * TXE_ERR_ARG (nothing launched): a NULL loss / log pointer / ws, step outside [0, capacity), n_tensors < 0, a NULL table with
+ * n_tensors > 0, a negative numel or a NULL pointer of a non-empty tensor; TXE_ERR_WORKSPACE: ws_bytes too small. */
+#define TXE_STEP_LOG_CHUNK 4096
+size_t txe_step_log_ws_bytes(int n_chunks);
+int txe_step_log(const float* loss, int n_tensors, const float* const* grads, const long long* numel, long long step, long long capacity,
+                 float* loss_log, double* gnorm2_log, double* acc, long long* first_bad, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- fp32 products on the bf16 matrix pipe (replaces the fp32-MFMA route of model_zoo.py:83 `self.fc(...)` for the first
  * layer's projection).  A packed operand holds every fp32 element as the EXACT sum of three bf16 numbers (three planes, stored as 1-KB
  * MFMA fragments: csrc/txe_gemm_split.h); txe_gemm_nt_split forms C [M][N] = A [M][K] B[N][K]^T from six of the nine plane products with

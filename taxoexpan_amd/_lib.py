@@ -11,6 +11,7 @@ DENSE_DX, DENSE_DW, DENSE_REDUCE, DENSE_ALL, DENSE_DX_SPLIT, PH_DEFER = 1, 2, 4,
 FUSED_DZ, FUSED_DW, FUSED_SWEEP, FUSED_REDUCE, FUSED_ALL = 1, 2, 4, 8, 15
 FUSED_DW_BESIDE, FUSED_DZ_GIVEN, FUSED_EDOT, FUSED_NO_EGO_WALK = 128, 256, 512, 1024
 FOLD_A12_READY, FOLD_HG_SPLIT = 1, 2
+STEP_LOG_CHUNK = 4096          # TXE_STEP_LOG_CHUNK: gradient elements per workgroup of txe_step_log
 
 P, I, L, F, D, U64, SZ = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_size_t
 
@@ -128,6 +129,8 @@ SIGNATURES = {
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),
     "txe_info_nce": (I, [P, L, I, I, P, P, P, L, P]),
     "txe_adam_step": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P]),
+    "txe_step_log_ws_bytes": (SZ, [I]),
+    "txe_step_log": (I, [P, I, P, P, L, L, P, P, P, P, P, SZ, P]),
     "txe_dropout_uniform_host": (F, [U64, U64]),
     "txe_dropout_mask_word_host": (C.c_uint, [U64, U64, F]),
     "txe_profile_enable": (I, [I]),

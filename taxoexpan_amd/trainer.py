@@ -1,0 +1,289 @@
+"""The training loop of the reference -- Trainer._train_epoch (trainer/trainer.py:41-94) and BaseTrainer.train / _save_checkpoint /
+_resume_checkpoint (base/base_trainer.py:59-176) -- in the style of evaluate.validate: nothing per step returns to the host.
+
+    StepLog       the device log of an epoch: per step the loss and the gradients' L2 norm, the running loss sum and the first step
+                  whose loss or gradients were not finite, written by ONE launch per step (txe_step_log, csrc/txe_steplog.hip) between
+                  `loss.backward()` and `optimizer.step()`; read back once per epoch
+    train_epoch   trainer.py:41-77 without `label.sum()` (:53), `loss.item()` (:64-65) or any other read-back inside the loop
+    fit           base_trainer.py:59-107 + trainer.py:79-94: epochs of train_epoch + evaluate.validate, the LR schedule, monitoring,
+                  early stopping, checkpoints with the reference's keys, resume -- and one addition: a diverged epoch ends the run
+    host_step_log the numpy restatement of txe_step_log (its written definition; the CPU tests use it)
+"""
+import math
+import os
+import warnings
+
+import numpy as np
+import torch
+
+
+def host_step_log(losses, grads_per_step, capacity=None):
+    """What txe_step_log leaves after len(losses) steps: (loss_log fp32 [capacity], gnorm2_log fp64 [capacity], acc fp64 [2],
+    first_bad int64 [1]).  grads_per_step[s] = the gradient arrays of step s (any shapes; none at all logs the loss alone).
+    gnorm2 adds the fp64 squares of the fp32 elements one after the other, tensor after tensor in index order (the kernel adds the same
+    numbers in its own fixed order: equal up to the reordering error of an fp64 sum, N * 2^-52 relative)."""
+    n = len(losses)
+    if len(grads_per_step) != n:
+        raise ValueError("one list of gradients per step")
+    capacity = n if capacity is None else int(capacity)
+    if n > capacity:
+        raise ValueError(f"{n} steps do not fit a log of capacity {capacity}")
+    loss_log, gnorm2_log = np.zeros(capacity, dtype=np.float32), np.zeros(capacity, dtype=np.float64)
+    acc, first_bad = np.zeros(2, dtype=np.float64), np.full(1, -1, dtype=np.int64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s in range(n):
+            loss = np.float32(losses[s])
+            flat = [np.asarray(g, dtype=np.float32).reshape(-1).astype(np.float64) for g in grads_per_step[s]]
+            sq = np.concatenate(flat) ** 2 if flat else np.zeros(0)
+            total = float(np.cumsum(sq)[-1]) if sq.size else 0.0          # cumsum: strictly sequential, unlike np.sum's pairwise blocks
+            loss_log[s], gnorm2_log[s] = loss, total
+            acc[0] += np.float64(loss)
+            acc[1] += 1.0
+            if first_bad[0] < 0 and not (np.isfinite(loss) and np.isfinite(sq).all()):
+                first_bad[0] = s
+    return loss_log, gnorm2_log, acc, first_bad
+
+
+class StepLog:
+    """The device log of up to `capacity` training steps (one epoch).  record() enqueues one txe_step_log on the current stream and
+    returns nothing; read() is the one read-back.  All records of one log must be enqueued on one stream (the kernel's last workgroup
+    updates the running sums with a plain read-modify-write)."""
+
+    def __init__(self, device, capacity):
+        from . import _lib
+        self.device, self.capacity = torch.device(device), int(capacity)
+        if self.capacity < 1:
+            raise ValueError("StepLog needs a capacity of at least one step")
+        if self.device.type != "cuda":
+            raise RuntimeError("taxoexpan_amd.trainer.StepLog lives on the GPU (no CPU path; host_step_log is the restatement)")
+        # one fp64 buffer, so that read() is ONE copy: [acc (2) | first_bad (1, as int64) | gnorm2 (capacity) | loss (capacity fp32)]
+        c = self.capacity
+        self._buf = torch.zeros(3 + c + (c + 1) // 2, dtype=torch.float64, device=self.device)
+        self._acc, self._first_bad = self._buf[0:2], self._buf[2:3].view(torch.int64)
+        self._gnorm2, self._loss = self._buf[3:3 + c], self._buf[3 + c:].view(torch.float32)[:c]
+        self._first_bad.fill_(-1)
+        self._ws, self._ws_bytes = None, 0
+        self._table = None
+        self.n_recorded = 0
+        self._lib = _lib
+
+    def _workspace(self, n_chunks):
+        need = self._lib.pure("txe_step_log_ws_bytes", n_chunks)
+        if need > self._ws_bytes:                                   # zeroed: the ticket word starts at 0 and every launch leaves it there
+            self._ws = torch.zeros((need + 7) // 8, dtype=torch.float64, device=self.device)
+            self._ws_bytes = self._ws.numel() * 8
+        return self._ws
+
+    def record(self, loss, params):
+        """log the step whose scalar `loss` (fp32, on the device) was just back-propagated into the `.grad` of `params` (parameters
+        whose .grad is None are skipped); raises before any launch when the log is full"""
+        import ctypes as C
+        _lib = self._lib
+        s = self.n_recorded
+        if s >= self.capacity:
+            raise IndexError(f"StepLog is full: step {s} of a log of capacity {self.capacity} (reset() starts the next epoch)")
+        if not (torch.is_tensor(loss) and loss.numel() == 1 and loss.dtype == torch.float32 and loss.device == self.device):
+            raise ValueError("StepLog.record needs the loss as one fp32 element on the log's device")
+        grads = []
+        for p in params:
+            g = p.grad
+            if g is None:
+                continue
+            if g.is_sparse or g.dtype != torch.float32 or g.device != self.device:
+                raise RuntimeError("taxoexpan_amd.trainer.StepLog: dense fp32 gradients on the log's device only")
+            grads.append(g if g.is_contiguous() else g.contiguous())
+        addr = [g.data_ptr() for g in grads]
+        numel = [g.numel() for g in grads]
+        tab = self._table
+        if tab is None or tab["addr"] != addr or tab["numel"] != numel:      # (set_to_none gradients are new tensors, usually at the old addresses)
+            chunk = _lib.STEP_LOG_CHUNK
+            tab = self._table = dict(addr=addr, numel=numel, g=(C.c_void_p * len(addr))(*addr), n=(C.c_longlong * len(numel))(*numel),
+                                     n_chunks=sum(-(-n // chunk) for n in numel))
+        ws = self._workspace(tab["n_chunks"])
+        loss = loss.detach()
+        with _lib.on_device(self.device):
+            _lib.call("txe_step_log", loss.data_ptr(), len(addr), tab["g"], tab["n"], s, self.capacity, self._loss.data_ptr(),
+                      self._gnorm2.data_ptr(), self._acc.data_ptr(), self._first_bad.data_ptr(), ws.data_ptr(), self._ws_bytes,
+                      _lib.stream_ptr())
+        self.n_recorded = s + 1
+
+    def read(self):
+        """the epoch's one read-back: dict(loss fp32 [n], grad_norm fp64 [n], loss_sum, n_steps, first_nonfinite (-1: none))"""
+        host = self._buf.cpu().numpy()
+        c, n = self.capacity, self.n_recorded
+        return dict(loss=host[3 + c:].view(np.float32)[:n].copy(), grad_norm=np.sqrt(host[3:3 + n]), loss_sum=float(host[0]),
+                    n_steps=int(host[1]), first_nonfinite=int(host[2:3].view(np.int64)[0]))
+
+    def reset(self):
+        """clear the log for the next epoch"""
+        self._buf.zero_()
+        self._first_bad.fill_(-1)
+        self.n_recorded = 0
+
+
+def _is_info_nce(loss_fn):
+    return getattr(loss_fn, "__name__", "").startswith("info_nce")        # trainer.py:20 tests the config's loss NAME the same way
+
+
+def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None):
+    """trainer.py:41-77 on the device: model.train(), then per batch zero_grad, forward, loss, backward, ONE txe_step_log launch,
+    optimizer.step() -- no .item(), .cpu() or synchronize between the first batch and the last (what `loader` does to build a batch is
+    its own business), then one read-back of the log.
+    loader: DeviceBatchLoader's (g, h, qf, label) or MaskedGraphDataLoader's (g, qf, label) batches, as evaluate.validate takes them.
+    loss_fn (default loss.info_nce_loss): a function whose __name__ starts with "info_nce" gets the scores regrouped to
+    [-1, group_size] and the target None (= all zeros, trainer.py:53-55); group_size defaults to 1 + loader.dataset.negative_size --
+    sampling_mode 1 draws exactly that many anchors per query, so the shape is known without trainer.py:53's `label.sum()` -- and a batch
+    that is no multiple of it raises ValueError.  Any other loss_fn gets (prediction, label) as trainer.py:57-58 passes them.
+    log: a StepLog to reuse (it is reset first; one too small for len(loader) steps raises ValueError before the first step); default:
+    one of len(loader) steps.
+    Returns dict(loss = the fp64 sum of the fp32 step losses / n_batches -- trainer.py:76's total_loss / len(data_loader) --, n_batches,
+    losses fp32 [n_batches], grad_norms fp64 [n_batches], first_nonfinite = the first step with a non-finite loss or gradient, or -1).
+    It never stops early: that would take a read-back per step."""
+    if loss_fn is None:
+        from .loss import info_nce_loss as loss_fn
+    info_nce = _is_info_nce(loss_fn)
+    if info_nce and group_size is None:
+        k = getattr(getattr(loader, "dataset", None), "negative_size", None)
+        if k is None:
+            raise ValueError("train_epoch: group_size is needed (the loader has no dataset.negative_size to take it from)")
+        group_size = 1 + int(k)
+    if info_nce and int(group_size) < 1:
+        raise ValueError(f"group_size must be positive, got {group_size}")
+    params = list(model.parameters())
+    dev = params[0].device
+    if log is None:
+        log = StepLog(dev, max(1, len(loader)))
+    else:
+        if hasattr(loader, "__len__") and log.capacity < len(loader):
+            raise ValueError(f"the StepLog holds {log.capacity} steps, the loader yields {len(loader)}")     # before any optimizer step
+        log.reset()
+    model.train()                                                      # trainer.py:42
+    n_batches = 0
+    for batch in loader:
+        if len(batch) == 4:
+            g, h, qf, label = batch
+        else:
+            g, qf, label = batch
+            h = g.ndata.pop("x")                                       # trainer.py:48
+        h = h.to(dev, non_blocking=True)
+        qf = qf.to(dev, non_blocking=True) if torch.is_tensor(qf) else qf
+        label = label.to(dev, non_blocking=True)
+        optimizer.zero_grad()                                          # trainer.py:50
+        prediction = model(g, h, qf)
+        if info_nce:
+            if prediction.numel() % group_size:
+                raise ValueError(f"a batch of {prediction.numel()} scores is no multiple of group_size {group_size}")
+            loss = loss_fn(prediction.reshape(-1, group_size), None)
+        else:
+            loss = loss_fn(prediction, label)
+        loss.backward()                                                # trainer.py:60
+        log.record(loss, params)
+        optimizer.step()                                               # trainer.py:61
+        n_batches += 1
+    rec = log.read()
+    return dict(loss=rec["loss_sum"] / n_batches if n_batches else float("nan"), n_batches=n_batches, losses=rec["loss"],
+                grad_norms=rec["grad_norm"], first_nonfinite=rec["first_nonfinite"])
+
+
+class TrainingDiverged(RuntimeError):
+    """fit() met an epoch whose loss or gradients were not finite: .epoch (1-based), .step (0-based within the epoch) and .logs (the
+    per-epoch logs up to and including that epoch)"""
+
+    def __init__(self, epoch, step, logs=()):
+        super().__init__(f"training diverged: non-finite loss or gradient at step {step} of epoch {epoch}")
+        self.epoch, self.step, self.logs = epoch, step, list(logs)
+
+
+def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, save_best):
+    """base_trainer.py:126-149"""
+    state = {"arch": type(model).__name__, "epoch": epoch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
+             "monitor_best": monitor_best, "config": config}
+    os.makedirs(str(save_dir), exist_ok=True)
+    torch.save(state, os.path.join(str(save_dir), f"checkpoint-epoch{epoch}.pth"))
+    if save_best:
+        torch.save(state, os.path.join(str(save_dir), "model_best.pth"))
+
+
+def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
+        lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
+        loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None):
+    """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
+    `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
+      - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
+        picks val_metrics[0] or [2] by position, trainer.py:87-90), any other scheduler with a plain .step()
+      - monitor "min <key>" / "max <key>" / "off": improved = `<=` / `>=` the best so far (a tie counts); an epoch that did not improve
+        raises a count, and the run stops, without a checkpoint for that epoch, once the count exceeds early_stop; a key the log does
+        not have warns once and turns monitoring off
+      - every save_period epochs checkpoint-epoch{N}.pth under save_dir (None: nothing is written), and model_best.pth beside it when
+        the epoch was the best so far; keys arch, epoch, state_dict, optimizer, monitor_best, config as base_trainer.py:134-142
+    resume: such a checkpoint (this function's or the reference's): model, optimizer state, monitor_best and the start epoch are restored.
+    Two deviations from the reference, both on purpose: (1) when the monitored key is missing, base_trainer.py:87-101 sets the count to 0
+    and then still falls into its `else` branch, which raises it to 1 -- with early_stop = 0 the reference stops right there; here
+    monitoring is switched off without counting, so the run goes on.  (2) _resume_checkpoint warns when the checkpoint's `arch` config
+    differs and SKIPS the optimizer state when its optimizer `type` differs (base_trainer.py:164-174); fit has no config schema to compare,
+    so both checks are dropped: the optimizer state is always loaded, and a mismatch surfaces as load_state_dict's own error.
+    The one addition: an epoch whose step log shows a non-finite loss or gradient ends the run -- no validation, no scheduler step and no
+    checkpoint for it -- with TrainingDiverged(epoch, step).  train_epoch itself runs the epoch to its end (see there).
+    loss_fn / group_size go to train_epoch.  train_epoch_fn / validate_fn replace trainer.train_epoch / evaluate.validate (same call
+    signatures); the loop control here makes no GPU call of its own.  Returns the list of per-epoch logs."""
+    if train_epoch_fn is None:
+        train_epoch_fn = train_epoch
+    if validate_fn is None:
+        from .evaluate import validate as validate_fn
+    if metrics is None:
+        from .evaluate import VALIDATION_METRICS as metrics
+    metrics = list(metrics)
+    if monitor == "off":                                               # base_trainer.py:31-39
+        mnt_mode, mnt_metric, mnt_best = "off", None, 0
+    else:
+        mnt_mode, mnt_metric = monitor.split()
+        if mnt_mode not in ("min", "max"):
+            raise ValueError(f"monitor must be 'off', 'min <key>' or 'max <key>', got {monitor!r}")
+        mnt_best = math.inf if mnt_mode == "min" else -math.inf
+    plateau = isinstance(lr_scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau)
+    if plateau and scheduler_metric is None:
+        if mnt_metric is None:
+            raise ValueError("a ReduceLROnPlateau needs scheduler_metric when monitor is 'off'")
+        scheduler_metric = mnt_metric
+    start_epoch = 1
+    if resume is not None:                                             # base_trainer.py:151-176
+        ckpt = torch.load(str(resume), map_location="cpu", weights_only=False)
+        start_epoch = ckpt["epoch"] + 1
+        mnt_best = ckpt["monitor_best"]
+        model.load_state_dict(ckpt["state_dict"])
+        optimizer.load_state_dict(ckpt["optimizer"])
+    logs = []
+    not_improved_count = 0
+    for epoch in range(start_epoch, epochs + 1):
+        result = train_epoch_fn(model, train_loader, optimizer, loss_fn=loss_fn, group_size=group_size)
+        log = {"epoch": epoch}
+        log.update(result)
+        logs.append(log)
+        if result.get("first_nonfinite", -1) >= 0:
+            raise TrainingDiverged(epoch, int(result["first_nonfinite"]), logs)
+        if valid_loader is not None:                                   # trainer.py:80-82, base_trainer.py:71-72
+            val = validate_fn(model, valid_loader, metrics=metrics, larger_is_better=larger_is_better)
+            log.update({"val_" + name: v for name, v in zip(metrics, val["val_metrics"])})
+        if lr_scheduler is not None:                                   # trainer.py:84-92
+            if plateau:
+                if scheduler_metric not in log:
+                    raise ValueError(f"scheduler_metric {scheduler_metric!r} is not in the epoch's log {sorted(log)}")
+                lr_scheduler.step(log[scheduler_metric])
+            else:
+                lr_scheduler.step()
+        best = False
+        if mnt_mode != "off":                                          # base_trainer.py:81-104
+            if mnt_metric not in log:
+                warnings.warn(f"Metric '{mnt_metric}' is not found. Model performance monitoring is disabled.")
+                mnt_mode = "off"
+            else:
+                improved = log[mnt_metric] <= mnt_best if mnt_mode == "min" else log[mnt_metric] >= mnt_best
+                if improved:
+                    mnt_best, not_improved_count, best = log[mnt_metric], 0, True
+                else:
+                    not_improved_count += 1
+                if not_improved_count > early_stop:
+                    break
+        if save_dir is not None and epoch % save_period == 0:         # base_trainer.py:106-107
+            _save_checkpoint(save_dir, model, optimizer, epoch, mnt_best, config, best)
+    return logs

@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""One training epoch (trainer.py:41-77) on a MAG-CS-shaped masked dataset (synthetic.make_named_taxonomy("mag_cs", seed=47) written as
+raw files and read back; train mode, sampling_mode 1, 31 negatives, batches of 128 queries = 4,096 egonets: bench.py's step;
+bench.make_model("pgat"), optim.Adam(amsgrad) at bench.LR), two legs alternating in one process on DeviceBatchLoader(sampler="device"):
+  (a) trainer.train_epoch: one txe_step_log launch per step, nothing read back inside the loop, one read-back per epoch;
+  (b) the reference-style loop: `label.sum()` read back to reshape the scores, a torch.zeros target, `loss.item()` twice per step.
+Prints per leg and epoch the wall time and the time per step, then the step-log kernel's own average (and the Adam kernel's, for scale)
+from the library's profile hooks over --profile-steps steps of leg (a).
+
+    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50]"""
+import argparse
+import ctypes
+import os
+import random
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from taxoexpan_amd import _lib, synthetic as syn  # noqa: E402
+from taxoexpan_amd.data_loaders import DeviceBatchLoader  # noqa: E402
+from taxoexpan_amd.dataset import MAGDataset, MaskedGraphDataset  # noqa: E402
+from taxoexpan_amd.loss import info_nce_loss  # noqa: E402
+from taxoexpan_amd.optim import Adam  # noqa: E402
+from taxoexpan_amd.trainer import train_epoch  # noqa: E402
+
+BS, K = bench.N_QUERIES, bench.NEG
+
+
+def masked_mag_cs_train(directory):
+    tax = syn.make_named_taxonomy("mag_cs", seed=47)
+    syn.write_raw(directory, "magcs", syn.taxonomy_edges(tax), tax.features.numpy())
+    random.seed(0)
+    raw = MAGDataset("magcs", directory, raw=True)
+    return MaskedGraphDataset(raw, mode="train", sampling_mode=1, negative_size=K, expand_factor=50, normalize_embed=True)
+
+
+def reference_style_epoch(model, loader, optimizer, dev):
+    """trainer.py:41-77 as written: two host round trips per step"""
+    model.train()
+    total_loss, n = 0, 0
+    for bg, h, nf, label in loader:
+        optimizer.zero_grad()
+        prediction = model(bg, h, nf)
+        n_batches = int(label.sum().detach())
+        prediction = prediction.reshape(n_batches, -1)
+        target = torch.zeros(n_batches, dtype=torch.long).to(dev)
+        loss = info_nce_loss(prediction, target)
+        loss.backward()
+        optimizer.step()
+        loss.item()                                          # trainer.py:64 (the tensorboard scalar)
+        total_loss += loss.item()
+        n += 1
+    return total_loss / n, n
+
+
+class _First:
+    """the first n batches of a loader"""
+
+    def __init__(self, loader, n):
+        self.loader, self.n, self.dataset = loader, min(n, len(loader)), loader.dataset
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        for i, b in enumerate(self.loader):
+            if i == self.n:
+                return
+            yield b
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def profiled_kernels(model, loader, opt, steps):
+    """average duration by kernel name over `steps` steps of train_epoch (HIP events around every launch of the library)"""
+    lib = _lib.load()
+    lib.txe_profile_reset()
+    lib.txe_profile_enable(1)
+    train_epoch(model, _First(loader, steps), opt)
+    torch.cuda.synchronize()
+    lib.txe_profile_enable(0)
+    buf = ctypes.create_string_buffer(64)
+    ms, work, kind = ctypes.c_float(), ctypes.c_double(), ctypes.c_int()
+    by = {}
+    for i in range(lib.txe_profile_count()):
+        lib.txe_profile_get(i, buf, 64, ctypes.byref(ms), ctypes.byref(work), ctypes.byref(kind))
+        by.setdefault(buf.value.decode(), []).append((1e3 * ms.value, work.value))
+    lib.txe_profile_reset()
+    return {k: (float(np.mean([u for u, _ in v])), float(np.median([u for u, _ in v])), len(v), v[0][1]) for k, v in by.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--profile-steps", type=int, default=50)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "train_epoch_timing.py times the MI355X: no GPU found"
+    dev = torch.device("cuda:0")
+    with tempfile.TemporaryDirectory() as d:
+        t0 = time.perf_counter()
+        ds = masked_mag_cs_train(d)
+        print(f"dataset: {ds.node_features.shape[0]} nodes, {len(ds)} training queries (built in {time.perf_counter() - t0:.1f} s)", flush=True)
+    torch.manual_seed(47)
+    model = bench.make_model("pgat", dev)
+    opt = Adam(model.parameters(), lr=bench.LR, weight_decay=0, amsgrad=True)
+    loader = DeviceBatchLoader(ds, BS, dev, shuffle=True, seed=0, sampler="device")
+    n_grad = sum(p.numel() for p in model.parameters())
+    print(f"{len(loader)} steps per epoch, {BS} queries x {1 + K} egonets per step, {n_grad} gradient elements per step", flush=True)
+    train_epoch(model, _First(loader, 30), opt)              # warm-up of both legs (first-call costs, allocator)
+    reference_style_epoch(model, _First(loader, 30), opt, dev)
+    a_s, b_s = [], []
+    for e in range(args.epochs):
+        ta, ra = timed(lambda: train_epoch(model, loader, opt))
+        tb, (lb, nb) = timed(lambda: reference_style_epoch(model, loader, opt, dev))
+        assert ra["first_nonfinite"] == -1 and np.isfinite(lb), "the model diverged: the timing is void"
+        a_s.append(1e3 * ta / ra["n_batches"])
+        b_s.append(1e3 * tb / nb)
+        print(f"epoch {e}: (a) train_epoch {1e3 * ta:.1f} ms = {a_s[-1]:.3f} ms/step (loss {ra['loss']:.3f}, |g| {ra['grad_norms'][-1]:.3f}) | "
+              f"(b) reference-style loop {1e3 * tb:.1f} ms = {b_s[-1]:.3f} ms/step (loss {lb:.3f})", flush=True)
+    prof = profiled_kernels(model, loader, opt, args.profile_steps)
+    for name in ("step_log_kernel", "adam_kernel<true>"):
+        if name in prof:
+            mean, med, n, work = prof[name]
+            print(f"{name}: mean {mean:.2f} us, median {med:.2f} us over {n} launches; {work / 1e6:.2f} MB compulsory per launch "
+                  f"= {work / (1e-6 * med) / 1e12:.2f} TB/s at the median")
+    print(f"summary: (a) {min(a_s):.3f}-{max(a_s):.3f} ms/step (median {float(np.median(a_s)):.3f}), (b) {min(b_s):.3f}-{max(b_s):.3f} ms/step "
+          f"(median {float(np.median(b_s)):.3f}); (a) <= (b) in every epoch: {all(a <= b for a, b in zip(a_s, b_s))}")
+
+
+if __name__ == "__main__":
+    main()
