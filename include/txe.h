@@ -578,6 +578,24 @@ int txe_adam_step(int n_tensors, float* const* params, const float* const* grads
                   float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1, double beta2, double eps,
                   double weight_decay, long long step, void* stream);
 
+/* txe_adam_step behind a guard: two DEVICE scalars that the launches of this step read once per workgroup, before any per-element
+ * work, and never write.  Either may be NULL; both NULL is txe_adam_step itself (the same launches, the same bits).
+ *   first_bad   *first_bad >= 0: every workgroup returns before its first load -- params, exp_avg, exp_avg_sq and max_exp_avg_sq are
+ *               left untouched.  The host still counts the step; optim.Adam.discount_frozen_steps takes such steps back.
+ *   gnorm2      the squared global L2 norm of the gradients.  coef64 = max_grad_norm / (sqrt(*gnorm2) + 1e-6) in fp64
+ *               (torch.nn.utils.clip_grad_norm_'s formula), coef = coef64 < 1 ? (float)coef64 : 1, and every gradient element is
+ *               multiplied by coef before the weight-decay term (g * 1.0f is g: an inactive clip changes no bit).  `grads` are not
+ *               written.  max_grad_norm is ignored when gnorm2 is NULL; otherwise it must be finite and > 0 (TXE_ERR_ARG, nothing
+ *               launched).  A *gnorm2 that is not finite, met without a first_bad pointer, goes through the formula as written: NaN
+ *               gives coef 1, +Inf gives coef 0 (and NaN in the elements that are Inf); no parity with torch is claimed for that case.
+ * ORDERING CONTRACT: both scalars must have been written by work enqueued EARLIER ON THE SAME `stream` (txe_step_log's first_bad word
+ * and its gnorm2_log[step] slot are; every launch of one step reads the same two values).  A value written from another stream or by
+ * the host without an ordering against `stream` may or may not be seen. */
+int txe_adam_step_guarded(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, long long step, const double* gnorm2,
+                          const long long* first_bad, double max_grad_norm, void* stream);
+
 /* The per-step device log of the training loop (what trainer.py:63-65 reads back with `loss.item()` every step; csrc/txe_steplog.hip):
  * one call per step, enqueued between `loss.backward()` and `optimizer.step()`; nothing returns to the host.
  *   loss_log[step]   = loss[0]                                     (fp32 device scalar)

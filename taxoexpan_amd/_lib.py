@@ -129,6 +129,7 @@ SIGNATURES = {
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),
     "txe_info_nce": (I, [P, L, I, I, P, P, P, L, P]),
     "txe_adam_step": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P]),
+    "txe_adam_step_guarded": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P, P, D, P]),
     "txe_step_log_ws_bytes": (SZ, [I]),
     "txe_step_log": (I, [P, I, P, P, L, L, P, P, P, P, P, SZ, P]),
     "txe_dropout_uniform_host": (F, [U64, U64]),

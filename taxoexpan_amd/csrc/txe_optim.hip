@@ -27,18 +27,31 @@ struct AdamScalars {
     float one_minus_b1, b2, one_minus_b2, eps, wd, step_size, bc2_sqrt;
 };
 
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float& vm, bool ams, const AdamScalars& c) {
+// The guard of one step (txe_adam_step_guarded): two device scalars that work enqueued EARLIER ON THE SAME STREAM has written (the
+// step log's first_bad word and its gnorm2 slot of this step) and the host's clip threshold.  Either pointer may be null.  Both are
+// only read -- one wave-uniform load each, once per workgroup, before any per-element work.
+struct AdamGuard {
+    const long long* first_bad;     // *first_bad >= 0: the whole step is skipped (no load, no store)
+    const double* gnorm2;           // the squared global L2 norm of the gradients: every g is scaled by min(1, max_norm / (sqrt(.) + 1e-6))
+    double max_grad_norm;
+};
+
+// The products that hipcc contracts under its default -ffp-contract=fast are spelled as fmaf here, so that the arithmetic is a property
+// of the source (optim.host_guarded_adam restates it operation for operation): m = fma(1-b1, g - m, m), v = fma(g, (1-b2) g, b2 v).
+template <bool GUARD>
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float& vm, bool ams, const AdamScalars& c, float coef) {
+    if (GUARD) g *= coef;                                   // coef == 1: g unchanged, bit for bit
     g = fmaf(c.wd, p, g);                                   // wd == 0: g unchanged
-    m = m + (g - m) * c.one_minus_b1;                       // lerp(m, g, 1 - beta1)
-    v = c.b2 * v + c.one_minus_b2 * g * g;
+    m = fmaf(c.one_minus_b1, g - m, m);                     // lerp(m, g, 1 - beta1)
+    v = fmaf(g, c.one_minus_b2 * g, c.b2 * v);
     float d;
     if (ams) { vm = fmaxf(vm, v); d = sqrtf(vm) / c.bc2_sqrt + c.eps; }
     else d = sqrtf(v) / c.bc2_sqrt + c.eps;
     p -= c.step_size * m / d;
 }
 
-template <bool AMS>
-__global__ __launch_bounds__(256) void adam_kernel(AdamTable T, AdamScalars c) {
+template <bool AMS, bool GUARD>
+__device__ __forceinline__ void adam_chunk(const AdamTable& T, const AdamScalars& c, float coef) {
     int t = 0;
 #pragma unroll 1
     while (t + 1 < T.count && (int)blockIdx.x >= T.first_chunk[t + 1]) ++t;
@@ -57,10 +70,10 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamTable T, AdamScalars c) {
         float4 m = *reinterpret_cast<const float4*>(M + i0);
         float4 v = *reinterpret_cast<const float4*>(V + i0);
         float4 x = *reinterpret_cast<const float4*>(X + i0);
-        adam_one(p.x, g.x, m.x, v.x, x.x, AMS, c);
-        adam_one(p.y, g.y, m.y, v.y, x.y, AMS, c);
-        adam_one(p.z, g.z, m.z, v.z, x.z, AMS, c);
-        adam_one(p.w, g.w, m.w, v.w, x.w, AMS, c);
+        adam_one<GUARD>(p.x, g.x, m.x, v.x, x.x, AMS, c, coef);
+        adam_one<GUARD>(p.y, g.y, m.y, v.y, x.y, AMS, c, coef);
+        adam_one<GUARD>(p.z, g.z, m.z, v.z, x.z, AMS, c, coef);
+        adam_one<GUARD>(p.w, g.w, m.w, v.w, x.w, AMS, c, coef);
         *reinterpret_cast<float4*>(P + i0) = p;
         *reinterpret_cast<float4*>(M + i0) = m;
         *reinterpret_cast<float4*>(V + i0) = v;
@@ -68,26 +81,42 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamTable T, AdamScalars c) {
     } else {
         for (long long i = i0; i < n && i < i0 + 4; ++i) {
             float p = P[i], m = M[i], v = V[i], x = AMS ? X[i] : 0.f;
-            adam_one(p, G[i], m, v, x, AMS, c);
+            adam_one<GUARD>(p, G[i], m, v, x, AMS, c, coef);
             P[i] = p; M[i] = m; V[i] = v;
             if (AMS) X[i] = x;
         }
     }
 }
 
+template <bool AMS>
+__global__ __launch_bounds__(256) void adam_kernel(AdamTable T, AdamScalars c) {
+    adam_chunk<AMS, false>(T, c, 1.f);
+}
+
+// adam_kernel behind the guard.  The coefficient is clip_grad_norm_'s, formed in fp64: max_norm / (norm + 1e-6), used when below 1.  A
+// norm that is not finite, met without a first_bad pointer, goes through the same formula: NaN compares false and leaves the
+// coefficient at 1, +Inf gives 0 (and 0 * Inf = NaN in the elements that are Inf) -- no parity with torch is claimed there.
+template <bool AMS>
+__global__ __launch_bounds__(256) void adam_guarded_kernel(AdamTable T, AdamScalars c, AdamGuard G) {
+    if (G.first_bad && G.first_bad[0] >= 0) return;         // frozen: p, m, v and vmax stay as they are
+    float coef = 1.f;
+    if (G.gnorm2) {
+        const double coef64 = G.max_grad_norm / (sqrt(G.gnorm2[0]) + 1e-6);
+        coef = coef64 < 1.0 ? (float)coef64 : 1.0f;
+    }
+    adam_chunk<AMS, true>(T, c, coef);
+}
+
 }  // namespace txe
 
 using namespace txe;
 
-extern "C" {
+namespace {
 
-// One optimizer step over n_tensors parameter tensors (HOST arrays of DEVICE pointers; numel[t] elements each, fp32, dense).
-//   g' = g + weight_decay p;  m = lerp(m, g', 1-beta1);  v = beta2 v + (1-beta2) g'^2;  [vmax = max(vmax, v)]
-//   p -= lr / (1 - beta1^step) * m / (sqrt(vmax or v) / sqrt(1 - beta2^step) + eps)
-// `step` is the 1-based count of THIS update (shared by the tensors of the call); max_exp_avg_sq == NULL selects plain Adam.
-int txe_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                  float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1, double beta2, double eps,
-                  double weight_decay, long long step, void* stream) {
+// txe_adam_step and txe_adam_step_guarded; guard == nullptr launches adam_kernel, anything else adam_guarded_kernel over the same tables
+int adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+              float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay,
+              long long step, const AdamGuard* guard, void* stream) {
     if (n_tensors < 0 || step < 1 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel))) return TXE_ERR_ARG;
     if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return TXE_ERR_ARG;
     AdamScalars c;
@@ -120,12 +149,47 @@ int txe_adam_step(int n_tensors, float* const* params, const float* const* grads
         if (T.count == 0) continue;
         T.first_chunk[T.count] = (int)chunks;
         for (int k = T.count; k < ADAM_MAX_T; ++k) { T.p[k] = nullptr; T.g[k] = nullptr; T.m[k] = nullptr; T.v[k] = nullptr; T.vmax[k] = nullptr; T.n[k] = 0; T.first_chunk[k + 1] = (int)chunks; }
-        ProfScope prof(ams ? "adam_kernel<true>" : "adam_kernel<false>", (hipStream_t)stream, 4.0 * elems * (ams ? 9 : 7), 1);   // p, g, m, v [, vmax] read; all but g written
-        if (ams) hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, T, c);
-        else hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, T, c);
-        TXE_CHECK_LAUNCH();
+        const double bytes = 4.0 * elems * (ams ? 9 : 7);          // p, g, m, v [, vmax] read; all but g written (a frozen step moves none of it)
+        if (guard) {
+            ProfScope prof(ams ? "adam_guarded_kernel<true>" : "adam_guarded_kernel<false>", (hipStream_t)stream, bytes + 16.0, 1);
+            if (ams) hipLaunchKernelGGL(adam_guarded_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, T, c, *guard);
+            else hipLaunchKernelGGL(adam_guarded_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, T, c, *guard);
+            TXE_CHECK_LAUNCH();
+        } else {
+            ProfScope prof(ams ? "adam_kernel<true>" : "adam_kernel<false>", (hipStream_t)stream, bytes, 1);
+            if (ams) hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, T, c);
+            else hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, T, c);
+            TXE_CHECK_LAUNCH();
+        }
     }
     return TXE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One optimizer step over n_tensors parameter tensors (HOST arrays of DEVICE pointers; numel[t] elements each, fp32, dense).
+//   g' = g + weight_decay p;  m = lerp(m, g', 1-beta1);  v = beta2 v + (1-beta2) g'^2;  [vmax = max(vmax, v)]
+//   p -= lr / (1 - beta1^step) * m / (sqrt(vmax or v) / sqrt(1 - beta2^step) + eps)
+// `step` is the 1-based count of THIS update (shared by the tensors of the call); max_exp_avg_sq == NULL selects plain Adam.
+int txe_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                  float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, long long step, void* stream) {
+    return adam_step(n_tensors, params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, step, nullptr,
+                     stream);
+}
+
+// txe_adam_step behind two DEVICE scalars written by earlier work on the same stream (include/txe.h): *first_bad >= 0 skips the step,
+// g is scaled by min(1, max_grad_norm / (sqrt(*gnorm2) + 1e-6)).  Both NULL: txe_adam_step itself, the same launches.
+int txe_adam_step_guarded(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                          float* const* max_exp_avg_sq, const long long* numel, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, long long step, const double* gnorm2, const long long* first_bad, double max_grad_norm,
+                          void* stream) {
+    if (gnorm2 && !(isfinite(max_grad_norm) && max_grad_norm > 0.0)) return TXE_ERR_ARG;
+    const AdamGuard guard = {first_bad, gnorm2, gnorm2 ? max_grad_norm : 0.0};
+    return adam_step(n_tensors, params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, step,
+                     (gnorm2 || first_bad) ? &guard : nullptr, stream);
 }
 
 }  // extern "C"

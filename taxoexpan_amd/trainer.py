@@ -3,12 +3,15 @@ _resume_checkpoint (base/base_trainer.py:59-176) -- in the style of evaluate.val
 
     StepLog       the device log of an epoch: per step the loss and the gradients' L2 norm, the running loss sum and the first step
                   whose loss or gradients were not finite, written by ONE launch per step (txe_step_log, csrc/txe_steplog.hip) between
-                  `loss.backward()` and `optimizer.step()`; read back once per epoch
+                  `loss.backward()` and `optimizer.step()`; read back once per epoch.  guard() hands the optimizer launch of the step
+                  the addresses of that norm and of that word (optim.Adam.step(guard=...)): clipping by the global norm and freezing
+                  at the first non-finite step, with no launch, pass over the gradients or read-back added
     train_epoch   trainer.py:41-77 without `label.sum()` (:53), `loss.item()` (:64-65) or any other read-back inside the loop
     fit           base_trainer.py:59-107 + trainer.py:79-94: epochs of train_epoch + evaluate.validate, the LR schedule, monitoring,
                   early stopping, checkpoints with the reference's keys, resume -- and one addition: a diverged epoch ends the run
     host_step_log the numpy restatement of txe_step_log (its written definition; the CPU tests use it)
 """
+import inspect
 import math
 import os
 import warnings
@@ -107,6 +110,17 @@ class StepLog:
                       _lib.stream_ptr())
         self.n_recorded = s + 1
 
+    def guard(self, step=None, gnorm2=True, first_bad=True):
+        """the optim.StepGuard of a recorded step (default: the one recorded last) for the optimizer launch that follows record() on the
+        same stream: gnorm2 = the address of that step's slot in the log's fp64 buffer, first_bad = the address of the log's word
+        (either left out on request).  No device memory, no launch: two addresses and a reference to the buffer."""
+        from .optim import StepGuard
+        s = self.n_recorded - 1 if step is None else int(step)
+        if not 0 <= s < self.n_recorded:
+            raise IndexError(f"StepLog.guard: step {s} has not been recorded ({self.n_recorded} steps so far)")
+        return StepGuard(gnorm2=self._gnorm2.data_ptr() + 8 * s if gnorm2 else None,
+                         first_bad=self._first_bad.data_ptr() if first_bad else None, keep=(self._buf,))
+
     def read(self):
         """the epoch's one read-back: dict(loss fp32 [n], grad_norm fp64 [n], loss_sum, n_steps, first_nonfinite (-1: none))"""
         host = self._buf.cpu().numpy()
@@ -125,7 +139,7 @@ def _is_info_nce(loss_fn):
     return getattr(loss_fn, "__name__", "").startswith("info_nce")        # trainer.py:20 tests the config's loss NAME the same way
 
 
-def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None):
+def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None, max_grad_norm=None, freeze_on_nonfinite=False):
     """trainer.py:41-77 on the device: model.train(), then per batch zero_grad, forward, loss, backward, ONE txe_step_log launch,
     optimizer.step() -- no .item(), .cpu() or synchronize between the first batch and the last (what `loader` does to build a batch is
     its own business), then one read-back of the log.
@@ -138,7 +152,16 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
     one of len(loader) steps.
     Returns dict(loss = the fp64 sum of the fp32 step losses / n_batches -- trainer.py:76's total_loss / len(data_loader) --, n_batches,
     losses fp32 [n_batches], grad_norms fp64 [n_batches], first_nonfinite = the first step with a non-finite loss or gradient, or -1).
-    It never stops early: that would take a read-back per step."""
+    It never stops early: that would take a read-back per step.
+    max_grad_norm / freeze_on_nonfinite (off by default: then the loop is launch for launch what it was): the optimizer launch of every
+    step reads what the log launch before it wrote -- `optimizer.step(guard=log.guard())`, which optim.Adam takes and an optimizer whose
+    step() has no `guard` does not (ValueError before the first step).
+      max_grad_norm c: the gradients enter the update scaled by min(1, c / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s rule, with
+        the norm the log has just formed (a group's own Adam(max_grad_norm=...) counts when c is None).  `.grad` is not rewritten and the
+        returned grad_norms stay the norms BEFORE clipping -- what clip_grad_norm_ returns.
+      freeze_on_nonfinite: from the first step s whose loss or gradients are not finite on, the optimizer launches return without a load
+        or a store; after the read-back optimizer.discount_frozen_steps(n_batches - s) takes the skipped steps off the step counts.
+        Model and optimizer are then exactly as after step s - 1 (the forward and backward passes of the later steps still ran)."""
     if loss_fn is None:
         from .loss import info_nce_loss as loss_fn
     info_nce = _is_info_nce(loss_fn)
@@ -149,6 +172,13 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         group_size = 1 + int(k)
     if info_nce and int(group_size) < 1:
         raise ValueError(f"group_size must be positive, got {group_size}")
+    from .optim import _checked_max_norm
+    max_grad_norm = _checked_max_norm(max_grad_norm)
+    clip = max_grad_norm is not None or any(g.get("max_grad_norm") is not None for g in optimizer.param_groups)
+    guarded = clip or bool(freeze_on_nonfinite)
+    if guarded and "guard" not in inspect.signature(optimizer.step).parameters:
+        raise ValueError(f"max_grad_norm / freeze_on_nonfinite need an optimizer whose step() takes `guard` (taxoexpan_amd.optim.Adam); "
+                         f"{type(optimizer).__name__}.step does not")
     params = list(model.parameters())
     dev = params[0].device
     if log is None:
@@ -178,26 +208,37 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
             loss = loss_fn(prediction, label)
         loss.backward()                                                # trainer.py:60
         log.record(loss, params)
-        optimizer.step()                                               # trainer.py:61
+        if guarded:                                                    # only what was asked for is passed
+            guard = log.guard(gnorm2=clip, first_bad=bool(freeze_on_nonfinite))
+            guard.max_grad_norm = max_grad_norm
+            optimizer.step(guard=guard)
+        else:
+            optimizer.step()                                           # trainer.py:61
         n_batches += 1
     rec = log.read()
+    if freeze_on_nonfinite and rec["first_nonfinite"] >= 0:
+        optimizer.discount_frozen_steps(n_batches - rec["first_nonfinite"])
     return dict(loss=rec["loss_sum"] / n_batches if n_batches else float("nan"), n_batches=n_batches, losses=rec["loss"],
                 grad_norms=rec["grad_norm"], first_nonfinite=rec["first_nonfinite"])
 
 
 class TrainingDiverged(RuntimeError):
-    """fit() met an epoch whose loss or gradients were not finite: .epoch (1-based), .step (0-based within the epoch) and .logs (the
-    per-epoch logs up to and including that epoch)"""
+    """fit() met an epoch whose loss or gradients were not finite: .epoch (1-based), .step (0-based within the epoch), .logs (the
+    per-epoch logs up to and including that epoch) and .checkpoint (the path of the last_finite.pth that fit wrote, or None)"""
 
-    def __init__(self, epoch, step, logs=()):
+    def __init__(self, epoch, step, logs=(), checkpoint=None):
         super().__init__(f"training diverged: non-finite loss or gradient at step {step} of epoch {epoch}")
-        self.epoch, self.step, self.logs = epoch, step, list(logs)
+        self.epoch, self.step, self.logs, self.checkpoint = epoch, step, list(logs), checkpoint
+
+
+def _checkpoint_state(model, optimizer, epoch, monitor_best, config):
+    return {"arch": type(model).__name__, "epoch": epoch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
+            "monitor_best": monitor_best, "config": config}
 
 
 def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, save_best):
     """base_trainer.py:126-149"""
-    state = {"arch": type(model).__name__, "epoch": epoch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
-             "monitor_best": monitor_best, "config": config}
+    state = _checkpoint_state(model, optimizer, epoch, monitor_best, config)
     os.makedirs(str(save_dir), exist_ok=True)
     torch.save(state, os.path.join(str(save_dir), f"checkpoint-epoch{epoch}.pth"))
     if save_best:
@@ -206,7 +247,7 @@ def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, sa
 
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
-        loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None):
+        loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -224,6 +265,10 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     so both checks are dropped: the optimizer state is always loaded, and a mismatch surfaces as load_state_dict's own error.
     The one addition: an epoch whose step log shows a non-finite loss or gradient ends the run -- no validation, no scheduler step and no
     checkpoint for it -- with TrainingDiverged(epoch, step).  train_epoch itself runs the epoch to its end (see there).
+    max_grad_norm / freeze_on_nonfinite go to train_epoch (see there; they are passed only when set).  With freeze_on_nonfinite the
+    diverged epoch left model and optimizer as they were after its last finite step, and with a save_dir that state is written to
+    last_finite.pth before TrainingDiverged is raised (.checkpoint names it): the keys of every other checkpoint, `epoch` = the epoch
+    completed before the diverged one, so that `resume=` starts the diverged epoch again.
     loss_fn / group_size go to train_epoch.  train_epoch_fn / validate_fn replace trainer.train_epoch / evaluate.validate (same call
     signatures); the loop control here makes no GPU call of its own.  Returns the list of per-epoch logs."""
     if train_epoch_fn is None:
@@ -254,13 +299,23 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
         optimizer.load_state_dict(ckpt["optimizer"])
     logs = []
     not_improved_count = 0
+    guard_args = {}
+    if max_grad_norm is not None:
+        guard_args["max_grad_norm"] = max_grad_norm
+    if freeze_on_nonfinite:
+        guard_args["freeze_on_nonfinite"] = True
     for epoch in range(start_epoch, epochs + 1):
-        result = train_epoch_fn(model, train_loader, optimizer, loss_fn=loss_fn, group_size=group_size)
+        result = train_epoch_fn(model, train_loader, optimizer, loss_fn=loss_fn, group_size=group_size, **guard_args)
         log = {"epoch": epoch}
         log.update(result)
         logs.append(log)
         if result.get("first_nonfinite", -1) >= 0:
-            raise TrainingDiverged(epoch, int(result["first_nonfinite"]), logs)
+            checkpoint = None
+            if freeze_on_nonfinite and save_dir is not None:
+                os.makedirs(str(save_dir), exist_ok=True)
+                checkpoint = os.path.join(str(save_dir), "last_finite.pth")
+                torch.save(_checkpoint_state(model, optimizer, epoch - 1, mnt_best, config), checkpoint)
+            raise TrainingDiverged(epoch, int(result["first_nonfinite"]), logs, checkpoint)
         if valid_loader is not None:                                   # trainer.py:80-82, base_trainer.py:71-72
             val = validate_fn(model, valid_loader, metrics=metrics, larger_is_better=larger_is_better)
             log.update({"val_" + name: v for name, v in zip(metrics, val["val_metrics"])})

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """per-kernel HIP-event timings of the bench step (bench.profile_step over the resident batches), top N -- a quick look between builds
-usage: python tools/kt_quick.py [workload] [N]"""
+usage: python tools/kt_quick.py [workload] [N]
+TXE_GUARDED_ADAM=1: the optimizer launch goes through txe_adam_step_guarded behind a guard that never acts (norm 0, first_bad -1: the
+same bits) -- adam_guarded_kernel<true> beside adam_kernel<true> of a run without the switch"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -26,6 +28,12 @@ tax = syn.make_named_taxonomy({"pgat2": "mag_full", "semeval": "semeval_noun"}.g
 torch.manual_seed(47)
 model = bench.make_model(wl, dev)
 opt = Adam(model.parameters(), lr=bench.LR, weight_decay=0, amsgrad=True)
+if os.environ.get("TXE_GUARDED_ADAM", "0") == "1":
+    from taxoexpan_amd.optim import StepGuard
+    _norm, _bad = torch.zeros(1, dtype=torch.float64, device=dev), torch.full((1,), -1, dtype=torch.int64, device=dev)
+    _guard = StepGuard(gnorm2=_norm.data_ptr(), first_bad=_bad.data_ptr(), max_grad_norm=1.0, keep=(_norm, _bad))
+    _plain_step = opt.step
+    opt.step = lambda closure=None: _plain_step(closure, guard=_guard)
 batches = bench.build_batches(tax, 4, seed0=1000, device=dev)
 target = torch.zeros(bench.N_QUERIES, dtype=torch.long, device=dev)
 for i in range(300):

@@ -6,8 +6,13 @@ bench.make_model("pgat"), optim.Adam(amsgrad) at bench.LR), two legs alternating
   (b) the reference-style loop: `label.sum()` read back to reshape the scores, a torch.zeros target, `loss.item()` twice per step.
 Prints per leg and epoch the wall time and the time per step, then the step-log kernel's own average (and the Adam kernel's, for scale)
 from the library's profile hooks over --profile-steps steps of leg (a).
+--guard adds a third alternating leg
+  (g) trainer.train_epoch(max_grad_norm=1e30, freeze_on_nonfinite=True): clip and freeze on, the clip never active (the same bits);
+then profiles (a) and (g) twice each, alternating -- adam_kernel<true> beside adam_guarded_kernel<true>, and the library's launches per
+step of both legs -- and last times the frozen tail of a diverged epoch: every loss times inf, so every optimizer launch of leg (g)
+returns at once (parameters and moments are checked to be untouched).
 
-    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50]"""
+    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50] [--guard]"""
 import argparse
 import ctypes
 import os
@@ -82,12 +87,19 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
-def profiled_kernels(model, loader, opt, steps):
+GUARD = dict(max_grad_norm=1e30, freeze_on_nonfinite=True)
+
+
+def info_nce_times_inf(output, target=None):
+    return info_nce_loss(output, target) * float("inf")
+
+
+def profiled_kernels(model, loader, opt, steps, **kw):
     """average duration by kernel name over `steps` steps of train_epoch (HIP events around every launch of the library)"""
     lib = _lib.load()
     lib.txe_profile_reset()
     lib.txe_profile_enable(1)
-    train_epoch(model, _First(loader, steps), opt)
+    train_epoch(model, _First(loader, steps), opt, **kw)
     torch.cuda.synchronize()
     lib.txe_profile_enable(0)
     buf = ctypes.create_string_buffer(64)
@@ -100,10 +112,37 @@ def profiled_kernels(model, loader, opt, steps):
     return {k: (float(np.mean([u for u, _ in v])), float(np.median([u for u, _ in v])), len(v), v[0][1]) for k, v in by.items()}
 
 
+def guard_report(model, loader, opt, steps, g_s):
+    """adam_kernel<true> of leg (a) beside adam_guarded_kernel<true> of leg (g), two alternating rounds; then the frozen tail"""
+    print(f"(g) {min(g_s):.3f}-{max(g_s):.3f} ms/step (median {float(np.median(g_s)):.3f})")
+    for r in range(2):
+        for leg, kw, name in (("a", {}, "adam_kernel<true>"), ("g", GUARD, "adam_guarded_kernel<true>")):
+            prof = profiled_kernels(model, loader, opt, steps, **kw)
+            mean, med, n, work = prof[name]
+            launches = sum(v[2] for v in prof.values()) / steps
+            print(f"round {r} leg ({leg}): {name}: mean {mean:.2f} us, median {med:.2f} us over {n} launches = {work / (1e-6 * med) / 1e12:.2f} TB/s "
+                  f"at the median; {launches:.1f} library launches per step", flush=True)
+    before = [p.detach().clone() for p in model.parameters()]
+    moments = [opt.state[p]["exp_avg_sq"].clone() for p in model.parameters()]
+    counts = [float(opt.state[p]["step"]) for p in model.parameters()]
+    n = min(60, len(loader))
+    train_epoch(model, _First(loader, 10), opt, loss_fn=info_nce_times_inf, group_size=1 + K, **GUARD)       # (first calls of the non-finite route)
+    t, r = timed(lambda: train_epoch(model, _First(loader, n), opt, loss_fn=info_nce_times_inf, group_size=1 + K, **GUARD))
+    prof = profiled_kernels(model, loader, opt, min(steps, n), loss_fn=info_nce_times_inf, group_size=1 + K, **GUARD)
+    assert r["first_nonfinite"] == 0 and all(torch.equal(p, q) for p, q in zip(model.parameters(), before))
+    assert all(torch.equal(opt.state[p]["exp_avg_sq"], q) for p, q in zip(model.parameters(), moments))
+    assert [float(opt.state[p]["step"]) for p in model.parameters()] == counts
+    mean, med, k, _work = prof["adam_guarded_kernel<true>"]
+    print(f"frozen tail: {n} steps of a diverged epoch (every loss inf, freeze on): {1e3 * t / n:.3f} ms/step; the frozen "
+          f"adam_guarded_kernel<true>: mean {mean:.2f} us, median {med:.2f} us over {k} launches (no traffic); parameters, moments and step "
+          f"counts untouched", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=50)
+    ap.add_argument("--guard", action="store_true", help="add leg (g): clip (never active) and freeze on; see the module docstring")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "train_epoch_timing.py times the MI355X: no GPU found"
     dev = torch.device("cuda:0")
@@ -119,21 +158,30 @@ def main():
     print(f"{len(loader)} steps per epoch, {BS} queries x {1 + K} egonets per step, {n_grad} gradient elements per step", flush=True)
     train_epoch(model, _First(loader, 30), opt)              # warm-up of both legs (first-call costs, allocator)
     reference_style_epoch(model, _First(loader, 30), opt, dev)
-    a_s, b_s = [], []
+    if args.guard:
+        train_epoch(model, _First(loader, 30), opt, **GUARD)
+    a_s, b_s, g_s = [], [], []
     for e in range(args.epochs):
         ta, ra = timed(lambda: train_epoch(model, loader, opt))
+        if args.guard:
+            tg, rg = timed(lambda: train_epoch(model, loader, opt, **GUARD))
+            assert rg["first_nonfinite"] == -1, "the model diverged: the timing is void"
+            g_s.append(1e3 * tg / rg["n_batches"])
         tb, (lb, nb) = timed(lambda: reference_style_epoch(model, loader, opt, dev))
         assert ra["first_nonfinite"] == -1 and np.isfinite(lb), "the model diverged: the timing is void"
         a_s.append(1e3 * ta / ra["n_batches"])
         b_s.append(1e3 * tb / nb)
         print(f"epoch {e}: (a) train_epoch {1e3 * ta:.1f} ms = {a_s[-1]:.3f} ms/step (loss {ra['loss']:.3f}, |g| {ra['grad_norms'][-1]:.3f}) | "
-              f"(b) reference-style loop {1e3 * tb:.1f} ms = {b_s[-1]:.3f} ms/step (loss {lb:.3f})", flush=True)
+              + (f"(g) guarded {1e3 * tg:.1f} ms = {g_s[-1]:.3f} ms/step | " if args.guard else "")
+              + f"(b) reference-style loop {1e3 * tb:.1f} ms = {b_s[-1]:.3f} ms/step (loss {lb:.3f})", flush=True)
     prof = profiled_kernels(model, loader, opt, args.profile_steps)
     for name in ("step_log_kernel", "adam_kernel<true>"):
         if name in prof:
             mean, med, n, work = prof[name]
             print(f"{name}: mean {mean:.2f} us, median {med:.2f} us over {n} launches; {work / 1e6:.2f} MB compulsory per launch "
                   f"= {work / (1e-6 * med) / 1e12:.2f} TB/s at the median")
+    if args.guard:
+        guard_report(model, loader, opt, args.profile_steps, g_s)
     print(f"summary: (a) {min(a_s):.3f}-{max(a_s):.3f} ms/step (median {float(np.median(a_s)):.3f}), (b) {min(b_s):.3f}-{max(b_s):.3f} ms/step "
           f"(median {float(np.median(b_s)):.3f}); (a) <= (b) in every epoch: {all(a <= b for a, b in zip(a_s, b_s))}")
 
