@@ -898,10 +898,14 @@ int txe_gat_collapse_fwd(const struct txe_graph_batch* batch, const struct txe_g
         !alpha || !coef || !wsum || !gid || !Z || !ws || (pw && !pos))
         return TXE_ERR_ARG;
     if (feat_drop_p < 0.f || feat_drop_p >= 1.f || attn_drop_p < 0.f || attn_drop_p >= 1.f) return TXE_ERR_ARG;
+    // e_part rides in the chunked Z sweep only (txe_gat_collapse_e_tiles == 0 otherwise) and needs Tf and zrow: said before any launch
+    if (e_part && (!cl_zsum_chunked(n_nodes, G) || !Tf || !zrow)) return TXE_ERR_ARG;
     const int Kt = Kh + Pd, Kp = round_up(Kt, 32);
     CollapseWs p = plan_collapse_ws(ws, n_nodes, n_edges, G, Kp, D, Pd, 0);
     if (ws_bytes < p.total) return TXE_ERR_WORKSPACE;
     if (G == 0) return TXE_OK;
+    // (the bf16 route for hg is the caller's choice, not the buffer's size: a buffer too small for it is an error, before any launch)
+    if (hg && (flags & TXE_FOLD_HG_SPLIT) && ws_bytes < p.total + collapse_split_bytes(G, D, Kt)) return TXE_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const unsigned* mk = (mask && feat_drop_p > 0.f) ? mask : nullptr;
     const int mask_ld = (Kt + 31) / 32;
@@ -928,7 +932,6 @@ int txe_gat_collapse_fwd(const struct txe_graph_batch* batch, const struct txe_g
     if (rc_z) return rc_z;
     if (!hg) return TXE_OK;          // (the caller folds hg = Z W^T into what consumes it: txe_bilinear_folded_*)
     if (G > 0 && (flags & TXE_FOLD_HG_SPLIT)) {
-        if (ws_bytes < p.total + collapse_split_bytes(G, D, Kt)) return TXE_ERR_WORKSPACE;            // (the route is the caller's choice, not the buffer's size)
         // hg = Z W^T on the bf16 matrix pipe (txe_gemm_split.h): Z and the weight rows packed behind the workspace's own regions
         char* sw = (char*)ws + p.total;
         const int Kc = round_up(Kt, 16);
