@@ -569,6 +569,36 @@ int txe_copy_stream(const void* src, void* dst, long long n_bytes, void* stream)
 int txe_info_nce(const float* x, long long ld_x, int B, int Cc, const long long* target, float* loss, float* d_x, long long ld_dx,
                  void* stream);
 
+/* ---- the reference's other training losses on a labelled score vector (csrc/txe_pairloss.hip): x [B] fp32, labels [B] int32
+ * (label_bytes 4) or int64 (8), read as they are.  An entry is a POSITIVE iff its label is 1.  Each call leaves the sum-reduced loss in
+ * loss[0] and its gradient in d_x [B]; no host synchronisation, no floating-point atomics: two calls on the same input give the same
+ * bits.  TXE_ERR_ARG (before any device work, nothing written): a NULL pointer, B < 1, label_bytes not 4 or 8, a non-finite beta /
+ * margin; TXE_ERR_WORKSPACE: ws_bytes below txe_margin_rank_loss_ws_bytes(B).
+ *
+ * model/loss.py:21-29 bce_loss = F.binary_cross_entropy_with_logits(output.squeeze(), 1.0 - target.float(), reduction="sum") (the target
+ * is inverted: the score is an energy, loss.py:26):  loss = sum over positives of softplus(x_i) + sum over every other entry of
+ * softplus(-x_i), softplus(z) = max(z, 0) + log1p(exp(-|z|)) (finite for x = +-1e4);  d_x[i] = sigmoid(x_i) - [i is no positive].
+ * The contract is labels in {0, 1}.  One launch. */
+int txe_bce_loss(const float* x, const void* labels, int label_bytes, int B, float* loss, float* d_x, void* stream);
+/* model/loss.py:12-19 square_exp_loss = (output[target==1]**2).sum() + beta * torch.exp(-1.0*output[target==0]).sum():
+ * loss = sum over positives of x_i^2 + beta * sum over label == 0 EXACTLY of exp(-x_i) (any other label contributes nothing);
+ * d_x[i] = 2 x_i for a positive, -beta exp(-x_i) for label 0, else 0.  exp overflows to +Inf / -Inf in fp32 as torch's does.
+ * One launch. */
+int txe_square_exp_loss(const float* x, const void* labels, int label_bytes, int B, float beta, float* loss, float* d_x, void* stream);
+/* model/loss.py:31-50 margin_rank_loss (label.cpu(), a regex over the label bytes, itertools.product, then
+ * F.margin_ranking_loss(pos, neg, -1, margin, reduction="sum")) without the read-back.  Groups start at index 0 and at every i with
+ * label[i-1] == 0 and label[i] == 1 (txe_group_rank's rule); within a group every (positive p, negative n) pair -- a negative is every
+ * entry that is no positive -- contributes max(0, (x_p - x_n) + margin), the condition evaluated in fp32 exactly as written (one
+ * subtraction, one addition).  d_x[p] = +(negatives of its group with (x_p - x_n) + margin > 0), d_x[n] = -(positives of its group with
+ * the same): integer-valued, bit-equal to torch autograd's.  NaN never compares true (no gradient; the loss is NaN, as torch's clamp
+ * gives); a group without negatives or without positives contributes nothing.  On label vectors whose every group is >= 1 ones followed
+ * by >= 1 zeros this is the reference's pair list; on a vector that begins with a zero the reference's bookkeeping drops the pairs
+ * (loss 0) and this follows the group rule.  Five enqueued steps on `stream` (flags, one 64-bit scan, index, pairs, finish): positives'
+ * counts are added with integer atomics, per-tile loss partials are combined in a fixed order.  ws is sized from B alone. */
+size_t txe_margin_rank_loss_ws_bytes(int B);
+int txe_margin_rank_loss(const float* x, const void* labels, int label_bytes, int B, float margin, float* loss, float* d_x, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* trainer.py:61 `self.optimizer.step()` for torch.optim.Adam (config.mag.json:66-73: lr 1e-3, weight_decay 0, amsgrad true): the whole
  * parameter set in one launch.  params / grads / exp_avg / exp_avg_sq / max_exp_avg_sq are HOST arrays of n_tensors DEVICE pointers
  * (dense fp32, numel[t] elements); max_exp_avg_sq == NULL selects plain Adam; `step` >= 1 is the count of this update.

@@ -128,6 +128,10 @@ SIGNATURES = {
     "txe_select_k_ws_bytes": (SZ, [I, I]),
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),
     "txe_info_nce": (I, [P, L, I, I, P, P, P, L, P]),
+    "txe_bce_loss": (I, [P, P, I, I, P, P, P]),
+    "txe_square_exp_loss": (I, [P, P, I, I, F, P, P, P]),
+    "txe_margin_rank_loss_ws_bytes": (SZ, [I]),
+    "txe_margin_rank_loss": (I, [P, P, I, I, F, P, P, P, SZ, P]),
     "txe_adam_step": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P]),
     "txe_adam_step_guarded": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P, P, D, P]),
     "txe_step_log_ws_bytes": (SZ, [I]),

@@ -12,41 +12,9 @@
 //   index: pos_off[g] = positives before group g, pos_elem[p] = the entry of positive p, ranks[p] = 1, counts = {n_groups, n_pos}.
 //   rank:  one wave per 64 consecutive entries; for every group that meets the tile and every positive of that group, the wave counts
 //          its own better negatives (ballot) and adds them to the positive's rank.  Work = sum over groups of P_g x (tiles of the group).
-#include "txe_common.h"
-#include <hipcub/hipcub.hpp>
+#include "txe_groups.h"      // group_flags_kernel, the scan, group_index_kernel: shared with txe_pairloss.hip
 
 namespace txe {
-
-typedef unsigned long long u64;
-
-template <typename L>
-__global__ __launch_bounds__(256) void group_flags_kernel(const L* __restrict__ lab, int B, u64* __restrict__ v) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < B; i += (long long)gridDim.x * 256) {
-        const L x = lab[i];
-        const u64 f = (i == 0 || (lab[i - 1] == 0 && x == 1)) ? 1ull : 0ull;
-        v[i] = (f << 32) | (x == 1 ? 1ull : 0ull);
-    }
-}
-
-__global__ __launch_bounds__(256) void group_index_kernel(const u64* __restrict__ v, const u64* __restrict__ e, int B, int* __restrict__ pos_off,
-                                                          int* __restrict__ pos_elem, int* __restrict__ ranks, int* __restrict__ counts) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < B; i += (long long)gridDim.x * 256) {
-        const u64 vi = v[i], ei = e[i];
-        const int f = (int)(vi >> 32), p = (int)(vi & 0xffffffffull);
-        const int g = (int)(ei >> 32) + f - 1;
-        const int pi = (int)(ei & 0xffffffffull);
-        if (f) pos_off[g] = pi;
-        if (p) {
-            pos_elem[pi] = (int)i;
-            ranks[pi] = 1;
-        }
-        if (i == B - 1) {
-            pos_off[g + 1] = pi + p;
-            counts[0] = g + 1;
-            counts[1] = pi + p;
-        }
-    }
-}
 
 template <typename L, int MODE>
 __global__ __launch_bounds__(256) void group_rank_kernel(const float* __restrict__ score, const L* __restrict__ lab, const u64* __restrict__ v,
@@ -130,14 +98,6 @@ __global__ __launch_bounds__(256) void group_metrics_kernel(const int* __restric
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t scan_temp_bytes(int B) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const u64*)nullptr, (u64*)nullptr, B);
-    return bytes;
-}
-
 template <typename L>
 static int group_rank_impl(const float* score, const L* lab, int B, int mode, int* ranks, int* pos_off, int* counts, char* ws, size_t ws_bytes,
                            hipStream_t s) {
@@ -146,11 +106,11 @@ static int group_rank_impl(const float* score, const L* lab, int B, int mode, in
     int* pos_elem = (int*)(ws + 2 * align256((size_t)B * 8));
     char* temp = ws + 2 * align256((size_t)B * 8) + align256((size_t)B * 4);
     size_t temp_bytes = ws_bytes - (size_t)(temp - ws);
-    const int blocks = (int)((B + 255LL) / 256 < 65536 ? (B + 255LL) / 256 : 65536);
+    const int blocks = group_blocks(B);
     hipLaunchKernelGGL(group_flags_kernel<L>, dim3(blocks), dim3(256), 0, s, lab, B, v);
     TXE_CHECK_LAUNCH();
-    if (hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, (const u64*)v, e, B, s) != hipSuccess) return TXE_ERR_LAUNCH;
-    hipLaunchKernelGGL(group_index_kernel, dim3(blocks), dim3(256), 0, s, v, e, B, pos_off, pos_elem, ranks, counts);
+    if (!group_scan(v, e, B, temp, temp_bytes, s)) return TXE_ERR_LAUNCH;
+    hipLaunchKernelGGL(group_index_kernel<1>, dim3(blocks), dim3(256), 0, s, v, e, B, pos_off, pos_elem, ranks, counts);
     TXE_CHECK_LAUNCH();
     const long long tiles = (B + 63LL) / 64;
     const dim3 grid((unsigned)((tiles + 3) / 4));
@@ -170,7 +130,7 @@ extern "C" {
 
 size_t txe_group_rank_ws_bytes(int B) {
     if (B < 1) return 0;
-    return 2 * align256((size_t)B * 8) + align256((size_t)B * 4) + align256(scan_temp_bytes(B));
+    return 2 * align256((size_t)B * 8) + align256((size_t)B * 4) + align256(group_scan_temp_bytes(B));
 }
 
 int txe_group_rank(const float* score, const void* labels, int label_bytes, int B, int mode, int* ranks, int* pos_off, int* counts, void* ws,

@@ -1,6 +1,18 @@
-"""model/loss.py:52-57 `info_nce_loss` -- the loss of the PGAT+LBM training path (config "loss": "info_nce_loss"; trainer.py:52-56
-regroups the scores to [queries, 1 + negatives] and passes all-zero targets) -- as one HIP launch that also leaves the gradient.
-The reference's other losses are plain torch one-liners and stay with torch."""
+"""The training losses of the reference's model/loss.py on the device, each a HIP launch chain that leaves the sum-reduced loss AND its
+gradient (no autograd graph of small torch kernels behind it, no read-back):
+
+    info_nce_loss     loss.py:52-57 -- the loss of the PGAT+LBM training path (config "loss": "info_nce_loss"; trainer.py:52-56 regroups
+                      the scores to [queries, 1 + negatives] and passes all-zero targets): one launch (csrc/txe_loss.hip)
+    bce_loss          loss.py:21-29 -- the loss of nine of the reference's eleven configs: one launch (csrc/txe_pairloss.hip)
+    square_exp_loss   loss.py:12-19: one launch
+    margin_rank_loss  loss.py:31-50 without its `target.cpu()`, its regex over the label bytes and its itertools.product: five enqueued
+                      steps on the stream, nothing read back
+    host_bce_loss / host_square_exp_loss / host_margin_rank_loss   the numpy float64 restatements (the written definitions; the tests
+                      compare against them)
+
+The last three device losses take (output [B] or [B, 1], target [B] int32 / int64) as trainer.py:57-58 passes them.  An entry is a
+positive iff its label is 1.  Only `nll_loss` (no config uses it) stays with torch."""
+import numpy as np
 import torch
 
 from . import _lib
@@ -24,10 +36,15 @@ class _InfoNCE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss):
         (d_x,) = ctx.saved_tensors
-        unit = _UNIT.get(grad_loss.device)
-        if unit is not None and grad_loss.data_ptr() == unit.data_ptr() and grad_loss.numel() == 1:
-            return d_x, None                    # d_x * 1: the plain `loss.backward()` of trainer.py:60 (LossTensor.backward below)
-        return d_x * grad_loss, None
+        return _scaled(d_x, grad_loss), None
+
+
+def _scaled(d_x, grad_loss):
+    """the saved gradient times the upstream one; the cached unit constant of LossTensor.backward is recognised by its address"""
+    unit = _UNIT.get(grad_loss.device)
+    if unit is not None and grad_loss.data_ptr() == unit.data_ptr() and grad_loss.numel() == 1:
+        return d_x                              # d_x * 1: the plain `loss.backward()` of trainer.py:60 (LossTensor.backward below)
+    return d_x * grad_loss
 
 
 _UNIT = {}      # device -> the constant 1.0 that `loss.backward()` starts from (never written after its creation)
@@ -36,8 +53,8 @@ _UNIT = {}      # device -> the constant 1.0 that `loss.backward()` starts from 
 class LossTensor(torch.Tensor):
     """The scalar loss.  `loss.backward()` without a gradient (trainer/trainer.py:60) makes autograd allocate a ones tensor and fill it
     (one ~5 us launch), and the loss function's backward then multiplies its saved gradient by that 1.0 (another): here the call starts
-    from a cached device constant, which _InfoNCE.backward recognises by its address and answers with the saved gradient itself -- the
-    same numbers, two launches fewer per step.  Any other use (an explicit gradient, arithmetic on the loss first,
+    from a cached device constant, which the loss functions' backward (_scaled) recognises by its address and answers with the saved
+    gradient itself -- the same numbers, two launches fewer per step.  Any other use (an explicit gradient, arithmetic on the loss first,
     torch.autograd.backward / grad) takes the ordinary path."""
 
     def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
@@ -58,3 +75,171 @@ def info_nce_loss(output, target=None):
     if not output.is_cuda:
         raise RuntimeError("taxoexpan_amd.loss.info_nce_loss runs on the MI355X only (no CPU path)")
     return _InfoNCE.apply(output, target).as_subclass(LossTensor)
+
+
+# ---- bce, square-exp and margin-rank ------------------------------------------------------------------------------------------------
+
+_BCE, _SQUARE_EXP, _MARGIN_RANK = 0, 1, 2
+
+
+class _LabelledLoss(torch.autograd.Function):
+    """txe_bce_loss / txe_square_exp_loss / txe_margin_rank_loss: forward leaves the loss and d_x [B]; backward scales d_x"""
+
+    @staticmethod
+    def forward(ctx, output, target, kind, scalar):
+        x = output.reshape(-1)                                        # [B] or [B, 1]: a view either way
+        if not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.float().contiguous()
+        lab = target if target.is_contiguous() else target.contiguous()
+        B = x.shape[0]
+        dev = x.device
+        ctx.shape, ctx.dtype = output.shape, output.dtype
+        with _lib.on_device(dev):
+            d_x = torch.empty(B, dtype=torch.float32, device=dev)
+            if B == 0:                                                # nothing to launch
+                ctx.save_for_backward(d_x)
+                return torch.zeros((), dtype=torch.float32, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            if kind == _BCE:
+                _lib.call("txe_bce_loss", x.data_ptr(), lab.data_ptr(), lab.element_size(), B, loss.data_ptr(), d_x.data_ptr(),
+                          _lib.stream_ptr())
+            elif kind == _SQUARE_EXP:
+                _lib.call("txe_square_exp_loss", x.data_ptr(), lab.data_ptr(), lab.element_size(), B, scalar, loss.data_ptr(),
+                          d_x.data_ptr(), _lib.stream_ptr())
+            else:
+                wsb = _lib.pure("txe_margin_rank_loss_ws_bytes", B)   # a function of B alone
+                ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+                _lib.call("txe_margin_rank_loss", x.data_ptr(), lab.data_ptr(), lab.element_size(), B, scalar, loss.data_ptr(),
+                          d_x.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr())
+        ctx.save_for_backward(d_x)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (d_x,) = ctx.saved_tensors
+        d = _scaled(d_x, grad_loss).view(ctx.shape)
+        return (d if ctx.dtype == torch.float32 else d.to(ctx.dtype)), None, None, None
+
+
+def _labelled(name, output, target, kind, scalar):
+    if not (torch.is_tensor(output) and torch.is_tensor(target)):
+        raise TypeError(f"{name} takes tensors")
+    if not output.is_cuda:
+        raise RuntimeError(f"taxoexpan_amd.loss.{name} runs on the MI355X only (no CPU path; loss.host_{name} is the restatement)")
+    if not (output.dim() == 1 or (output.dim() == 2 and output.shape[1] == 1)):
+        raise ValueError(f"{name} takes scores [B] or [B, 1], got {tuple(output.shape)}")
+    if target.dim() != 1 or target.shape[0] != output.shape[0]:
+        raise ValueError(f"labels must be [B] with B = {output.shape[0]}, got {tuple(target.shape)}")
+    if target.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"labels must be int32 or int64, got {target.dtype}")
+    if target.device != output.device:
+        raise ValueError("scores and labels must be on one device")
+    if output.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name} takes B < 2^31")
+    scalar = float(scalar)
+    if not np.isfinite(scalar):
+        raise ValueError(f"{name}: beta / margin must be finite, got {scalar}")
+    return _LabelledLoss.apply(output, target, kind, scalar).as_subclass(LossTensor)
+
+
+def bce_loss(output, target, beta=1.0):
+    """model/loss.py:21-29.  output: [B] or [B, 1] scores (energies: smaller = more likely a true position, so the target is inverted,
+    loss.py:26); target: [B] int32 / int64 in {0, 1}.  Returns sum over positives (label 1) of softplus(x) + sum over the others of
+    softplus(-x) = F.binary_cross_entropy_with_logits(x, 1 - target, reduction="sum"), with d_x = sigmoid(x) - [no positive].  beta is
+    accepted and unused, as in the reference.  B == 1 works (the reference's `squeeze()` makes a 0-dim tensor there and raises)."""
+    return _labelled("bce_loss", output, target, _BCE, 0.0)
+
+
+def square_exp_loss(output, target, beta=1.0):
+    """model/loss.py:12-19: sum over label == 1 of x^2 + beta * sum over label == 0 of exp(-x); any other label contributes nothing (the
+    reference masks with `== 0`).  exp overflows to Inf in fp32 as the torch expression does."""
+    return _labelled("square_exp_loss", output, target, _SQUARE_EXP, beta)
+
+
+def margin_rank_loss(output, target, margin=1.0):
+    """model/loss.py:31-50 without its read-back.  Groups start at index 0 and at every i with target[i-1] == 0 and target[i] == 1
+    (metric.obtain_ranks' rule); within a group every (positive p, negative n) pair -- label 1 against every other label -- contributes
+    max(0, (x_p - x_n) + margin).  The gradient is integer-valued: +/- the number of active pairs of the entry, with the condition
+    (x_p - x_n) + margin > 0 evaluated in fp32 exactly as written, so it is bit-equal to torch autograd's on the same pairs.
+    DEVIATION from the reference: on label vectors whose every group is >= 1 ones followed by >= 1 zeros (what the samplers produce) the
+    pairs are the reference's; on a vector that BEGINS WITH A ZERO ([0, 1, 0], [0, 0, 1, 0]) the reference's regex bookkeeping pairs
+    nothing and returns 0, while this follows the group rule ([0, 1, 0]: the leading zero is a group of its own without a positive, and
+    [1, 0] gives one pair)."""
+    return _labelled("margin_rank_loss", output, target, _MARGIN_RANK, margin)
+
+
+def _host_args(output, target):
+    x = np.asarray(output)
+    if not (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == 1)):
+        raise ValueError(f"scores must be [B] or [B, 1], got {x.shape}")
+    x = x.reshape(-1).astype(np.float64)
+    t = np.asarray(target)
+    if t.ndim != 1 or t.shape[0] != x.shape[0]:
+        raise ValueError(f"labels must be [B] with B = {x.shape[0]}, got {t.shape}")
+    if t.dtype not in (np.int32, np.int64):
+        raise ValueError(f"labels must be int32 or int64, got {t.dtype}")
+    return x, t
+
+
+def host_bce_loss(output, target, beta=1.0):
+    """numpy float64 restatement of txe_bce_loss: (loss, d_x [B])"""
+    x, t = _host_args(output, target)
+    pos = t == 1
+    with np.errstate(over="ignore", invalid="ignore"):
+        z = np.where(pos, x, -x)
+        loss = np.sum(np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z))) + np.where(np.isnan(z), np.nan, 0.0))
+        e = np.exp(-np.abs(x))
+        sig = np.where(x >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+        d = np.where(np.isnan(x), np.nan, sig - np.where(pos, 0.0, 1.0))
+    return float(loss), d
+
+
+def host_square_exp_loss(output, target, beta=1.0):
+    """numpy float64 restatement of txe_square_exp_loss: (loss, d_x [B])"""
+    x, t = _host_args(output, target)
+    pos, neg = t == 1, t == 0
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.exp(-x[neg])
+        loss = np.sum(x[pos] ** 2) + beta * np.sum(e)
+        d = np.zeros_like(x)
+        d[pos] = 2.0 * x[pos]
+        d[neg] = -beta * e
+    return float(loss), d
+
+
+def group_starts(target):
+    """the first index of every group of a label vector: 0 and every i with target[i-1] == 0 and target[i] == 1"""
+    t = np.asarray(target)
+    if t.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64)
+    return np.flatnonzero(np.concatenate([[True], (t[:-1] == 0) & (t[1:] == 1)]))
+
+
+def host_margin_pairs(target):
+    """(positive indices, negative indices) of every pair of the group rule, group by group, positives outermost"""
+    t = np.asarray(target)
+    starts = group_starts(t)
+    ends = np.append(starts[1:], t.shape[0])
+    pi, ni = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+    for a, b in zip(starts, ends):
+        idx = np.arange(a, b)
+        p, n = idx[t[a:b] == 1], idx[t[a:b] != 1]
+        pi.append(np.repeat(p, n.size))
+        ni.append(np.tile(n, p.size))
+    return np.concatenate(pi).astype(np.int64), np.concatenate(ni).astype(np.int64)
+
+
+def host_margin_rank_loss(output, target, margin=1.0, dtype=np.float64):
+    """numpy restatement of txe_margin_rank_loss: (loss, d_x [B]); dtype = the arithmetic of the hinge terms (float64: the definition;
+    float32: the condition as the kernel evaluates it)"""
+    x, t = _host_args(output, target)
+    x = x.astype(dtype)
+    pi, ni = host_margin_pairs(t)
+    with np.errstate(invalid="ignore"):
+        term = (x[pi] - x[ni]) + dtype(margin)
+        active = term > 0
+        loss = np.sum(np.where(~(term <= 0), term, dtype(0)).astype(np.float64))     # a NaN term stays (torch's clamp keeps it)
+    d = np.zeros(x.shape[0], dtype=np.float64)
+    np.add.at(d, pi[active], 1.0)
+    np.add.at(d, ni[active], -1.0)
+    return float(loss), d

@@ -12,7 +12,12 @@ then profiles (a) and (g) twice each, alternating -- adam_kernel<true> beside ad
 step of both legs -- and last times the frozen tail of a diverged epoch: every loss times inf, so every optimizer launch of leg (g)
 returns at once (parameters and moments are checked to be untouched).
 
-    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50] [--guard]"""
+--loss {info_nce,bce,square_exp,margin_rank} (default info_nce: everything above, unchanged) puts another loss into both legs: (a) gets
+the device loss (loss.bce_loss / square_exp_loss / margin_rank_loss: still nothing read back), (b) the torch expression of the same loss
+as tools/loss_timing.py writes it -- for margin_rank the literal route with its label read-back and host pair construction -- and keeps
+its two `loss.item()`.  --guard goes with info_nce only.
+
+    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50] [--guard] [--loss info_nce]"""
 import argparse
 import ctypes
 import os
@@ -26,6 +31,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+import loss_timing  # noqa: E402  (tools/loss_timing.py: the torch expressions of the labelled losses)
+from taxoexpan_amd import loss as txe_loss  # noqa: E402
 from taxoexpan_amd import _lib, synthetic as syn  # noqa: E402
 from taxoexpan_amd.data_loaders import DeviceBatchLoader  # noqa: E402
 from taxoexpan_amd.dataset import MAGDataset, MaskedGraphDataset  # noqa: E402
@@ -44,17 +51,24 @@ def masked_mag_cs_train(directory):
     return MaskedGraphDataset(raw, mode="train", sampling_mode=1, negative_size=K, expand_factor=50, normalize_embed=True)
 
 
-def reference_style_epoch(model, loader, optimizer, dev):
+DEVICE_LOSS = {"bce": txe_loss.bce_loss, "square_exp": txe_loss.square_exp_loss, "margin_rank": txe_loss.margin_rank_loss}
+TORCH_LOSS = {"bce": loss_timing.torch_bce, "square_exp": loss_timing.torch_square_exp, "margin_rank": loss_timing.torch_margin_literal}
+
+
+def reference_style_epoch(model, loader, optimizer, dev, loss_name="info_nce"):
     """trainer.py:41-77 as written: two host round trips per step"""
     model.train()
     total_loss, n = 0, 0
     for bg, h, nf, label in loader:
         optimizer.zero_grad()
         prediction = model(bg, h, nf)
-        n_batches = int(label.sum().detach())
-        prediction = prediction.reshape(n_batches, -1)
-        target = torch.zeros(n_batches, dtype=torch.long).to(dev)
-        loss = info_nce_loss(prediction, target)
+        if loss_name == "info_nce":
+            n_batches = int(label.sum().detach())
+            prediction = prediction.reshape(n_batches, -1)
+            target = torch.zeros(n_batches, dtype=torch.long).to(dev)
+            loss = info_nce_loss(prediction, target)
+        else:
+            loss = TORCH_LOSS[loss_name](prediction.reshape(-1, 1), label)      # trainer.py:57-58
         loss.backward()
         optimizer.step()
         loss.item()                                          # trainer.py:64 (the tensorboard scalar)
@@ -143,7 +157,13 @@ def main():
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=50)
     ap.add_argument("--guard", action="store_true", help="add leg (g): clip (never active) and freeze on; see the module docstring")
+    ap.add_argument("--loss", choices=["info_nce", "bce", "square_exp", "margin_rank"], default="info_nce")
     args = ap.parse_args()
+    if args.guard and args.loss != "info_nce":
+        ap.error("--guard goes with --loss info_nce only")
+    kw = {} if args.loss == "info_nce" else {"loss_fn": DEVICE_LOSS[args.loss]}       # (info_nce: the calls are what they were)
+    if kw:
+        print(f"loss: {args.loss} -- (a) the device loss, (b) its torch expression", flush=True)
     assert torch.cuda.is_available(), "train_epoch_timing.py times the MI355X: no GPU found"
     dev = torch.device("cuda:0")
     with tempfile.TemporaryDirectory() as d:
@@ -156,26 +176,28 @@ def main():
     loader = DeviceBatchLoader(ds, BS, dev, shuffle=True, seed=0, sampler="device")
     n_grad = sum(p.numel() for p in model.parameters())
     print(f"{len(loader)} steps per epoch, {BS} queries x {1 + K} egonets per step, {n_grad} gradient elements per step", flush=True)
-    train_epoch(model, _First(loader, 30), opt)              # warm-up of both legs (first-call costs, allocator)
-    reference_style_epoch(model, _First(loader, 30), opt, dev)
+    train_epoch(model, _First(loader, 30), opt, **kw)        # warm-up of both legs (first-call costs, allocator)
+    reference_style_epoch(model, _First(loader, 30), opt, dev, args.loss)
     if args.guard:
         train_epoch(model, _First(loader, 30), opt, **GUARD)
     a_s, b_s, g_s = [], [], []
     for e in range(args.epochs):
-        ta, ra = timed(lambda: train_epoch(model, loader, opt))
+        ta, ra = timed(lambda: train_epoch(model, loader, opt, **kw))
         if args.guard:
             tg, rg = timed(lambda: train_epoch(model, loader, opt, **GUARD))
             assert rg["first_nonfinite"] == -1, "the model diverged: the timing is void"
             g_s.append(1e3 * tg / rg["n_batches"])
-        tb, (lb, nb) = timed(lambda: reference_style_epoch(model, loader, opt, dev))
+        tb, (lb, nb) = timed(lambda: reference_style_epoch(model, loader, opt, dev, args.loss))
         assert ra["first_nonfinite"] == -1 and np.isfinite(lb), "the model diverged: the timing is void"
         a_s.append(1e3 * ta / ra["n_batches"])
         b_s.append(1e3 * tb / nb)
         print(f"epoch {e}: (a) train_epoch {1e3 * ta:.1f} ms = {a_s[-1]:.3f} ms/step (loss {ra['loss']:.3f}, |g| {ra['grad_norms'][-1]:.3f}) | "
               + (f"(g) guarded {1e3 * tg:.1f} ms = {g_s[-1]:.3f} ms/step | " if args.guard else "")
               + f"(b) reference-style loop {1e3 * tb:.1f} ms = {b_s[-1]:.3f} ms/step (loss {lb:.3f})", flush=True)
-    prof = profiled_kernels(model, loader, opt, args.profile_steps)
-    for name in ("step_log_kernel", "adam_kernel<true>"):
+    prof = profiled_kernels(model, loader, opt, args.profile_steps, **kw)
+    loss_kernels = {"bce": ("bce_loss_kernel",), "square_exp": ("square_exp_loss_kernel",),
+                    "margin_rank": ("group_flags_kernel", "group_scan", "group_index_kernel<0>", "margin_pairs_kernel", "margin_finish_kernel")}
+    for name in ("step_log_kernel", "adam_kernel<true>") + loss_kernels.get(args.loss, ()):
         if name in prof:
             mean, med, n, work = prof[name]
             print(f"{name}: mean {mean:.2f} us, median {med:.2f} us over {n} launches; {work / 1e6:.2f} MB compulsory per launch "
