@@ -3,6 +3,7 @@
 torch is plumbing here: it owns device memory (caching allocator), the current HIP stream and autograd's tape;
 every number is produced by the hand-written HIP kernels.  There is no CPU path -- host tensors raise.
 """
+import ctypes
 import typing
 import weakref
 
@@ -116,9 +117,10 @@ class _CaptureList(list):
 
 class debug_capture:
     """`with ops.debug_capture() as runs:` -- every GAT / GCN stack forward inside the block appends (csr, cfg, states): the per-layer
-    buffers of the fused stack (X = padded layer input, Y = projection output, alpha [E, H] in destination-CSR order, cl = the folded
-    output layer's GatFolded / GcnFolded: cl.Z, cl.alpha, ...).  Parity tests read the intermediates the reference exposes per layer
-    (model_zoo.py:90-95) from here; nothing is copied and nothing changes in the computation."""
+    buffers of the fused stack (X = padded layer input, None where it is never stored: layer 0 on the table route or with st.vx;
+    Y = projection output, alpha [E, H] in destination-CSR order, cl = the folded output layer's GatFolded / GcnFolded: cl.Z,
+    cl.alpha, ...).  Parity tests read the intermediates the reference exposes per layer (model_zoo.py:90-95) from here;
+    nothing is copied and nothing changes in the computation."""
 
     def __enter__(self):
         global _CAPTURE
@@ -137,6 +139,74 @@ def apply_stack(fn, csr, cfg, *args):
     table-projection path of GatheredRows."""
     cfg.grad_enabled = torch.is_grad_enabled()
     return fn.apply(csr, cfg, *args)
+
+
+# ---- the frame GATStackFunction and GCNStackFunction share around their layer loops -----------------------------------------------------
+def _stack_begin(ctx, csr, cfg, h, pos, rpos, pw, params, feat_p):
+    """A stack forward's inputs, normalised: (need, z_only, collapse, table, src, ld_h, ref, N, kh, pos).
+    need: keep the backward state (see apply_stack); collapse: the output layer is folded behind the readout, z_only: and stops at Z;
+    table: layer 0 projects src.table and gathers (GatheredRows), otherwise src [N, kh] with row pitch ld_h holds the
+    features; ref: the allocation reference (src, or the table).  What backward needs of the inputs goes on ctx here: csr, cfg, h_req,
+    link, and -- only for a folded layer with position weights -- rpos, pwf (pw flat, fp32), pw_shape."""
+    need = cfg.grad_enabled and any(ctx.needs_input_grad)
+    z_only = (cfg.final == "collapse_z")        # 'collapse' that stops at Z: the Function returns (Z [G, Kp], the output layer's packed weights)
+    collapse = (cfg.final == "collapse") or z_only
+    table = _use_table(h, need, feat_p) and not (collapse and cfg.n_layers == 1)
+    if isinstance(h, GatheredRows) and not table:
+        h = h.tensor()
+    if table:
+        _need_cuda(h.table, *[p for p in params if p is not None])
+        src, ld_h, ref, N = h, 0, h.table, h.index.shape[0]
+    else:
+        _need_cuda(h, *[p for p in params if p is not None])
+        src, ld_h = _rows(h)
+        ref, N = src, src.shape[0]
+    weighted = collapse and pw is not None
+    ctx.csr, ctx.cfg, ctx.h_req, ctx.link = csr, cfg, ctx.needs_input_grad[2], (cfg.link if z_only else None)
+    ctx.rpos, ctx.pwf, ctx.pw_shape = ((_i32(rpos, ref.device), _f32(pw.reshape(-1)), pw.shape) if weighted else (None, None, None))
+    return need, z_only, collapse, table, src, ld_h, ref, N, ref.shape[1], _i32(pos, ref.device)
+
+
+def _stack_folded_result(ctx, st, res, z_only, need):
+    """what a stack returns for its folded output layer `st`: res (hg [G, D]), or with z_only (Z, the layer's packed weights)"""
+    if z_only:
+        res = (res, st.Wp)
+        ctx.mark_non_differentiable(st.Wp)
+        ctx.set_materialize_grads(False)        # (no zero "gradient" of the packed weights: a 4 MB fill per step)
+    if not need:
+        st.cl = st.desc = st.mask = st.Wp = st.X = None
+    return res
+
+
+def _stack_end(ctx, states, need, route):
+    ctx.states = states if need else None
+    note_route("stack", route)
+    if _CAPTURE is not None:
+        _CAPTURE.append((ctx.csr, ctx.cfg, states))
+
+
+def _stack_bwd_begin(ctx, d_res, n_params, implicit=False):
+    """(the saved states, d_res as fp32) -- or (None, the Function's all-None gradients) when no gradient arrived: collapse_z does not
+    materialise absent gradients, Z took no part in the loss, and the saved state can go.  implicit: no tensor is expected (the
+    matcher's 'dZ' travels through the FoldLink, not through autograd)."""
+    states = ctx.states
+    if states is None:
+        raise RuntimeError(_BACKWARD_TWICE)
+    if implicit:
+        return states, None
+    if d_res is None:
+        ctx.states = None
+        return None, (None,) * (6 + n_params)
+    return states, _f32(d_res)
+
+
+def _stack_bwd_end(ctx, states, d_X, d_pw, grads):
+    """the Function's gradients (csr, cfg, h, pos, rpos, pw, *params) from the bottom layer's d_X; releases the saved state"""
+    d_h = d_X[:, :states[0].Kh].contiguous() if ctx.h_req else None
+    ctx.states = None
+    if d_pw is not None:
+        d_pw = d_pw.reshape(ctx.pw_shape)
+    return (None, None, d_h, None, None, d_pw, *grads)
 
 
 # ================================================================================================================
@@ -353,18 +423,19 @@ class GatFolded(typing.NamedTuple):
 
 
 class _GatLayerState:
-    __slots__ = ("X", "Wp", "mask", "Y", "alpha", "W", "al", "ar", "P", "pos", "Kh", "Pd", "Kp", "Fp", "H", "D", "seed", "cl", "prepared",
+    __slots__ = ("N", "device", "X", "Wp", "mask", "Y", "alpha", "W", "al", "ar", "P", "pos", "Kh", "Pd", "Kp", "Fp", "H", "D", "seed", "cl",
                  "x_dropped", "Xt", "vx", "desc")
 
-    def __init__(self):
+    def __init__(self, N=0, device=None):
+        self.N, self.device = N, device     # the batch's node count; where the layer's buffers live (_empty / _ws take the state as `ref`)
         self.X = self.Wp = self.mask = self.Y = self.alpha = self.Xt = None
         self.W = self.al = self.ar = self.P = None
         self.pos = None             # the nodes' positions if the layer has a position table P, else None
         self.Kh = self.Pd = self.Kp = self.Fp = self.H = self.D = self.seed = 0
         self.cl = None              # GatFolded: the output layer folded behind the readout
         self.desc = None            # ... and its (_lib.GraphBatch, _lib.GatFoldLayer): raw addresses of the batch's and this state's tensors
-        self.prepared = self.x_dropped = False
-        self.vx = False             # X is NOT stored (a first layer on the bf16 pipe: the packs form dropout([h | Emb[pos]]) themselves)
+        self.x_dropped = False
+        self.vx = False             # X is NOT stored, it stays None (a first layer on the bf16 pipe: the packs form dropout([h | Emb[pos]]) themselves)
 
 
 def _virtual_x_ok(st, h, ld_h, N, need, first_is_folded):
@@ -390,34 +461,21 @@ def _x_dropped_ok(cfg, states, l, collapse):
 
 
 def _gat_layers_prepare(items, feat_p):
-    """_gat_layer_prepare for several layers of a stack in ONE launch (txe_gat_layers_prepare): items = [(st, h, ld_h, dropped)],
-    st.X allocated.  A layer's preparation never depends on the layer below's output, so the whole stack is prepared before its first
-    GEMM.  dropped: X is written with the feature dropout already applied (a first layer on raw features whose X only GEMMs read)."""
-    import ctypes
+    """Several layers of a stack prepared in ONE launch (txe_gat_layers_prepare): layer input X = [h | Emb[pos] | 0] (h == None: the
+    aggregation below writes the feature columns), packed weights, keep mask.  items = [(st, h, ld_h, dropped)], st.X allocated unless
+    st.vx.  A layer's preparation never depends on the layer below's output, so the whole stack is prepared before its first GEMM.
+    dropped: X is written with the feature dropout already applied (a first layer on raw features whose X only GEMMs read)."""
     descs = (_lib.GatPrepareDesc * len(items))()
     for d, (st, h, ld_h, dropped) in zip(descs, items):
-        N = st.X.shape[0]
-        st.Wp = _empty((st.Fp, st.Kp), st.X)
-        st.mask = torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=st.X.device) if feat_p > 0.0 else None
-        d.h, d.ld_h, d.n_nodes, d.Kh, d.pos, d.P, d.Pd, d.X = ptr(h), ld_h, N, st.Kh, ptr(st.pos), ptr(st.P), st.Pd, (None if st.vx else ptr(st.X))
+        N = st.N
+        st.Wp = _empty((st.Fp, st.Kp), st)
+        st.mask = torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=st.device) if feat_p > 0.0 else None
+        d.h, d.ld_h, d.n_nodes, d.Kh, d.pos, d.P, d.Pd, d.X = ptr(h), ld_h, N, st.Kh, ptr(st.pos), ptr(st.P), st.Pd, ptr(st.X)
         d.W, d.attn_l, d.attn_r, d.H, d.D, d.Wp = ptr(st.W), ptr(st.al), ptr(st.ar), st.H, st.D, ptr(st.Wp)
         d.feat_drop_p, d.seed, d.mask = feat_p, st.seed, ptr(st.mask)
         st.x_dropped = bool(dropped and feat_p > 0.0)
         d.x_dropped = int(st.x_dropped)
-        st.prepared = True
     call("txe_gat_layers_prepare", ctypes.cast(descs, ctypes.c_void_p), len(items), _lib.stream_ptr())
-
-
-def _gat_layer_prepare(st, h, ld_h, feat_p):
-    """layer input X = [h | Emb[pos] | 0] (h == None: the producer already wrote the feature columns), packed weights, keep mask"""
-    if st.prepared:
-        return
-    N = st.X.shape[0]
-    s = _lib.stream_ptr()
-    st.Wp = _empty((st.Fp, st.Kp), st.X)
-    st.mask = torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=st.X.device) if feat_p > 0.0 else None
-    call("txe_gat_layer_prepare", ptr(h), ld_h, N, st.Kh, ptr(st.pos), ptr(st.P), st.Pd, ptr(st.X), ptr(st.W), ptr(st.al), ptr(st.ar),
-         st.H, st.D, ptr(st.Wp), feat_p, st.seed, ptr(st.mask), s)
 
 
 def _graph_batch(csr, N):
@@ -426,30 +484,29 @@ def _graph_batch(csr, N):
                            pos_out=ptr(csr.pos_out), graph_off=ptr(csr.graph_off), n_nodes=N, n_edges=csr.n_edges, G=csr.n_graphs)
 
 
-def _gat_collapse_fwd(csr, st, h, ld_h, rpos, pw, feat_p, attn_p, attn_slope, a12=None, z_only=False, fold_job=None, link=None):
-    """output layer (one head) folded behind the weighted-mean readout: hg [G, D] (txe_gat_collapse_fwd).
-    a12 given: the layer is already prepared and the previous layer's aggregation has formed its attention logits.
+def _gat_collapse_fwd(csr, st, rpos, pw, feat_p, attn_p, attn_slope, a12=None, z_only=False, fold_job=None, link=None):
+    """output layer (one head, prepared) folded behind the weighted-mean readout: hg [G, D] (txe_gat_collapse_fwd).
+    a12 given: the previous layer's aggregation has formed its attention logits.
     z_only: stop at Z [G, Kp] (hg = Z W^T is left to the consumer: FoldedGraphLinearFunction / BilinearFoldedRunsFunction)."""
-    N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
+    N, G, E = st.N, csr.n_graphs, csr.n_edges
     ready = a12 is not None
     if not ready:
-        _gat_layer_prepare(st, h, ld_h, feat_p)
-        a12 = _empty((max(N, 1), 2), st.X)
-    alpha, coef = _empty((max(E, 1),), st.X), _empty((max(N, 1),), st.X)
-    wsum, Z, hg = _empty((max(G, 1),), st.X), _empty((max(G, 1), st.Kp), st.X), (None if z_only else _empty((G, st.D), st.X))
-    gid = torch.empty(max(N, 1), dtype=torch.int32, device=st.X.device)
+        a12 = _empty((max(N, 1), 2), st)
+    alpha, coef = _empty((max(E, 1),), st), _empty((max(N, 1),), st)
+    wsum, Z, hg = _empty((max(G, 1),), st), _empty((max(G, 1), st.Kp), st), (None if z_only else _empty((G, st.D), st))
+    gid = torch.empty(max(N, 1), dtype=torch.int32, device=st.device)
     wsb = pure("txe_gat_collapse_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, 8)
     split_hg = not z_only and G > 0 and not _NO_SPLIT_GEMM
     if split_hg:                                         # room for Z and the weight rows as packed planes: hg = Z W^T on the bf16 pipe
         wsb += pure("txe_gat_collapse_split_ws_bytes", G, st.Kh, st.Pd, st.D)
-    ws = _ws(wsb, st.X)
+    ws = _ws(wsb, st)
     match = None
     if z_only and fold_job is not None and link is not None and N > 0 and G > 0 and not _NO_FOLD_EDOT:
         nt = pure("txe_gat_collapse_e_tiles", N, G, st.Kh, st.Pd)
         job = fold_job(st.Wp, st.D) if nt > 0 else None      # the matcher's runs, V and T, formed now: T rides in the Z sweep
         if job is not None:
             zrow = job.run_ids(G)
-            link.fwd, link.e_part = job, _empty((N, nt), st.X)
+            link.fwd, link.e_part = job, _empty((N, nt), st)
             match = _lib.FoldMatch(Tf=ptr(job.T), zrow=ptr(zrow), e_part=ptr(link.e_part))
             job.score = FoldScore(csr.graph_off, N, G, st.Kh, st.Pd, coef, wsum, feat_p, int(st.mask is not None and feat_p > 0.0))
     # the descriptors hold raw addresses: st.cl (and st, csr) own the tensors, and both go when the state does
@@ -476,21 +533,21 @@ def _gat_fold_grads(st, layer, rpos, pw, vocab):
 
 
 def _gat_collapse_bwd(csr, st, rpos, pw, vocab, d_hg, act_on, act_slope):
-    N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
+    N, G, E = st.N, csr.n_graphs, csr.n_edges
     batch, layer = st.desc
     d_hg, ld = _rows(d_hg)
     out, grads = _gat_fold_grads(st, layer, rpos, pw, vocab)
-    d_X = _empty((N, st.Kp), st.X)
+    d_X = _empty((N, st.Kp), st)
     wsb = pure("txe_gat_collapse_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(layer.vocab, 8))
-    ws = _ws(wsb, st.X)
+    ws = _ws(wsb, st)
     call("txe_gat_collapse_bwd", _lib.ref(batch), _lib.ref(layer), ptr(d_hg), ld, int(act_on), act_slope if act_slope else 1.0, ptr(d_X),
          _lib.ref(grads), ptr(ws), wsb, _lib.stream_ptr())
     return (d_X,) + out
 
 
 def _gat_layer_fwd(csr, st, h, ld_h, out, ld_out, feat_p, attn_p, attn_slope, out_mode, act_slope, save, nxt=None, out_drop=None):
-    """st.X is pre-allocated [N, Kp]; h != None copies the raw features in, h == None means the producer already wrote them.
-    nxt = (prepared state of the next, folded one-head layer, a12 buffer): its attention logits ride in the aggregation's epilogue."""
+    """one prepared layer: projection (of X; of h, pos and the mask themselves when st.vx; of the table when h is a GatheredRows), then
+    the attention / aggregation sweep into out.  nxt = (prepared state of the next, folded one-head layer, a12 buffer): its attention logits ride in the aggregation's epilogue."""
     H, D, Kh, Pd, Kp, Fp, pos = st.H, st.D, st.Kh, st.Pd, st.Kp, st.Fp, st.pos
     F = H * D
     s = _lib.stream_ptr()
@@ -511,16 +568,15 @@ def _gat_layer_fwd(csr, st, h, ld_h, out, ld_out, feat_p, attn_p, attn_slope, ou
         call("txe_gather_add_rows", ptr(T), Fp, ptr(_i32(h.index, T.device)), ptr(T2), Fp, ptr(pos) if T2 is not None else None, N, Fp,
              ptr(st.Y), Fp, s)
     else:
-        N = st.X.shape[0]
-        _gat_layer_prepare(st, h, ld_h, feat_p)
-        st.Y = _empty((N, Fp), st.X)
-        tws = _tail_ws(st.X)
+        N = st.N
+        st.Y = _empty((N, Fp), st)
+        tws = _tail_ws(st)
         dropped = st.x_dropped
         if (dropped or feat_p == 0.0) and not _NO_SPLIT_GEMM:      # X is a plain operand: fp32-accurate product on the bf16 pipe
             wsb = pure("txe_gat_dense_split_ws_bytes", N, Kh, Pd, H, D)
-            sws = _ws(wsb, st.X)
+            sws = _ws(wsb, st)
             xtb = pure("txe_gat_dense_split_xt_bytes", N, Kh, Pd, H, D) if save else 0
-            st.Xt = _ws(xtb, st.X) if xtb else None        # X packed contraction-major: the backward pass's weight gradient reads it
+            st.Xt = _ws(xtb, st) if xtb else None        # X packed contraction-major: the backward pass's weight gradient reads it
             if st.vx:                                      # X was never written: the packs read h, the position table and the mask
                 call("txe_gat_dense_fwd_split_src", ptr(h), ld_h, ptr(pos), ptr(st.P), ptr(st.mask), feat_p if st.mask is not None else 0.0,
                      N, Kh, Pd, ptr(st.Wp), H, D, ptr(st.Xt), ptr(st.Y), ptr(sws), wsb, s)
@@ -542,11 +598,11 @@ def _gat_layer_fwd(csr, st, h, ld_h, out, ld_out, feat_p, attn_p, attn_slope, ou
 
 def _gat_aggregate_bwd(csr, st, attn_p, attn_slope, d_pre, ld_dpre):
     """message/reduce backward of one layer: d_Y [N, Fp] = [d_ft | d_a1 | d_a2 | 0] from the gradient of its aggregated output"""
-    N = st.X.shape[0]
+    N = st.N
     H, D, Fp = st.H, st.D, st.Fp
     F, Fe = H * D, H * D + 2 * H
-    d_Y = _empty((N, Fp), st.X)
-    dz = _empty((max(csr.n_edges, 1) * H,), st.X)
+    d_Y = _empty((N, Fp), st)
+    dz = _empty((max(csr.n_edges, 1) * H,), st)
     call("txe_gat_aggregate_bwd", ptr(csr.rowptr_in), ptr(csr.col_src), ptr(csr.rowptr_out), ptr(csr.col_dst), ptr(csr.pos_out),
          N, ptr(st.Y), Fp, ptr(st.Y) + 4 * F, ptr(st.Y) + 4 * (F + H), Fp, H, D, attn_slope, attn_p, st.seed + 1, ptr(st.alpha),
          ptr(d_pre), ld_dpre, ptr(d_Y), Fp, ptr(d_Y) + 4 * F, ptr(d_Y) + 4 * (F + H), Fp, ptr(dz), Fp - Fe, _lib.stream_ptr())   # clears d_Y's padding too
@@ -559,7 +615,6 @@ class _TailChain:
     (a buffer released earlier could be handed to a later allocation of the same stream and overwritten before that launch)"""
 
     def __init__(self):
-        import ctypes
         self.buf = ctypes.create_string_buffer(_lib.TAIL_CHAIN_BYTES)
         self.ptr = ctypes.cast(self.buf, ctypes.c_void_p)
         self.keep = []
@@ -568,17 +623,17 @@ class _TailChain:
 def _gat_dense_bwd(st, vocab, feat_p, d_Y, need_dh, act_on, act_slope, chain=None, defer=False):
     """projection backward of one layer from d_Y: (d_X or None, dW, d_attn_l, d_attn_r, dP).
     chain / defer: see _TailChain (defer: this layer's last reduction launch is left to the bottom layer's)"""
-    N = st.X.shape[0]
+    N = st.N
     dW, dal, dar = torch.empty_like(st.W), torch.empty_like(st.al), torch.empty_like(st.ar)
     dP = torch.empty_like(st.P) if st.P is not None else None
-    d_X = _empty((N, st.Kp), st.X) if (need_dh or st.Pd > 0) else None
+    d_X = _empty((N, st.Kp), st) if (need_dh or st.Pd > 0) else None
     wsb = pure("txe_gat_dense_ws_bytes", N, st.Kh, st.Pd, st.H, st.D, vocab)
     split_dx = bool(need_dh) and not _NO_SPLIT_GEMM
     if split_dx:                                       # room for d_Y and Wp as packed planes: d_X = d_Y Wp on the bf16 pipe (DESIGN 4.10)
         wsb += pure("txe_gat_dense_bwd_split_ws_bytes", N, st.Kh, st.Pd, st.H, st.D)
-    ws = _ws(wsb, st.X)
+    ws = _ws(wsb, st)
     def run(phases):
-        call("txe_gat_dense_bwd", None if st.vx else ptr(st.X), N, st.Kh, st.Pd, ptr(st.pos), vocab, ptr(st.Wp), ptr(st.W), ptr(st.al), ptr(st.ar), st.H, st.D, feat_p,
+        call("txe_gat_dense_bwd", ptr(st.X), N, st.Kh, st.Pd, ptr(st.pos), vocab, ptr(st.Wp), ptr(st.W), ptr(st.al), ptr(st.ar), st.H, st.D, feat_p,
              ptr(st.mask), ptr(d_Y), int(need_dh), int(act_on), act_slope if act_slope else 1.0, ptr(d_X), ptr(dW), ptr(dal), ptr(dar),
              ptr(dP), int(st.x_dropped), ptr(st.Xt), phases, chain.ptr if chain is not None else None, ptr(ws), wsb, _lib.stream_ptr())
     # (a first PGAT layer's d_X -- position columns only -- is one HBM stream over d_Y, txe_dxpos.hip; every other d_X is a GEMM)
@@ -674,7 +729,7 @@ _WALK_PLANS = {}       # id of a CSR's rowptr_in tensor -> (weak reference to it
 def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, attn_p, attn_slope, d_hg, act_slope, chain=None, link=None):
     """txe_gat_collapse_bwd_fused: the folded layer's parameter gradients AND the layer below's d_Y in one sweep (no d_X).
     link given: d_hg IS dZ [G, Kp] (the consumer of Z folded hg = Z W^T into its own products, FoldLink)."""
-    N, G, E = st.X.shape[0], csr.n_graphs, csr.n_edges
+    N, G, E = st.N, csr.n_graphs, csr.n_edges
     batch, layer = st.desc
     lk = link or _NO_LINK
     edot = lk.dz_implicit                           # the <dZ, X> sweep was done in forward (FoldLink)
@@ -685,15 +740,15 @@ def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, attn_p, attn_slope, d_
     else:
         d_hg, ld = _rows(d_hg)
     out, grads = _gat_fold_grads(st, layer, rpos, pw, vocab)
-    d_Yp = _empty((N, sp.Fp), st.X)
-    dz = _empty((max(E, 1) * sp.H,), st.X)
+    d_Yp = _empty((N, sp.Fp), st)
+    dz = _empty((max(E, 1) * sp.H,), st)
     below = _lib.GatFoldBelow(Yp=ptr(sp.Y), ld_yp=sp.Fp, Hp=sp.H, Dp=sp.D, attn_slope_p=attn_slope, attn_drop_p_p=attn_p, seed_p=sp.seed + 1,
                               alpha_p=ptr(sp.alpha), d_Yp=ptr(d_Yp), ld_dyp=sp.Fp, n_pad=sp.Fp - (sp.H * sp.D + 2 * sp.H), dz_p=ptr(dz))
-    zgid = torch.empty(max(N, 1), dtype=torch.int32, device=st.X.device) if edot else None
+    zgid = torch.empty(max(N, 1), dtype=torch.int32, device=st.device) if edot else None
     match = lk.edot_args(zgid)
     plan = walk_plan(csr) if (sp.H == 4 and not _NO_EGO_WALK and not _NO_WALK_PLAN) else None
     wsb = pure("txe_gat_collapse_bwd_fused_ws_bytes", N, E, G, st.Kh, st.Pd, st.D, max(layer.vocab, 8), sp.H)
-    ws = _ws(wsb, st.X)
+    ws = _ws(wsb, st)
     # one set of descriptors for every call of this backward pass: the calls differ in `phases` alone
     args = (_lib.ref(batch), _lib.ref(layer), _lib.ref(below), _lib.ref(match), _lib.ref(grads), ptr(d_hg), ld, act_slope if act_slope else 1.0)
     rest = (ptr(lk.part) if lk.S > 0 else None, lk.S, ptr(plan), chain.ptr if chain is not None else None, ptr(ws), wsb)
@@ -715,7 +770,7 @@ def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, attn_p, attn_slope, d_
         # the folded layer's weight-gradient GEMM (MFMA-bound, needs only d_hg and Z) runs on a second stream under the HBM-bound
         # sweeps: complementary resources, and nothing downstream waits for it before the final reduction
         # (| FUSED_DW_BESIDE on every call: the product beside other kernels takes few fat k-slices, and the workspace is laid out for them)
-        main, side = torch.cuda.current_stream(), _side_stream(st.X.device)
+        main, side = torch.cuda.current_stream(), _side_stream(st.device)
         _order(main, side)
         with torch.cuda.stream(side):
             run(_lib.FUSED_DW | _lib.FUSED_DW_BESIDE)
@@ -734,30 +789,12 @@ class GATStackFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, csr, cfg, h, pos, rpos, pw, *params):
-        need = cfg.grad_enabled and any(ctx.needs_input_grad)      # (see apply_stack)
-        z_only = (cfg.final == "collapse_z")        # 'collapse' that stops at Z: returns (Z [G, Kp], the output layer's packed weights)
-        collapse = (cfg.final == "collapse") or z_only
-        table = _use_table(h, need, cfg.feat_p) and not (collapse and cfg.n_layers == 1)
-        if isinstance(h, GatheredRows) and not table:
-            h = h.tensor()
-        if table:
-            _need_cuda(h.table, *[p for p in params if p is not None])
-            src, ld_h = h, 0
-        else:
-            _need_cuda(h, *[p for p in params if p is not None])
-            h, ld_h = _rows(h)
-            src = h
-        pos = _i32(pos, h.device)
-        rpos = _i32(rpos, h.device) if (collapse and pw is not None) else None
-        pwf = _f32(pw.reshape(-1)) if (collapse and pw is not None) else None
+        need, z_only, collapse, table, src, ld_h, ref, N, kh, pos = _stack_begin(ctx, csr, cfg, h, pos, rpos, pw, params, cfg.feat_p)
         L = cfg.n_layers
-        N = h.shape[0]
         states = []
-        with _lib.on_device(h.device):
-            kh = h.shape[1]
-            ref = h.table if table else h
+        with _lib.on_device(ref.device):
             for l in range(L):
-                st = _GatLayerState()
+                st = _GatLayerState(N, ref.device)
                 st.W, st.al, st.ar, st.P = (_f32(p) for p in params[4 * l:4 * l + 4])
                 st.H, st.D, st.Kh = cfg.heads[l], cfg.out_dims[l], kh
                 st.Pd, st.pos = (0, None) if st.P is None else (st.P.shape[1], pos)
@@ -766,50 +803,36 @@ class GATStackFunction(torch.autograd.Function):
                 st.seed = cfg.seed + 16 * l
                 states.append(st)
                 kh = st.H * st.D
-            h = ref                                  # (allocation reference from here on; the features travel as `src`)
-            states[0].X = None if table else _empty((N, states[0].Kp), h)
-            if N > 0:                                # every layer's input buffer now, and ONE preparation launch for the whole stack
-                for l in range(1, L):
-                    states[l].X = _empty((N, states[l].Kp), h)
-                # (a layer that is not the folded one: only its GEMMs read X, so X is stored with the dropout applied -- by the
-                #  preparation (raw features, position columns) and by the aggregation of the layer below (_drops_output))
-                states[0].vx = (not table) and _virtual_x_ok(states[0], src, ld_h, N, need, collapse and L == 1)
-                _gat_layers_prepare([(st, (src if l == 0 else None), (ld_h if l == 0 else 0), _x_dropped_ok(cfg, states, l, collapse))
-                                     for l, st in enumerate(states) if not (table and l == 0)], cfg.feat_p)
+            # every layer's input buffer now (not the first's where the table or the packs stand in for it), and ONE preparation launch for
+            # the whole stack.  (a layer that is not the folded one: only its GEMMs read X, so X is stored with the dropout applied -- by
+            #  the preparation (raw features, position columns) and by the aggregation of the layer below (out_drop))
+            states[0].vx = (not table) and _virtual_x_ok(states[0], src, ld_h, N, need, collapse and L == 1)
+            todo = states[1:] if (table or states[0].vx) else states
+            for st in todo:
+                st.X = _empty((N, st.Kp), st)
+            _gat_layers_prepare([(st, (src if l == 0 else None), (ld_h if l == 0 else 0), _x_dropped_ok(cfg, states, l, collapse))
+                                 for l, st in enumerate(states) if not (table and l == 0)], cfg.feat_p)
             fused_a12 = None
             for l, st in enumerate(states):
                 last = (l == L - 1)
-                F = st.H * st.D
                 if last and collapse:
-                    res = _gat_collapse_fwd(csr, st, src if l == 0 else None, ld_h if l == 0 else 0, rpos, pwf, cfg.feat_p, cfg.attn_p,
-                                            cfg.attn_slope, a12=fused_a12, z_only=z_only,
+                    res = _gat_collapse_fwd(csr, st, ctx.rpos, ctx.pwf, cfg.feat_p, cfg.attn_p, cfg.attn_slope, a12=fused_a12, z_only=z_only,
                                             fold_job=cfg.fold_job if (z_only and need) else None, link=cfg.link)
-                    if z_only:
-                        res = (res, st.Wp)
-                        ctx.mark_non_differentiable(st.Wp)
-                        ctx.set_materialize_grads(False)    # (no zero "gradient" of the packed weights: a 4 MB fill per step)
-                    if not need:
-                        st.cl = st.desc = st.mask = st.Wp = st.X = None
+                    res = _stack_folded_result(ctx, st, res, z_only, need)
                     break
-                if last:
-                    out, ld_out = _empty((N, F), h), F
-                else:                                  # the aggregation writes straight into the next layer's padded input
-                    if states[l + 1].X is None:
-                        states[l + 1].X = _empty((N, states[l + 1].Kp), h)
-                    out, ld_out = states[l + 1].X, states[l + 1].Kp
-                out_mode = 0 if (last or cfg.act_slope is None) else 1
+                F = st.H * st.D
+                # (not the last layer: the aggregation writes straight into the next layer's padded input)
+                out, ld_out = (_empty((N, F), st), F) if last else (states[l + 1].X, states[l + 1].Kp)
                 nxt = None
-                if (collapse and l + 1 == L - 1 and N > 0 and st.D % 4 == 0 and states[l + 1].Kp - st.H * st.D <= 128 and states[l + 1].Kp <= 4096
+                if (collapse and l + 1 == L - 1 and N > 0 and st.D % 4 == 0 and states[l + 1].Kp - F <= 128 and states[l + 1].Kp <= 4096
                         and not _NO_FUSED_LOGITS):
-                    # the folded output layer is prepared first: its keep mask and folded attention rows feed this layer's epilogue
-                    sn = states[l + 1]
-                    _gat_layer_prepare(sn, None, 0, cfg.feat_p)
-                    fused_a12 = _empty((N, 2), h)
-                    nxt = (sn, fused_a12)
+                    # the folded output layer's keep mask and folded attention rows feed this layer's epilogue
+                    fused_a12 = _empty((N, 2), st)
+                    nxt = (states[l + 1], fused_a12)
                 # (the layer above reads its input through plain GEMM operands: this layer's aggregation applies that layer's dropout)
                 out_drop = states[l + 1] if (not last and nxt is None and states[l + 1].x_dropped) else None
                 _gat_layer_fwd(csr, st, src if l == 0 else None, ld_h if l == 0 else 0, out, ld_out, cfg.feat_p, cfg.attn_p, cfg.attn_slope,
-                               out_mode, cfg.act_slope or 1.0, need, nxt, out_drop)
+                               0 if (last or cfg.act_slope is None) else 1, cfg.act_slope or 1.0, need, nxt, out_drop)
                 if not need:
                     st.Y = st.mask = st.Wp = None
                     if l > 0:
@@ -817,46 +840,31 @@ class GATStackFunction(torch.autograd.Function):
             H, D = cfg.heads[-1], cfg.out_dims[-1]
             if collapse:
                 pass
-            elif cfg.final == "mean":
-                if H == 1:
-                    res = out.view(N, D)
-                else:
-                    res = _empty((N, D), h)
-                    call("txe_head_mean_fwd", ptr(out), H, D, N, ptr(res), _lib.stream_ptr())
+            elif cfg.final == "mean" and H > 1:
+                res = _empty((N, D), ref)
+                call("txe_head_mean_fwd", ptr(out), H, D, N, ptr(res), _lib.stream_ptr())
             else:
-                res = out.view(N, H, D)
-        ctx.csr, ctx.cfg, ctx.states = csr, cfg, (states if need else None)
-        ctx.rpos, ctx.pwf, ctx.pw_shape = rpos, pwf, (pw.shape if pwf is not None else None)
-        ctx.h_req = ctx.needs_input_grad[2]
+                res = out.view(N, D) if cfg.final == "mean" else out.view(N, H, D)
         ctx.param_ids, ctx.pw_id = [id(p) for p in params], id(pw)
-        ctx.link = cfg.link if z_only else None
-        note_route("stack", cfg.final + ("+edot" if (ctx.link is not None and ctx.link.carried_T) else ""))
-        if _CAPTURE is not None:
-            _CAPTURE.append((csr, cfg, states))
+        _stack_end(ctx, states, need, cfg.final + ("+edot" if (ctx.link is not None and ctx.link.carried_T) else ""))
         return res
 
     @staticmethod
     def backward(ctx, d_res, *_unused):
-        csr, cfg, states = ctx.csr, ctx.cfg, ctx.states
-        if states is None:
-            raise RuntimeError(_BACKWARD_TWICE)
+        csr, cfg = ctx.csr, ctx.cfg
         L = cfg.n_layers
         H, D = cfg.heads[-1], cfg.out_dims[-1]
         z_only = (cfg.final == "collapse_z")
         collapse = (cfg.final == "collapse") or z_only
-        link = ctx.link if z_only else None
-        edot = link is not None and link.dz_implicit
-        if d_res is None and not edot:
-            # (collapse_z does not materialise absent gradients: Z took no part in the loss -- nothing to propagate, and the saved
-            #  state can go)
-            ctx.states = None
-            return (None,) * (6 + 4 * L)
-        d_res = None if edot else _f32(d_res)       # (edot: the matcher's 'dZ' travels through the FoldLink, not through autograd)
-        N = states[0].X.shape[0]
+        edot = ctx.link is not None and ctx.link.dz_implicit
+        states, d_res = _stack_bwd_begin(ctx, d_res, 4 * L, implicit=edot)
+        if states is None:
+            return d_res
+        N = states[0].N
         grads = [None] * (4 * L)
         d_pw = None
         note_route("stack_bwd", "fused+edot" if edot else ("collapse" if collapse else "layers"))
-        with _lib.on_device(states[0].X.device):
+        with _lib.on_device(states[0].device):
             if collapse:
                 d_pre, ld_dpre = None, 0
             elif cfg.final == "mean" and H > 1:
@@ -898,16 +906,13 @@ class GATStackFunction(torch.autograd.Function):
                     _GRAD_READY(l, [dW, dal, dar, dP] + ([d_pw] if last_c else []), ctx.param_ids[4 * l:4 * l + 4] + ([ctx.pw_id] if last_c else []))
                 if l > 0 and d_Y_ready is None:
                     d_pre, ld_dpre = d_X, st.Kp            # its first H*D(l-1) columns are d(pre-activation out_{l-1})
-            d_h = d_X[:, :states[0].Kh].contiguous() if ctx.h_req else None
+            res = _stack_bwd_end(ctx, states, d_X, d_pw, grads)
             if chain is not None:                  # (nothing left unless the bottom layer took a route without a phase B of its own)
                 call("txe_gat_tail_flush", chain.ptr, _lib.stream_ptr())
                 chain.keep = []
             if _GRAD_FLUSH is not None:
                 _GRAD_FLUSH()
-        ctx.states = None
-        if d_pw is not None:
-            d_pw = d_pw.reshape(ctx.pw_shape)
-        return (None, None, d_h, None, None, d_pw, *grads)
+        return res
 
 
 # ================================================================================================================
@@ -933,14 +938,128 @@ class GcnFolded(typing.NamedTuple):
 
 
 class _GcnLayerState:
-    __slots__ = ("X", "Wp", "mask", "W", "b", "P", "Kh", "Pd", "Kp", "Fo", "Fop", "seed", "cl", "x_dropped", "desc")
+    __slots__ = ("N", "device", "X", "Wp", "mask", "W", "b", "P", "pos", "Kh", "Pd", "Kp", "Fo", "Fop", "seed", "cl", "x_dropped", "desc")
 
-    def __init__(self):
+    def __init__(self, N=0, device=None):
+        self.N, self.device = N, device     # as in _GatLayerState
         self.X = self.Wp = self.mask = self.W = self.b = self.P = None
+        self.pos = None             # the nodes' positions if the layer has a position table P, else None
         self.Kh = self.Pd = self.Kp = self.Fo = self.Fop = self.seed = 0
         self.cl = None              # GcnFolded: the output layer folded behind the readout
         self.desc = None            # ... and its (_lib.GraphBatch, _lib.GcnFoldLayer), as in _GatLayerState
         self.x_dropped = False
+
+
+def _gcn_layers_prepare(csr, cfg, todo, h, ld_h, norm, collapse, z_only):
+    """_gat_layers_prepare for GCN layers, todo = [(l, st)] with st.X allocated: ONE launch (txe_gcn_layers_prepare) writes the layer
+    inputs' position / padding columns (layer 0: the features h too), the packed weights and the keep masks -- none of it depends on
+    a layer below's output -- and forms the degree normalisation `norm`.  Nothing to prepare (one layer, on the table route): txe_gcn_norm."""
+    if not todo:
+        call("txe_gcn_norm", ptr(csr.rowptr_in), csr.n_nodes, ptr(norm), _lib.stream_ptr())
+        return
+    descs = (_lib.GcnPrepareDesc * len(todo))()
+    for d, (l, st) in zip(descs, todo):
+        N, drop_p, folded = st.N, cfg.drop_ps[l], (collapse and l == cfg.n_layers - 1)
+        st.Wp = _empty(((st.Kp + 127) // 128 * 128, st.Fop), st)
+        st.mask = torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=st.device) if drop_p > 0.0 else None
+        # (a first layer on raw features that is not the folded one: only its GEMMs read X -> stored with the dropout applied)
+        st.x_dropped = bool(l == 0 and not folded and drop_p > 0.0)
+        # (folded into the matcher: the bias rides as one more weight row, behind a column of Z that counts as 1)
+        bias_row = st.b if (folded and z_only) else None
+        d.h, d.ld_h, d.n_nodes, d.Kh = ptr(h if l == 0 else None), (ld_h if l == 0 else 0), N, st.Kh
+        d.pos, d.P, d.Pd, d.X = ptr(st.pos), ptr(st.P), st.Pd, ptr(st.X)
+        d.W, d.Fo, d.Wp, d.drop_p, d.seed, d.mask = ptr(st.W), st.Fo, ptr(st.Wp), drop_p, st.seed, ptr(st.mask)
+        d.x_dropped, d.bias_row = int(st.x_dropped), ptr(bias_row)
+    call("txe_gcn_layers_prepare", ctypes.cast(descs, ctypes.c_void_p), len(todo), ptr(csr.rowptr_in), csr.n_nodes, ptr(norm), _lib.stream_ptr())
+
+
+def _gcn_layer_fwd(csr, st, h, norm, out, ld_out, drop_p, act_slope):
+    """one prepared layer: the projection hw = dropout(X) W (h a GatheredRows: gathered from the projected table instead), then the
+    normalised aggregation + bias (+ leaky_relu, act_slope not None) into out"""
+    N, s = st.N, _lib.stream_ptr()
+    hw = _empty((N, st.Fop), st)
+    if isinstance(h, GatheredRows):            # eval-mode first layer on table rows: project the table, gather (SURVEY 8f-2)
+        T, T2 = _gcn_table_projection(st, h)[:2]
+        call("txe_gather_add_rows", ptr(T), st.Fop, ptr(_i32(h.index, st.device)), ptr(T2), st.Fop, ptr(st.pos) if T2 is not None else None,
+             N, st.Fop, ptr(hw), st.Fop, s)
+        st.mask = st.Wp = None
+    else:
+        tws = _tail_ws(st)
+        call("txe_gcn_dense_fwd", ptr(st.X), N, st.Kh, st.Pd, ptr(st.Wp), st.Fo, 0.0 if st.x_dropped else drop_p,
+             None if st.x_dropped else ptr(st.mask), ptr(hw), ptr(tws), tws.numel(), s)
+        _launch_pending_prefetch()
+    call("txe_gcn_aggregate_fwd", ptr(csr.rowptr_in), ptr(csr.col_src), N, ptr(hw), st.Fop, ptr(norm), ptr(st.b),
+         0 if act_slope is None else 1, act_slope or 1.0, st.Fo, ptr(out), ld_out, s)
+
+
+def _gcn_collapse_fwd(csr, st, rpos, pw, norm, drop_p, z_only=False, link=None):
+    """the (activation-free, prepared) output layer folded behind the weighted-mean readout: hg [G, Fo] (txe_gcn_collapse_fwd).
+    z_only: stop at Z [G, Kp]; the consumer of Z learns from `link` how this layer's weights are packed (FoldLink.by_k / one_col)."""
+    N, G = st.N, csr.n_graphs
+    coef, wsum = _empty((max(N, 1),), st), _empty((max(G, 1),), st)
+    gid = torch.empty(max(N, 1), dtype=torch.int32, device=st.device)
+    Z, hg = _empty((max(G, 1), st.Kp), st), (None if z_only else _empty((G, st.Fo), st))
+    wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, 8)
+    ws = _ws(wsb, st)
+    # the descriptors hold raw addresses: st.cl (and st, csr, ctx.norm) own the tensors, and both go when the state does
+    st.cl = GcnFolded(coef, wsum, gid, Z)
+    batch = _graph_batch(csr, N)
+    layer = _lib.GcnFoldLayer(X=ptr(st.X), Kh=st.Kh, Pd=st.Pd, pos=ptr(rpos), Wp=ptr(st.Wp), Fo=st.Fo, bias=ptr(st.b), drop_p=drop_p,
+                              mask=ptr(st.mask), norm=ptr(norm), pw=ptr(pw), coef=ptr(coef), wsum=ptr(wsum), gid=ptr(gid), Z=ptr(Z),
+                              hg=ptr(hg), ld_hg=st.Fo)
+    st.desc = (batch, layer)
+    call("txe_gcn_collapse_fwd", _lib.ref(batch), _lib.ref(layer), ptr(ws), wsb, _lib.stream_ptr())
+    if z_only and link is not None:
+        link.by_k, link.one_col = True, (st.Kh + st.Pd if st.b is not None else -1)
+    return Z if z_only else hg
+
+
+def _gcn_layer_bwd(csr, st, norm, vocab, drop_p, d_pre, ld_dpre, need_dh, act_slope):
+    """one layer's backward from the gradient of its aggregated (pre-activation) output: (d_X or None, dW, d_b, dP).
+    act_slope: of the leaky_relu that produced this layer's input (None: none), its derivative is folded into d_X"""
+    N, s = st.N, _lib.stream_ptr()
+    d_hw = _empty((N, st.Fop), st)
+    d_b = torch.empty_like(st.b) if st.b is not None else None
+    wsb = pure("txe_gcn_aggregate_bwd_ws_bytes", N, st.Fo)
+    ws = _ws(wsb, st)
+    call("txe_gcn_aggregate_bwd", ptr(csr.rowptr_out), ptr(csr.col_dst), N, ptr(d_pre), ld_dpre, ptr(norm), st.Fo, ptr(d_hw), st.Fop, ptr(d_b),
+         ptr(ws), wsb, s)
+    d_X = _empty((N, st.Kp), st) if (need_dh or st.Pd > 0) else None
+    dW = torch.empty_like(st.W)
+    dP = torch.empty_like(st.P) if st.P is not None else None
+    wsb2 = pure("txe_gcn_dense_ws_bytes", N, st.Kh, st.Pd, st.Fo, vocab)
+    ws2 = _ws(wsb2, st)
+    call("txe_gcn_dense_bwd", ptr(st.X), N, st.Kh, st.Pd, ptr(st.pos), vocab, ptr(st.Wp), st.Fo, drop_p, ptr(st.mask), ptr(d_hw), int(need_dh),
+         int(act_slope is not None), 1.0 if act_slope is None else act_slope, ptr(d_X), ptr(dW), ptr(dP), int(st.x_dropped), ptr(ws2), wsb2, s)
+    return d_X, dW, d_b, dP
+
+
+def _gcn_collapse_bwd(csr, st, rpos, pw, vocab, d_hg, act_slope, z_only=False, link=None):
+    """the folded layer's backward (txe_gcn_collapse_bwd): (d_X, dW, d_b, dP, d_pw).  z_only: d_hg IS dZ [G, Kp], and the consumer of Z
+    left dW (and d_b as row Kh + Pd) in link.part [Kp][Fo]"""
+    N, G = st.N, csr.n_graphs
+    batch, layer = st.desc
+    d_hg, ld = _rows(d_hg)
+    if z_only:
+        part = link.part if link is not None else None
+        if part is None or link.S != 1 or tuple(part.shape) != (st.Kp, st.Fo):
+            raise RuntimeError("folded GCN output layer: the consumer of Z left no weight gradient in the FoldLink")
+        Kt = st.Kh + st.Pd
+        dW, d_b = part[:Kt], (part[Kt] if st.b is not None else None)
+    else:
+        dW = torch.empty_like(st.W)
+        d_b = torch.empty_like(st.b) if st.b is not None else None
+    d_X = _empty((N, st.Kp), st)
+    dP = torch.empty_like(st.P) if st.P is not None else None
+    d_pw = torch.empty_like(pw) if pw is not None else None
+    # (what backward adds to the layer's descriptor: the vocabulary, and the positions as the position table's gradient reads them)
+    layer.pos, layer.vocab = ptr(st.pos if st.pos is not None else rpos), max(vocab, pw.numel() if pw is not None else 0)
+    wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, max(layer.vocab, 8))
+    ws = _ws(wsb, st)
+    grads = _lib.GcnFoldGrads(dW=None if z_only else ptr(dW), d_b=None if z_only else ptr(d_b), dP=ptr(dP), d_pw=ptr(d_pw))
+    call("txe_gcn_collapse_bwd", _lib.ref(batch), _lib.ref(layer), ptr(d_hg), ld, int(act_slope is not None), 1.0 if act_slope is None else act_slope,
+         ptr(d_X), _lib.ref(grads), int(z_only), ptr(ws), wsb, _lib.stream_ptr())
+    return d_X, dW, d_b, dP, d_pw
 
 
 class GCNStackFunction(torch.autograd.Function):
@@ -952,204 +1071,77 @@ class GCNStackFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, csr, cfg, h, pos, rpos, pw, *params):
-        z_only = (cfg.final == "collapse_z")        # 'collapse' that stops at Z: returns (Z [G, Kp], the output layer's packed weights)
-        collapse = (cfg.final == "collapse") or z_only
+        need, z_only, collapse, table, src, ld_h, ref, N, kh, pos = _stack_begin(ctx, csr, cfg, h, pos, rpos, pw, params, cfg.drop_ps[0])
         L = cfg.n_layers
-        need = cfg.grad_enabled and any(ctx.needs_input_grad)      # (see apply_stack)
-        table = _use_table(h, need, cfg.drop_ps[0]) and not (collapse and L == 1)
-        if isinstance(h, GatheredRows) and not table:
-            h = h.tensor()
-        src = h if table else None                 # features as rows of a table: layer 0 projects the table
-        if table:
-            _need_cuda(h.table, *[p for p in params if p is not None])
-            N, kh0, ld_h, h = h.index.shape[0], h.table.shape[1], 0, h.table       # h: allocation reference from here on
-        else:
-            _need_cuda(h, *[p for p in params if p is not None])
-            h, ld_h = _rows(h)
-            N, kh0 = h.shape
-        pos = _i32(pos, h.device)
-        rpos = _i32(rpos, h.device) if (collapse and pw is not None) else None
-        pwf = _f32(pw.reshape(-1)) if (collapse and pw is not None) else None
         states = []
-        with _lib.on_device(h.device):
-            st_ = _lib.stream_ptr()
-            kh = kh0
+        with _lib.on_device(ref.device):
             for l in range(L):
-                st = _GcnLayerState()
+                st = _GcnLayerState(N, ref.device)
                 st.W, st.b, st.P = (_f32(p) for p in params[3 * l:3 * l + 3])
                 st.Kh, st.Fo = kh, cfg.out_dims[l]
-                st.Pd = 0 if st.P is None else st.P.shape[1]
+                st.Pd, st.pos = (0, None) if st.P is None else (st.P.shape[1], pos)
                 st.Kp = pure("txe_gat_padded_k", st.Kh, st.Pd)
                 st.Fop = pure("txe_gcn_padded_f", st.Fo)
                 st.seed = cfg.seed + 16 * l
                 states.append(st)
                 kh = st.Fo
-            # every layer's input buffer now; ONE launch prepares the whole stack (layer inputs' position / padding columns, packed weights,
-            # keep masks -- none of it depends on a layer below's output) and forms the degree normalisation
-            norm = _empty((max(N, 1),), h)
-            for l, st in enumerate(states):
-                st.X = None if (table and l == 0) else _empty((N, st.Kp), h)
+            # every layer's input buffer now (not the first's on the table route), and ONE preparation launch for the whole stack
+            norm = _empty((max(N, 1),), ref)
             todo = [(l, st) for l, st in enumerate(states) if not (table and l == 0)]
-            import ctypes
-            descs = (_lib.GcnPrepareDesc * max(len(todo), 1))()
-            keep = []
-            for d, (l, st) in zip(descs, todo):
-                last = (l == L - 1)
-                kp128 = (st.Kp + 127) // 128 * 128
-                st.Wp = _empty((kp128, st.Fop), h)
-                st.mask = (torch.empty((N, (st.Kh + st.Pd + 31) // 32), dtype=torch.int32, device=h.device)
-                           if cfg.drop_ps[l] > 0.0 else None)
-                # (a first layer on raw features that is not the folded one: only its GEMMs read X -> stored with the dropout applied)
-                st.x_dropped = bool(l == 0 and not (last and collapse) and cfg.drop_ps[l] > 0.0)
-                # (folded into the matcher: the bias rides as one more weight row, behind a column of Z that counts as 1)
-                bias_row = st.b if (last and z_only and st.b is not None) else None
-                keep.append(bias_row)
-                d.h, d.ld_h, d.n_nodes, d.Kh = ptr(h if l == 0 else None), (ld_h if l == 0 else 0), N, st.Kh
-                d.pos, d.P, d.Pd, d.X = ptr(pos if st.P is not None else None), ptr(st.P), st.Pd, ptr(st.X)
-                d.W, d.Fo, d.Wp, d.drop_p, d.seed, d.mask = ptr(st.W), st.Fo, ptr(st.Wp), cfg.drop_ps[l], st.seed, ptr(st.mask)
-                d.x_dropped, d.bias_row = int(st.x_dropped), ptr(bias_row)
-            if todo:
-                call("txe_gcn_layers_prepare", ctypes.cast(descs, ctypes.c_void_p), len(todo), ptr(csr.rowptr_in), csr.n_nodes, ptr(norm), st_)
-            else:
-                call("txe_gcn_norm", ptr(csr.rowptr_in), csr.n_nodes, ptr(norm), st_)
-            tws = _tail_ws(h)
+            for l, st in todo:
+                st.X = _empty((N, st.Kp), st)
+            _gcn_layers_prepare(csr, cfg, todo, src, ld_h, norm, collapse, z_only)
             for l, st in enumerate(states):
                 last = (l == L - 1)
                 if last and collapse:
-                    G = csr.n_graphs
-                    coef, wsum = _empty((max(N, 1),), h), _empty((max(G, 1),), h)
-                    gid = torch.empty(max(N, 1), dtype=torch.int32, device=h.device)
-                    Z, out = _empty((max(G, 1), st.Kp), h), (None if z_only else _empty((G, st.Fo), h))
-                    wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, 8)
-                    ws = _ws(wsb, h)
-                    st.cl = GcnFolded(coef, wsum, gid, Z)            # (owns what the descriptors point to, with st, csr and ctx)
-                    batch = _graph_batch(csr, N)
-                    layer = _lib.GcnFoldLayer(X=ptr(st.X), Kh=st.Kh, Pd=st.Pd, pos=ptr(rpos), Wp=ptr(st.Wp), Fo=st.Fo,
-                                              bias=ptr(st.b), drop_p=cfg.drop_ps[l], mask=ptr(st.mask), norm=ptr(norm), pw=ptr(pwf),
-                                              coef=ptr(coef), wsum=ptr(wsum), gid=ptr(gid), Z=ptr(Z), hg=ptr(out), ld_hg=st.Fo)
-                    st.desc = (batch, layer)
-                    call("txe_gcn_collapse_fwd", _lib.ref(batch), _lib.ref(layer), ptr(ws), wsb, st_)
-                    if z_only:
-                        if cfg.link is not None:
-                            cfg.link.by_k, cfg.link.one_col = True, (st.Kh + st.Pd if st.b is not None else -1)
-                        out = (Z, st.Wp)
-                        ctx.mark_non_differentiable(st.Wp)
-                        ctx.set_materialize_grads(False)
-                    if not need:
-                        st.cl = st.desc = st.mask = st.Wp = st.X = None
+                    out = _gcn_collapse_fwd(csr, st, ctx.rpos, ctx.pwf, norm, cfg.drop_ps[l], z_only, cfg.link)
+                    out = _stack_folded_result(ctx, st, out, z_only, need)
                     break
-                hw = _empty((N, st.Fop), h)
-                if table and l == 0:
-                    T, T2 = _gcn_table_projection(st, src)[:2]
-                    call("txe_gather_add_rows", ptr(T), st.Fop, ptr(_i32(src.index, h.device)), ptr(T2), st.Fop,
-                         ptr(pos) if T2 is not None else None, N, st.Fop, ptr(hw), st.Fop, st_)
-                    st.mask = st.Wp = None
-                else:
-                    call("txe_gcn_dense_fwd", ptr(st.X), N, st.Kh, st.Pd, ptr(st.Wp), st.Fo, 0.0 if st.x_dropped else cfg.drop_ps[l],
-                         None if st.x_dropped else ptr(st.mask), ptr(hw), ptr(tws), tws.numel(), st_)
-                    _launch_pending_prefetch()
-                if last:
-                    out, ld_out = _empty((N, st.Fo), h), st.Fo
-                else:
-                    out, ld_out = states[l + 1].X, states[l + 1].Kp
-                slope = cfg.act_slopes[l]
-                call("txe_gcn_aggregate_fwd", ptr(csr.rowptr_in), ptr(csr.col_src), N, ptr(hw), st.Fop, ptr(norm), ptr(st.b),
-                     0 if slope is None else 1, slope or 1.0, st.Fo, ptr(out), ld_out, st_)
+                # (not the last layer: the aggregation writes straight into the next layer's padded input)
+                out, ld_out = (_empty((N, st.Fo), st), st.Fo) if last else (states[l + 1].X, states[l + 1].Kp)
+                _gcn_layer_fwd(csr, st, src if l == 0 else None, norm, out, ld_out, cfg.drop_ps[l], cfg.act_slopes[l])
                 if not need:
                     st.mask = st.Wp = None
                     if l > 0:
                         st.X = None
-        ctx.csr, ctx.cfg, ctx.pos, ctx.norm = csr, cfg, pos, norm
-        ctx.link = cfg.link if z_only else None
-        note_route("stack", cfg.final)
-        if _CAPTURE is not None:
-            _CAPTURE.append((csr, cfg, states))
-        ctx.states = states if need else None
-        ctx.h_req = ctx.needs_input_grad[2]
-        ctx.out = out if (need and not z_only) else None
-        ctx.rpos, ctx.pwf, ctx.pw_shape = rpos, pwf, (pw.shape if pwf is not None else None)
+        ctx.norm = norm
+        ctx.out = out if (need and not z_only) else None     # (a standalone activated layer's backward reads its output)
+        _stack_end(ctx, states, need, cfg.final)
         return out
 
     @staticmethod
     def backward(ctx, d_out, *_unused):
-        csr, cfg, pos, norm, states = ctx.csr, ctx.cfg, ctx.pos, ctx.norm, ctx.states
-        if states is None:
-            raise RuntimeError(_BACKWARD_TWICE)
+        csr, cfg, norm = ctx.csr, ctx.cfg, ctx.norm
         L = cfg.n_layers
-        z_only = (cfg.final == "collapse_z")
-        if d_out is None:                          # (collapse_z does not materialise absent gradients: Z took no part in the loss)
-            ctx.states = None
-            return (None,) * (6 + 3 * L)
-        d_out = _f32(d_out)
+        collapse = cfg.final in ("collapse", "collapse_z")
+        states, d_out = _stack_bwd_begin(ctx, d_out, 3 * L)
+        if states is None:
+            return d_out
         grads = [None] * (3 * L)
-        collapse = (cfg.final == "collapse") or z_only
         d_pw = None
-        with _lib.on_device(d_out.device):
-            st_ = _lib.stream_ptr()
-            N = states[0].X.shape[0]
+        with _lib.on_device(states[0].device):
             if collapse:
                 d_pre = None
             elif cfg.act_slopes[-1] is not None:   # a standalone activated layer: undo the fused activation explicitly
                 d_pre = torch.empty_like(d_out)
-                call("txe_leaky_relu_bwd", ptr(d_out), ptr(ctx.out), cfg.act_slopes[-1], d_out.numel(), ptr(d_pre), st_)
+                call("txe_leaky_relu_bwd", ptr(d_out), ptr(ctx.out), cfg.act_slopes[-1], d_out.numel(), ptr(d_pre), _lib.stream_ptr())
             else:
                 d_pre = d_out
             ld_dpre = d_pre.stride(0) if d_pre is not None else 0
             d_X = None
             for l in range(L - 1, -1, -1):
                 st = states[l]
+                # the input of layer l>0 is leaky_relu(out_{l-1}) (fused epilogue, where layer l-1 has an activation): fold its derivative into dX
+                act_slope = cfg.act_slopes[l - 1] if l > 0 else None
                 if collapse and l == L - 1:
-                    batch, layer = st.desc
-                    G = csr.n_graphs
-                    dh, ld = _rows(d_out)
-                    act_on = l > 0 and cfg.act_slopes[l - 1] is not None
-                    d_X = _empty((N, st.Kp), d_out)
-                    if z_only:                     # d_out IS dZ; the consumer of Z left dW (and d_b as row Kt) in the FoldLink, [Kp][Fo]
-                        part = ctx.link.part if ctx.link is not None else None
-                        if part is None or ctx.link.S != 1 or tuple(part.shape) != (st.Kp, st.Fo):
-                            raise RuntimeError("folded GCN output layer: the consumer of Z left no weight gradient in the FoldLink")
-                        Kt = st.Kh + st.Pd
-                        dW, d_b = part[:Kt], (part[Kt] if st.b is not None else None)
-                    else:
-                        dW = torch.empty_like(st.W)
-                        d_b = torch.empty_like(st.b) if st.b is not None else None
-                    dP = torch.empty_like(st.P) if st.P is not None else None
-                    d_pw = torch.empty_like(ctx.pwf) if ctx.pwf is not None else None
-                    # (what backward adds to the layer's descriptor: the vocabulary, and the positions as the position table's gradient reads them)
-                    layer.pos, layer.vocab = ptr(pos if st.P is not None else ctx.rpos), max(cfg.vocab, ctx.pwf.numel() if ctx.pwf is not None else 0)
-                    wsb = pure("txe_gcn_collapse_ws_bytes", N, G, st.Kh, st.Pd, st.Fo, max(layer.vocab, 8))
-                    ws = _ws(wsb, d_out)
-                    gdesc = _lib.GcnFoldGrads(dW=None if z_only else ptr(dW), d_b=None if z_only else ptr(d_b), dP=ptr(dP), d_pw=ptr(d_pw))
-                    call("txe_gcn_collapse_bwd", _lib.ref(batch), _lib.ref(layer), ptr(dh), ld, int(act_on),
-                         (cfg.act_slopes[l - 1] if act_on else 1.0), ptr(d_X), _lib.ref(gdesc), int(z_only), ptr(ws), wsb, st_)
-                    grads[3 * l:3 * l + 3] = [dW, d_b, dP]
-                    if l > 0:
-                        d_pre, ld_dpre = d_X, st.Kp
-                    continue
-                d_hw = _empty((N, st.Fop), d_out)
-                d_b = torch.empty_like(st.b) if st.b is not None else None
-                wsb = pure("txe_gcn_aggregate_bwd_ws_bytes", N, st.Fo)
-                ws = _ws(wsb, d_out)
-                call("txe_gcn_aggregate_bwd", ptr(csr.rowptr_out), ptr(csr.col_dst), N, ptr(d_pre), ld_dpre, ptr(norm), st.Fo, ptr(d_hw),
-                     st.Fop, ptr(d_b), ptr(ws), wsb, st_)
-                need_dh = (l > 0) or ctx.h_req
-                act_on = l > 0 and cfg.act_slopes[l - 1] is not None
-                d_X = _empty((N, st.Kp), d_out) if (need_dh or st.Pd > 0) else None
-                dW = torch.empty_like(st.W)
-                dP = torch.empty_like(st.P) if st.P is not None else None
-                wsb2 = pure("txe_gcn_dense_ws_bytes", N, st.Kh, st.Pd, st.Fo, cfg.vocab)
-                ws2 = _ws(wsb2, d_out)
-                call("txe_gcn_dense_bwd", ptr(st.X), N, st.Kh, st.Pd, ptr(pos if st.P is not None else None), cfg.vocab, ptr(st.Wp), st.Fo,
-                     cfg.drop_ps[l], ptr(st.mask), ptr(d_hw), int(need_dh), int(act_on), (cfg.act_slopes[l - 1] if act_on else 1.0),
-                     ptr(d_X), ptr(dW), ptr(dP), int(st.x_dropped), ptr(ws2), wsb2, st_)
+                    d_X, dW, d_b, dP, d_pw = _gcn_collapse_bwd(csr, st, ctx.rpos, ctx.pwf, cfg.vocab, d_out, act_slope,
+                                                               cfg.final == "collapse_z", ctx.link)
+                else:
+                    d_X, dW, d_b, dP = _gcn_layer_bwd(csr, st, norm, cfg.vocab, cfg.drop_ps[l], d_pre, ld_dpre, (l > 0) or ctx.h_req, act_slope)
                 grads[3 * l:3 * l + 3] = [dW, d_b, dP]
                 if l > 0:
-                    d_pre, ld_dpre = d_X, st.Kp
-            d_h = d_X[:, :states[0].Kh].contiguous() if ctx.h_req else None
-        ctx.states = None
-        if d_pw is not None:
-            d_pw = d_pw.reshape(ctx.pw_shape)
-        return (None, None, d_h, None, None, d_pw, *grads)
+                    d_pre, ld_dpre = d_X, st.Kp            # its first Fo(l-1) columns are d(pre-activation out_{l-1})
+            return _stack_bwd_end(ctx, states, d_X, d_pw, grads)
 
 
 # ================================================================================================================

@@ -331,7 +331,7 @@ def test_layer_states_have_every_field_from_the_start():
     """ops._GatLayerState / _GcnLayerState: every slot is readable on a fresh state -- buffers and the folded layer's record `cl` None,
     the flags False -- so nothing has to ask whether a field exists"""
     from taxoexpan_amd import ops
-    for cls, flags in ((ops._GatLayerState, ("vx", "x_dropped", "prepared")), (ops._GcnLayerState, ("x_dropped",))):
+    for cls, flags in ((ops._GatLayerState, ("vx", "x_dropped")), (ops._GcnLayerState, ("x_dropped",))):
         st = cls()
         for name in cls.__slots__:
             getattr(st, name)                                                    # (AttributeError: a slot __init__ forgot)
