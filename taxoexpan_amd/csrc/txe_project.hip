@@ -871,6 +871,12 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
     const int F = H * D, H2 = 2 * H, Fe = F + H2, Fp = round_up(Fe, 128), Kt = Kh + Pd, Kp = round_up(Kt, 32);
     DenseWs p = plan_dense_ws(ws, n_nodes, Fp, H2, Kp, Pd, vocab);
     if (ws_bytes < p.total) return TXE_ERR_WORKSPACE;
+    // (every rejection in front of the first launch: the bf16 d_X route's workspace, and a weight gradient that would take the fp32
+    //  product without a stored X)
+    if ((phases & TXE_DENSE_DX) && (phases & TXE_DENSE_DX_SPLIT) && need_dh && n_nodes > 0 && ws_bytes < p.total + dense_bwd_split_bytes(n_nodes, Fp, Kt))
+        return TXE_ERR_WORKSPACE;                                   // (the route is the caller's choice, not the buffer's size)
+    const bool dw_split = Xt && x_dropped + (feat_drop_p == 0.f) > 0 && split_tn_eligible(Fp, Kp) && split_tn_fits(n_nodes, Fp) && n_nodes > 0;
+    if ((phases & TXE_DENSE_DW) && !dw_split && !X) return TXE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     int rc;
     // ---- d_X[:, c0:Kt] = d_Y * Wp[:, c0:Kt] ----
@@ -893,7 +899,6 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
         rc = dxpos_launch(da, s);
         if (rc) return rc;
     } else if ((phases & TXE_DENSE_DX) && (phases & TXE_DENSE_DX_SPLIT) && need_dh && n_nodes > 0) {
-        if (ws_bytes < p.total + dense_bwd_split_bytes(n_nodes, Fp, Kt)) return TXE_ERR_WORKSPACE;     // (the route is the caller's choice, not the buffer's size)
         // the whole d_X = d_Y Wp on the bf16 pipe (txe_gemm_split.h): d_Y packed as the row operand, Wp -- given as the transpose of
         // the column operand -- packed from its columns; dropout mask and leaky' factor in the store loop (epi_store_one's arithmetic)
         char* sw = (char*)ws + p.total;
@@ -929,13 +934,12 @@ int txe_gat_dense_bwd(const float* X, int n_nodes, int Kh, int Pd, const int* po
     E.split_stride = (long long)Fp * Kp;
     E.alg_flops = 2.0 * Fe * (double)Kt * n_nodes;
     const int splits = p.splits;
-    if ((phases & TXE_DENSE_DW) && Xt && x_dropped + (feat_drop_p == 0.f) > 0 && split_tn_eligible(Fp, Kp) && split_tn_fits(n_nodes, Fp) && n_nodes > 0) {
+    if ((phases & TXE_DENSE_DW) && dw_split) {
         // the same slices on the bf16 pipe (txe_gemm_split.h): X packed contraction-major by the forward pass, d_Y split in the loader
         const int ks = round_up((n_nodes + splits - 1) / splits, 16);
         rc = gemm_tn_split_launch(d_Y, Fp, Fp, Xt, Kp, n_nodes, splits, ks, p.part, Kp, E.split_stride, E.alg_flops, s);
         if (rc) return rc;
     } else if (phases & TXE_DENSE_DW) {
-        if (!X) return TXE_ERR_ARG;
         rc = gemm_tn(A, B, E, Fp, Kp, n_nodes, splits, s);
         if (rc) return rc;
     }
