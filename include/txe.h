@@ -293,7 +293,10 @@ int txe_score_block(const float* Q, long long ld_q, int nq, const float* U, long
  * themselves: give all of them a workspace or none.
  * u_packed (NULL = pack here): the candidates' planes, txe_split_pack(U, ld_u, G, r, side 1, ...) into txe_split_packed_bytes(G, r) bytes,
  * made ONCE per candidate set -- the loop over query blocks then packs only its queries, and sws needs txe_split_packed_bytes(nq, r)
- * (rounded up to 256) bytes only.  Same planes, same kernel: bit-identical scores either way. */
+ * (rounded up to 256) bytes only.  Same planes, same kernel: bit-identical scores either way.
+ * TXE_ERR_ARG (all four entry points, before any launch): a negative count, r < 1, ld_u < r, a NULL operand or output, and with more than
+ * one query (a single row has no pitch) ld_q < r -- for txe_score_block also ld_s < G; txe_score_topk_block: k < 1, k > 8, G < 1.
+ * TXE_ERR_WORKSPACE (before any launch): sws given and sws_bytes too small. */
 size_t txe_score_split_ws_bytes(int nq, int G, int r);
 
 /* fused scoring + ranking: the score tile is compared in the GEMM epilogue and never stored.  counts [pos_off[nq]] int32
@@ -318,8 +321,9 @@ int txe_score_positives(const float* Q, long long ld_q, int nq, const float* Up,
  * + idx_base (the first row of a candidate shard), best first, -1 where a row has fewer than k candidates; out_key [nq][k] (may be
  * NULL) = the scores, negated when smaller is better.  Order = Python's stable sort: better score first, equal scores by ascending
  * candidate row; NaN ranks last.  1 <= k <= 8.
- * txe_topk_merge alone: best k of `cnt` (key, idx) entries per row (idx == INT_MAX: empty slot) -- also the merge of the per-rank
- * lists of a candidate-sharded loop. */
+ * txe_topk_merge alone: best k of `cnt` (key, idx) entries per row (idx == INT_MAX: empty slot; a NaN key counts as -inf) -- also the
+ * merge of the per-rank lists of a candidate-sharded loop.  Behind a row's last real entry out_idx is -1 and out_key -inf (as
+ * txe_select_k's unused slots), cnt == 0 included: every slot of both outputs is written by every call. */
 int txe_score_topk_tiles(int G);
 int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
                          int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,

@@ -762,6 +762,10 @@ static inline size_t score_split_bytes(int nq, int G, int r) {
     const size_t a = (split_packed_bytes(nq, r) + 255) / 256 * 256, b = (split_packed_bytes(G, r) + 255) / 256 * 256;
     return a + b;
 }
+// what score_split asks of sws_bytes: the queries' planes, and the candidates' unless the caller made them (u_packed)
+static inline size_t score_split_need(int nq, int G, int r, bool u_packed) {
+    return u_packed ? (split_packed_bytes(nq, r) + 255) / 256 * 256 : score_split_bytes(nq, G, r);
+}
 // 1 = done on the split route, 0 = not taken (no workspace), < 0 = error
 // u_packed: the candidates' planes (txe_split_pack(U, ld_u, G, r, side 1)) made ONCE per candidate set by the caller -- the loop over query
 // blocks then packs only its queries (a MAG-Full block packed 620 MB of U again for every 1,024 queries: 10.8 % of the inference profile)
@@ -769,7 +773,7 @@ static int score_split(const float* Q, long long ld_q, int nq, const float* U, l
                        size_t sws_bytes, const void* u_packed, hipStream_t s) {
     if (!sws || nq < 1 || G < 1) return 0;
     const size_t a = (split_packed_bytes(nq, r) + 255) / 256 * 256;
-    if (sws_bytes < (u_packed ? a : score_split_bytes(nq, G, r))) return TXE_ERR_WORKSPACE;
+    if (sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;
     char* w = (char*)sws;
     int rc = split_pack_launch(Q, ld_q, nq, r, 0, w, s);
     if (rc) return rc;
@@ -788,6 +792,7 @@ size_t txe_score_split_ws_bytes(int nq, int G, int r) { return (nq < 1 || G < 1 
 int txe_score_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp, float* S,
                     long long ld_s, void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, const void* u_packed, void* stream) {
     if (nq < 0 || G < 0 || r < 1 || ld_u < r || !Q || !U || !S) return TXE_ERR_ARG;
+    if (nq > 1 && (ld_q < r || ld_s < G)) return TXE_ERR_ARG;      // (a single row has no pitch)
     VMat A = vmat_plain(Q, ld_q, nq, r);
     VMat B = vmat_plain(U, ld_u, G, r);
     Epi E = epi_plain(S, ld_s, G);
@@ -810,7 +815,7 @@ int txe_score_block(const float* Q, long long ld_q, int nq, const float* U, long
 // computed and only those pairs are stored: ~(nq/128 + n_pos/128) tiles where the [nq x n_pos] product has their product.
 int txe_score_positives(const float* Q, long long ld_q, int nq, const float* Up, long long ld_u, int n_pos, int r, int apply_exp,
                         const int* pos_off, float* thr, void* sws, size_t sws_bytes, void* stream) {
-    if (nq < 0 || n_pos < 0 || r < 1 || ld_u < r || !Q || !Up || !pos_off || !thr) return TXE_ERR_ARG;
+    if (nq < 0 || n_pos < 0 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || !Q || !Up || !pos_off || !thr) return TXE_ERR_ARG;
     if (nq == 0 || n_pos == 0) return TXE_OK;
     VMat A = vmat_plain(Q, ld_q, nq, r);
     VMat B = vmat_plain(Up, ld_u, n_pos, r);
@@ -835,7 +840,7 @@ int txe_score_positives(const float* Q, long long ld_q, int nq, const float* Up,
 int txe_score_count_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
                           const int* pos_off, const float* thr, int larger_is_better, int* counts, void* sws, size_t sws_bytes,
                           const void* u_packed, void* stream) {
-    if (nq < 0 || G < 0 || r < 1 || ld_u < r || !Q || !U || !pos_off || !thr || !counts) return TXE_ERR_ARG;
+    if (nq < 0 || G < 0 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || !Q || !U || !pos_off || !thr || !counts) return TXE_ERR_ARG;
     if (nq == 0 || G == 0) return TXE_OK;
     VMat A = vmat_plain(Q, ld_q, nq, r);
     VMat B = vmat_plain(U, ld_u, G, r);
@@ -870,9 +875,11 @@ extern "C" {
 int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
                          int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,
                          float* out_key, void* sws, size_t sws_bytes, const void* u_packed, void* stream) {
-    if (nq < 0 || G < 1 || r < 1 || ld_u < r || k < 1 || k > TOPK_MAX || !Q || !U || !part_key || !part_idx || !floor_ws || !out_idx)
+    if (nq < 0 || G < 1 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || k < 1 || k > TOPK_MAX || !Q || !U || !part_key || !part_idx || !floor_ws ||
+        !out_idx)
         return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
+    if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
     hipLaunchKernelGGL(topk_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, (hipStream_t)stream, floor_ws, nq);
     TXE_CHECK_LAUNCH();
     VMat A = vmat_plain(Q, ld_q, nq, r);

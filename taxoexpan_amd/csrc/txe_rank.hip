@@ -134,6 +134,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
             const long long e = e0 + u * 64 + l;
             const long long ec = e < cnt ? e : cnt - 1;
             kv[u] = kp[ec]; iv[u] = (e < cnt) ? ip[ec] : 0x7fffffff;
+            kv[u] = (kv[u] != kv[u]) ? -INFINITY : kv[u];       // a NaN key compares false with everything: it ranks last, as -inf
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -170,15 +171,12 @@ using namespace txe;
 
 extern "C" {
 
-// keys / idx [nq][cnt] -> out_idx [nq][k] (+ idx_base; -1 where a row holds fewer than k real entries), out_key [nq][k] (may be NULL).
-// Entries with idx == INT_MAX are empty slots.  1 <= k <= 8.
+// keys / idx [nq][cnt] -> out_idx [nq][k] (+ idx_base; -1 where a row holds fewer than k real entries), out_key [nq][k] (may be NULL; -inf
+// in the slots behind a row's last real entry).  Entries with idx == INT_MAX are empty slots; a NaN key counts as -inf.  1 <= k <= 8.
+// cnt == 0 runs the same kernel (no entry is read): every slot -1 / -inf.
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key, void* stream) {
     if (nq < 0 || cnt < 0 || k < 1 || k > TOPK_MAX || !keys || !idx || !out_idx) return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
-    if (cnt == 0) {
-        if (hipMemsetAsync(out_idx, 0xff, (size_t)nq * k * sizeof(int), (hipStream_t)stream) != hipSuccess) return TXE_ERR_LAUNCH;
-        return TXE_OK;
-    }
     ProfScope prof("topk_merge_kernel", (hipStream_t)stream, 8.0 * nq * (double)cnt, 1);
     hipLaunchKernelGGL(topk_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, keys, idx, nq, cnt, k, idx_base, out_idx, out_key);
     TXE_CHECK_LAUNCH();
