@@ -375,6 +375,47 @@ int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const fl
                              const float* mw, int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws,
                              int* out_idx, float* out_key, void* stream);
 
+/* ---- all-candidate scoring loop of the NTN matcher (model_zoo.py:331-346 under test_fast.py:121-123 / infer.py:97-99) ---------------
+ * W = W.weight [k][l][r], b = W.bias [k], V = V.weight [k][l+r] = [V1 | V2], u = u_R.weight [k].  For candidate g, query q, slice j < k:
+ *     S[q][g] = sum_j u_j tanh((<q, U_j[g]> + a_j[g]) + c_j[q]),   U_j = hg W_j,   a_j[g] = V1_j . hg[g] + b_j,   c_j[q] = V2_j . q
+ * 1 <= k <= 16.  The U_j come from txe_bilinear_project: once per slice, or in one call on the stacked weight [l][k * rp] -- slice j of
+ * candidate g then lies at U + g * ld_u + j * slice_u.  The pair work is the score GEMM's 128 x 128 tile (csrc/txe_ntn_score.hip: fp32
+ * MFMA, full k order, never split along the reduction) run once per slice inside one workgroup, each slice folded into the tile by
+ * s = fma(u_j, tanh((acc + a_j[g]) + c_j[q]), s); the finished tile goes to the score GEMM's own epilogue.  No [nq][G][k] tensor is
+ * written; every mode below sees bit-identical scores, and a score is a function of its two rows' values only.  tanh: relatively
+ * accurate down to zero, exactly +-1 where it saturates (+-Inf included), NaN for NaN.
+ * The four scoring entry points mirror txe_score_block / txe_score_positives / txe_score_count_block / txe_score_topk_block: the same
+ * pos_off / thr / counts / part_key / part_idx / floor_ws / idx_base conventions, the same txe_score_topk_tiles(G); positives take the
+ * GATHERED candidate side (U and a of the queries' true parents, query by query: G = n_pos) like txe_score_positives.
+ * a is [k][G] on pitch ld_a, c is [k][nq] on pitch ld_c (slice-major: a tile reads 128 consecutive floats per slice).
+ * TXE_ERR_ARG before any device work: k < 1 or k > 16, r < 1 (l < 1), a negative size, a pitch below its width (ld_u < r, slice_u < r,
+ * ld_q < r for more than one query, ld_a < G, ld_c < nq, ld_s < G), a NULL required pointer, a top-k size outside 1..8 (or G < 1 there).
+ * TXE_OK without a launch when nq == 0 or G == 0. */
+/* model_zoo.py:331-346, test_fast.py:121-123 -- candidate side, once per candidate set: a [k][G] from hg [G][l], V1 (rows of V.weight, pitch
+ * ld_v = l + r) and b */
+int txe_ntn_project(const float* hg, long long ld_hg, int G, int l, const float* V1, long long ld_v, const float* b, int k, float* a,
+                    long long ld_a, void* stream);
+/* model_zoo.py:331-346, test_fast.py:121-123 -- query side, per query block: c [k][nq] from Q [nq][r] and V2 = V.weight + l (pitch ld_v) */
+int txe_ntn_query_project(const float* Q, long long ld_q, int nq, int r, const float* V2, long long ld_v, int k, float* c, long long ld_c,
+                          void* stream);
+/* model_zoo.py:331-346, test_fast.py:121-123 -- S [nq][G] (pitch ld_s) */
+int txe_ntn_score_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                        const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, float* S, long long ld_s,
+                        void* stream);
+/* model_zoo.py:331-346, test_fast.py:121-123 -- thr[j] = S[q][j] for j in [pos_off[q], pos_off[q+1]) over the gathered candidate side */
+int txe_ntn_score_positives(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                            const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, const int* pos_off,
+                            float* thr, void* stream);
+/* model_zoo.py:331-346, test_fast.py:121-123 -- counts[j] += #{g < G : S[q][g] strictly better than thr[j]} */
+int txe_ntn_score_count_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                              const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, const int* pos_off,
+                              const float* thr, int larger_is_better, int* counts, void* stream);
+/* model_zoo.py:331-346, test_fast.py:121-123 / infer.py:100-106 -- the best `topk` candidates per query, in txe_score_topk_block's order */
+int txe_ntn_score_topk_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                             const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
+                             int topk, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx, float* out_key,
+                             void* stream);
+
 /* plain dense product on the fp32 MFMA GEMM (tests / micro-benchmarks).  layout 0: C = A[M][K] B[N][K]^T; 1: C = A[M][K] B[K][N];
  * 2: C = A[K][M]^T B[K][N].  splits > 1: `splits` partial products at C + z*M*ldc.  ws/ws_bytes (optional, txe_gemm_tail_ws_bytes):
  * scratch that lets the last, partial round of workgroups be split along k ("tail splitting").

@@ -90,6 +90,12 @@ SIGNATURES = {
     "txe_mlp_score_positives": (I, [P, P, I, P, P, P, I, I, P, P, P, I, P, P]),
     "txe_mlp_score_count_block": (I, [P, P, I, P, P, P, I, I, P, P, P, I, P, P]),
     "txe_mlp_score_topk_block": (I, [P, P, I, P, P, P, I, I, P, I, I, I, P, P, P, P, P, P]),
+    "txe_ntn_project": (I, [P, L, I, I, P, L, P, I, P, L, P]),
+    "txe_ntn_query_project": (I, [P, L, I, I, P, L, I, P, L, P]),
+    "txe_ntn_score_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, P, L, P]),
+    "txe_ntn_score_positives": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, P, P, P]),
+    "txe_ntn_score_count_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, P, P, I, P, P]),
+    "txe_ntn_score_topk_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, I, I, P, P, P, P, P, P]),
     "txe_score_split_ws_bytes": (SZ, [I, I, I]),
     "txe_score_count_block": (I, [P, L, I, P, L, I, I, I, P, P, I, P, P, SZ, P, P]),
     "txe_score_positives": (I, [P, L, I, P, L, I, I, I, P, P, P, SZ, P]),

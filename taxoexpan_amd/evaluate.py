@@ -34,7 +34,7 @@ CASE_METRICS = ("macro_mr", "micro_mr", "hit_at_1", "hit_at_3", "hit_at_5", "mrr
 
 def _score_blocks(model, hg, qf, qblock):
     """score blocks [<= qblock queries, G candidates] of the per-query loop test_fast.py:121-123 / infer.py:96-98: the prepared matcher's
-    block kernel for BIM / LBM / MLP (scoring.prepare_matcher), the literal expand loop for any other matcher"""
+    block kernel for BIM / LBM / MLP / NTN (scoring.prepare_matcher), the literal expand loop for any other matcher"""
     pm = None
     for q0 in range(0, qf.shape[0], qblock):
         if fused_matcher_ok(model.match):
@@ -45,7 +45,7 @@ def _score_blocks(model, hg, qf, qblock):
 
 
 def _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock):
-    """the `topk` best candidates of every query, best first (infer.py:100-106 / test_fast.py:125-131): BIM / LBM / MLP with topk <= 8
+    """the `topk` best candidates of every query, best first (infer.py:100-106 / test_fast.py:125-131): BIM / LBM / MLP / NTN with topk <= 8
     through the fused score + select kernels (no score matrix), anything else by materialising score blocks"""
     if fused_matcher_ok(model.match) and 1 <= topk <= 8 and hg.shape[0] > 0 and qf.shape[0] > 0:
         return topk_parents_fused(model.match, hg, qf, cand_ids, topk, larger_is_better, block=qblock)
@@ -54,7 +54,7 @@ def _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock):
 
 
 def _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock):
-    """ranks of every query's true parents: fused (no score matrix) for BIM / LBM / MLP; any other matcher materialises score blocks with
+    """ranks of every query's true parents: fused (no score matrix) for BIM / LBM / MLP / NTN; any other matcher materialises score blocks with
     the literal loop and ranks them on device (ops.rank_block)"""
     from . import ops
     if fused_matcher_ok(model.match):
@@ -82,7 +82,7 @@ def _retrieval_masks(dataset, queries, index):
 def _retrieved_groups(model, hg, qf, pos_off, pos_idx, ridx, larger_is_better, qblock):
     """the retrieve-then-rank instances of dataset.py:316-330 as one labelled score vector: per query its positives (label 1) followed by
     its k retrieved candidate rows `ridx` (label 0; a -1 slot scores worst, so it never counts against a positive).  Only these pairs
-    are scored: the prepared matcher's gathered route for BIM / LBM / MLP, model.match on the gathered rows for anything else.
+    are scored: the prepared matcher's gathered route for BIM / LBM / MLP / NTN, model.match on the gathered rows for anything else.
     Returns (score [B] fp32, label [B] int32, ret_dst [Q, k] = where each retrieved slot sits in them)."""
     dev = hg.device
     Q, k = ridx.shape

@@ -10,7 +10,8 @@ libtxe (include/txe.h) instead of DGL + torch.
     MeanReadout/WeightedMeanReadout      model_zoo.py:227-242 -> txe_readout_*
     ConcatReadout/SumReadout/MaxReadout  model_zoo.py:244-276 -> txe_readout_multi_*
     MLP        model_zoo.py:281-298      MLP        -> txe_linear_*  
-    NTN        model_zoo.py:331-346      NTN        -> k x txe_bilinear_pair_* + txe_linear_* (not reachable from model/model.py)
+    NTN        model_zoo.py:331-346      NTN        -> k x txe_bilinear_pair_* + txe_linear_*  (+ score_all / txe_ntn_* for the eval loop;
+                                                       not reachable from model/model.py)
     BIM/LBM    model_zoo.py:301-328      BIM/LBM    -> txe_bilinear_pair_*  (+ score_all for the eval loop)
 Graph argument: a taxoexpan_amd.graph.(Batched)DGLGraph -- the DGL-0.4 surface of the reference's loaders.
 Side effects the callers rely on are kept: PGAT/PGCN pop g.ndata['pos'] (model_zoo.py:163,212); WeightedMeanReadout

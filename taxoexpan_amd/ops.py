@@ -2201,3 +2201,176 @@ def mlp_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=
         call("txe_mlp_score_topk_block", *_mlp_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]),
              ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
     return idx, key
+
+
+# ================================================================================================================
+# NTN matcher (model_zoo.py:331-346) on the all-candidate loop: txe_ntn_* (the score GEMM's tile once per bilinear slice, tanh and the
+# sum over slices in its registers, the score GEMM's own store / pick / count / best-k epilogue)
+# ================================================================================================================
+NTN_MAX_K = 16          # slices the kernel's entry points accept
+
+
+class NTNPrepared:
+    """the candidate side of an NTN matcher, once per candidate set: full [max(G, 1), k * rp] -- slice j of candidate g, U_j[g] = hg[g] W_j,
+    lies at full[g, j * rp : j * rp + r], zero-padded to rp columns (bilinear_prepare's rule: whole 32-column k-tiles) --
+    a [k, max(G, 1)] = V1 hg^T + b, u [k] = u_R.weight, V2 [k, r] = the query half of V.weight"""
+    __slots__ = ("full", "a", "u", "V2", "G", "r", "rp", "k")
+
+    def __init__(self, full, a, u, V2, G, r, rp, k):
+        self.full, self.a, self.u, self.V2, self.G, self.r, self.rp, self.k = full, a, u, V2, G, r, rp, k
+
+    def slice(self, j):
+        """U_j as a [G, r] view"""
+        return self.full[:self.G, j * self.rp:j * self.rp + self.r]
+
+    def gather(self, idx):
+        """the rows idx of every slice (with their zero padding) and of a: the candidate side of ntn_positive_scores"""
+        idx = idx.long()
+        return NTNPrepared(self.full.index_select(0, idx), self.a.index_select(1, idx), self.u, self.V2, int(idx.numel()), self.r, self.rp, self.k)
+
+
+class NTNQueries:
+    """the query side of a block: Qp [nq, rp] = the queries zero-padded like the candidates' slices, c [k, nq] = V2 Q^T"""
+    __slots__ = ("Qp", "c", "n")
+
+    def __init__(self, Qp, c, n):
+        self.Qp, self.c, self.n = Qp, c, n
+
+    @property
+    def shape(self):
+        return (self.n, self.Qp.shape[1])
+
+    def __getitem__(self, sl):
+        """a row block (slice) of a prepared query set: rows are independent, so a block of the whole set's preparation is the block's own"""
+        assert isinstance(sl, slice) and sl.step in (None, 1)
+        lo, hi, _ = sl.indices(self.n)
+        hi = max(hi, lo)
+        return NTNQueries(self.Qp[lo:hi], self.c[:, lo:hi], hi - lo)
+
+
+def ntn_project(hg, match):
+    """prepare the candidate side of an NTN matcher for scoring: the k products U_j = hg W_j as ONE txe_bilinear_project on the stacked,
+    zero-padded weight [l, k * rp] (the route bilinear_prepare takes: the bf16 pipe's fp32-accurate product unless _NO_SPLIT_GEMM; made
+    once, so every scoring mode reads the same values) and a = V1 hg^T + b (txe_ntn_project).  Returns NTNPrepared."""
+    W, b, V, u = match.W.weight, match.W.bias, match.V.weight, match.u_R.weight
+    _need_cuda(hg, W, b, V, u)
+    hg, ld = _rows(hg)
+    G, l = hg.shape
+    k, lw, r = W.shape
+    assert lw == l and V.shape == (k, l + r) and u.numel() == k and b is not None and b.numel() == k, \
+        "ntn_project: W = Bilinear(l, r, k), V = Linear(l + r, k), u_R = Linear(k, 1)"
+    assert 1 <= k <= NTN_MAX_K, f"ntn_project: 1 <= k <= {NTN_MAX_K}"
+    rp = (r + 31) // 32 * 32
+    Wst = torch.zeros((l, k, rp), dtype=torch.float32, device=hg.device)
+    Wst[:, :, :r].copy_(W.detach().permute(1, 0, 2))
+    full = _empty((max(G, 1), k * rp), hg)
+    a = _empty((k, max(G, 1)), hg)
+    V1 = _f32(V.detach()[:, :l])
+    with _lib.on_device(hg.device):
+        if G > 0:
+            swb = 0 if _NO_SPLIT_GEMM else pure("txe_gemm_plain_split_ws_bytes", G, k * rp, l)
+            sws = _ws(swb, hg) if swb else None
+            call("txe_bilinear_project", ptr(hg), ld, G, l, ptr(Wst), k * rp, ptr(full), k * rp, ptr(sws), swb, _lib.stream_ptr())
+            call("txe_ntn_project", ptr(hg), ld, G, l, ptr(V1), l, ptr(_f32(b.detach())), k, ptr(a), a.stride(0), _lib.stream_ptr())
+        else:
+            full.zero_()
+            a.zero_()
+    return NTNPrepared(full, a, _f32(u.detach().reshape(-1)), _f32(V.detach()[:, l:]), G, r, rp, k)
+
+
+def ntn_prepare_queries(Q, prep):
+    """the query side of a block (or of a whole query set: NTNQueries slices into blocks): the padded queries and c (txe_ntn_query_project)"""
+    if isinstance(Q, NTNQueries):
+        return Q
+    _need_cuda(Q)
+    Q, ldq = _rows(Q)
+    nq, r = Q.shape
+    assert r == prep.r, "ntn_prepare_queries: query width != the matcher's r"
+    Qp = torch.zeros((max(nq, 1), prep.rp), dtype=torch.float32, device=Q.device)
+    c = _empty((prep.k, max(nq, 1)), Q)
+    if nq > 0:
+        Qp[:nq, :r].copy_(Q)
+        with _lib.on_device(Q.device):
+            call("txe_ntn_query_project", ptr(Q), ldq, nq, r, ptr(prep.V2), r, prep.k, ptr(c), c.stride(0), _lib.stream_ptr())
+    return NTNQueries(Qp[:nq], c[:, :nq], nq)
+
+
+def _ntn_args(qp, prep):
+    """(Q, ld_q, nq, U, ld_u, slice_u, G, r, a, ld_a, c, ld_c, u, k) of the txe_ntn_score_* entry points: both operands padded to rp, the
+    reduction runs over all of it (zeros add exactly nothing)"""
+    return (ptr(qp.Qp), prep.rp, qp.n, ptr(prep.full), prep.full.stride(0), prep.rp, prep.G, prep.rp, ptr(prep.a), prep.a.stride(0),
+            ptr(qp.c), qp.c.stride(0), ptr(prep.u), prep.k)
+
+
+def ntn_score_block(Q, prep, out=None):
+    """S[q][g] = match(hg[g], Q[q]) of an NTN matcher for a block of queries (raw [nq, r] or NTNQueries) against every candidate
+    (txe_ntn_score_block).  out: [nq, G] view with unit column stride; default: rows on a 16-byte pitch like score_block."""
+    qp = ntn_prepare_queries(Q, prep)
+    G = prep.G
+    S = out if out is not None else _empty((qp.n, (G + 3) // 4 * 4), prep.full)[:, :G]
+    assert S.dtype == torch.float32 and (S.numel() == 0 or S.stride(1) == 1)
+    if qp.n > 0 and G > 0:
+        with _lib.on_device(prep.full.device):
+            call("txe_ntn_score_block", *_ntn_args(qp, prep), ptr(S), S.stride(0) if qp.n > 1 else max(S.stride(0), G), _lib.stream_ptr())
+    return S
+
+
+def ntn_positive_scores(Q, prep, pos_off, pos_idx, out=None, rows_valid=False):
+    """thr[j] = match(hg[pos_idx[j]], Q[q]) for each query's true parents: the score kernel's own tiles over the GATHERED candidate side
+    (NTNPrepared.gather), only those along the staircase of (query, own positive) pairs -- bit-identical to the stored block.  pos_idx
+    outside [0, G) (a positive that lives in another candidate shard) gives 0; rows_valid: the caller promises there is none (and masks
+    such positives itself)."""
+    qp = ntn_prepare_queries(Q, prep)
+    dev = prep.full.device
+    pos_off = _i32(pos_off, dev)
+    pos_idx = pos_idx.to(dev)
+    n_pos = int(pos_idx.numel())
+    thr = out if out is not None else torch.zeros(n_pos, dtype=torch.float32, device=dev)
+    assert thr.dtype == torch.float32 and thr.is_contiguous() and thr.numel() >= n_pos
+    if n_pos > 0 and qp.n > 0 and prep.G > 0:
+        rows = pos_idx.long()
+        ok = None
+        if not rows_valid:
+            ok = (rows >= 0) & (rows < prep.G)
+            rows = torch.where(ok, rows, torch.zeros_like(rows))
+        gp = prep.gather(rows)
+        with _lib.on_device(dev):
+            call("txe_ntn_score_positives", *_ntn_args(qp, gp), ptr(pos_off), ptr(thr), _lib.stream_ptr())
+        if ok is not None:
+            thr[:n_pos].copy_(torch.where(ok, thr[:n_pos], torch.zeros((), device=dev)))
+    return thr[:n_pos]
+
+
+def ntn_score_count_block(Q, prep, pos_off, thr, larger_is_better=True, counts=None):
+    """fused scoring + ranking of one query block (txe_ntn_score_count_block): int32 counts [n_pos] of candidates strictly better than
+    each positive's threshold; no [nq x G] block is materialised.  counts (zeroed by the caller) accumulate: shards add."""
+    qp = ntn_prepare_queries(Q, prep)
+    dev = prep.full.device
+    pos_off = _i32(pos_off, dev)
+    thr = _f32(thr)
+    if counts is None:
+        counts = torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=dev)
+    if thr.numel() == 0 or qp.n == 0 or prep.G == 0:
+        return counts
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
+    with _lib.on_device(dev):
+        call("txe_ntn_score_count_block", *_ntn_args(qp, prep), ptr(pos_off), ptr(thr), int(larger_is_better), ptr(counts), _lib.stream_ptr())
+    return counts
+
+
+def ntn_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=None):
+    """fused scoring + best-k selection of one query block (txe_ntn_score_topk_block): (idx int32 [nq, k] = candidate rows + idx_base,
+    key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(8, G).  scratch: dict reused across blocks."""
+    qp = ntn_prepare_queries(Q, prep)
+    dev = prep.full.device
+    G, nq = prep.G, qp.n
+    assert 1 <= k <= 8 and k <= G, "ntn_score_topk_block: 1 <= k <= min(8, candidates)"
+    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    key = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if nq == 0:
+        return idx, key
+    with _lib.on_device(dev):
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * k, prep.full)
+        call("txe_ntn_score_topk_block", *_ntn_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]),
+             ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
+    return idx, key

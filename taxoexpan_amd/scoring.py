@@ -60,26 +60,88 @@ class _PreparedMLP:
         return ops.mlp_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
 
 
+class _PreparedNTN:
+    """the NTN matcher over a candidate set: the k slices U_j = hg W_j and a = V1 hg^T + b once (ops.ntn_project), every query block
+    through the score GEMM's tile run once per slice with tanh and the sum over slices in registers (txe_ntn_*) -- the same four modes,
+    the same scratch and count conventions"""
+
+    def __init__(self, match, hg):
+        self.prep = ops.ntn_project(hg, match)
+
+    def queries(self, Q):
+        return ops.ntn_prepare_queries(Q, self.prep)
+
+    def score(self, qb, out=None):
+        return ops.ntn_score_block(qb, self.prep, out=out)
+
+    def positives(self, qb, off, rows, out):
+        # (rows: the positives' local rows, those of another shard clamped to 0 -- the caller masks their scores, as for BIM / LBM)
+        return ops.ntn_positive_scores(qb, self.prep, off, rows, out=out, rows_valid=True)
+
+    def count(self, qb, off, thr, larger_is_better, counts):
+        return ops.ntn_score_count_block(qb, self.prep, off, thr, larger_is_better, counts=counts)
+
+    def topk(self, qb, k, larger_is_better, idx_base, scratch):
+        return ops.ntn_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
+
+
+def _ntn_fused_ok(match):
+    """an NTN whose non-linearity is the tanh the kernel evaluates, with a slice count its entry points accept"""
+    return (match.f is torch.tanh or match.f is torch.nn.functional.tanh) and 1 <= int(match.W.weight.shape[0]) <= ops.NTN_MAX_K
+
+
 def fused_matcher_ok(match):
-    """does `match` have a fused all-candidate route (prepare_matcher)?  BIM / LBM and MLP do; anything else (NTN, a user's module) is
-    scored by calling it (evaluate._score_blocks)"""
-    from .model_zoo import MLP
+    """does `match` have a fused all-candidate route (prepare_matcher)?  BIM / LBM, MLP and NTN (with tanh and at most 16 slices) do;
+    anything else (an NTN with another non_linear, a user's module) is scored by calling it (evaluate._score_blocks)"""
+    from .model_zoo import MLP, NTN
+    if isinstance(match, NTN):
+        return _ntn_fused_ok(match)
     return isinstance(match, MLP) or (hasattr(match, "W") and hasattr(match, "apply_exp"))
 
 
 def prepare_matcher(match, hg):
     """the one place that dispatches on the matcher: a prepared candidate side with score / positives / count / topk over query blocks
     (blocks of .queries(all queries) for the last three)"""
-    from .model_zoo import MLP
+    from .model_zoo import MLP, NTN
+    if isinstance(match, NTN):
+        if not _ntn_fused_ok(match):
+            raise TypeError("no fused all-candidate route for an NTN matcher with a non_linear other than tanh or more than "
+                            f"{ops.NTN_MAX_K} slices")
+        return _PreparedNTN(match, hg)
     if isinstance(match, MLP):
         return _PreparedMLP(match, hg)
     if hasattr(match, "W") and hasattr(match, "apply_exp"):
         return _PreparedBilinear(match, hg)
-    raise TypeError(f"no fused all-candidate route for a {type(match).__name__} matcher (BIM / LBM / MLP have one)")
+    raise TypeError(f"no fused all-candidate route for a {type(match).__name__} matcher (BIM / LBM / MLP / NTN have one)")
+
+
+def _ntn_params(m):
+    """(W [k, l, r], b [k], V [k, l + r], u [k]) as float64 arrays from an NTN module or a (W, b, V, u) tuple / dict"""
+    import numpy as np
+    if isinstance(m, dict):
+        m = (m["W.weight"], m["W.bias"], m["V.weight"], m["u_R.weight"])
+    elif not isinstance(m, (tuple, list)):
+        m = (m.W.weight, m.W.bias, m.V.weight, m.u_R.weight)
+    W, b, V, u = (np.asarray(torch.as_tensor(t).detach().cpu(), dtype=np.float64) for t in m)
+    return W, b.reshape(-1), V, u.reshape(-1)
+
+
+def host_ntn_scores(match_or_params, hg, queries):
+    """score_all of an NTN matcher on the host, in float64 (the host_retrieve / sampler.host_draw pattern: the tests' reference and any
+    CPU caller's route): S[q][g] = sum_j u_j tanh(hg[g]^T W_j q + V_j . [hg[g] | q] + b_j) as a [Q, G] numpy array.
+    match_or_params: an NTN module, or its (W.weight, W.bias, V.weight, u_R.weight) as a tuple or a state-dict-keyed dict."""
+    import numpy as np
+    W, b, V, u = _ntn_params(match_or_params)
+    H = np.asarray(torch.as_tensor(hg).detach().cpu(), dtype=np.float64)
+    Q = np.asarray(torch.as_tensor(queries).detach().cpu(), dtype=np.float64)
+    l = W.shape[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.einsum("gl,klr,qr->qgk", H, W, Q) + (H @ V[:, :l].T + b)[None, :, :] + (Q @ V[:, l:].T)[:, None, :]
+        return np.tanh(t) @ u
 
 
 def score_all(match, hg, queries, block=None, out=None):
-    """S[q][g] = match(hg[g], queries[q]) for all pairs; match is a BIM / LBM / MLP module.
+    """S[q][g] = match(hg[g], queries[q]) for all pairs; match is a BIM / LBM / MLP / NTN module.
     block: queries per GEMM launch; default: a query set of up to 4,096 goes in ONE launch (MAG-CS: 2,459 queries x 24.7 k candidates
     are 7.6 rounds of tiles -- in blocks of 1,024 every block pays its own partial last round and a second, 16-tile launch), larger
     sets in blocks of 1,024."""
@@ -489,7 +551,7 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
     each tile's best k columns per row (txe_score_topk_block) + a merge launch -- no [Q, G] scores, no [Q, G] index temporaries (the
     torch composite topk_parents below needs two int64 [Q, G] ones: 3.5 GB per 1,024-query block on MAG-Full).  Same selection and
     order as topk_parents on the materialised scores of the same kernel (bit-identical values): better score first, ties by ascending
-    candidate position (Python's stable sort), NaN last.  match: BIM / LBM / MLP.  hg: this rank's candidate rows (positions
+    candidate position (Python's stable sort), NaN last.  match: BIM / LBM / MLP / NTN.  hg: this rank's candidate rows (positions
     [shard_lo, shard_lo + len) of the global list).  Candidate-sharded (ONLY when asked: `group` given or sharded=True, _sharded_call
     -- every rank then holds a DISJOINT slice, which the merge relies on): every rank's [Q, k] lists
     are all-gathered (k * 8 bytes per query instead of the [queries x candidates] block) and merged by the same kernel.
