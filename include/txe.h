@@ -331,6 +331,27 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
                    void* stream);
 
+/* ---- log-partition of the scoring loop: model/loss.py:52-57 (info_nce_loss: F.cross_entropy over [positive | sampled negatives]) over
+ * test_fast.py:121-123 / infer.py:97-99 (the scores of ALL candidates) -- the exact denominator of p(a | q) = exp(z(q, a)) / sum_a' exp(z(q, a')).
+ * Fused scoring + reduction of one query block: no [nq x G] score block is materialised.  s = the score kernel's own value (the kernel
+ * and k order of txe_score_block: bit-identical), z = s when larger_is_better, else -s;
+ *     lse[q] = log sum_{g < G} exp(z[q][g])    as the IEEE value of the float64 formula on the fp32 scores:
+ * a NaN score in the row gives NaN; otherwise a z = +Inf gives +Inf; otherwise all z = -Inf gives -Inf; otherwise M + log sum exp(z - M),
+ * M = max z (a lone candidate, or a leader the rest vanish beside, gives M bit for bit).  Every 128 x 128 tile of the score GEMM leaves, per
+ * row, (max z, sum exp(z - max)) over its columns < G in part_max / part_sum [nq][txe_score_topk_tiles(G)] (caller-provided scratch,
+ * rewritten by every call; an empty or all -Inf part is (-Inf, 0), a part with NaN / +Inf carries it as its max); txe_lse_merge
+ * combines a row's pairs in float64, tiles in a fixed order, no atomics: lse[q] is a function of row q's scores alone -- the same bits
+ * whatever the block size, the row's place in the block, or the run.  The three routes of txe_score_block (fp32 MFMA with sws = NULL, the
+ * bf16 pipe packed per call, u_packed) give the same bits wherever their scores are.
+ * TXE_ERR_ARG / TXE_ERR_WORKSPACE before any launch, as txe_score_topk_block: a negative count, G < 1, r < 1, ld_u < r, a NULL operand,
+ * scratch or output, with more than one query ld_q < r; sws given and sws_bytes too small.  nq == 0: TXE_OK, nothing launched.
+ * txe_lse_merge alone: lse [nq] from `cnt` (max, sum) pairs per row ([nq][cnt]) -- also the merge of the per-rank pairs of a
+ * candidate-sharded loop.  cnt == 0: every lse is -Inf.  TXE_ERR_ARG: nq < 0, cnt < 0, a NULL pointer. */
+int txe_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
+                        int larger_is_better, float* part_max, float* part_sum, float* lse, void* sws, size_t sws_bytes,
+                        const void* u_packed, void* stream);
+int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
+
 /* ---- retrieval stage of the two-stage test protocol (data_loader/dataset.py:316-330; csrc/txe_retrieve.hip) -------------------------
  * txe_row_normalize: y[i] = x[i] / ||x[i]||_2 (fp32, any pitch, y apart from x): cosine similarity then is a plain dot product, formed by
  * txe_score_block with apply_exp = 0.  A zero-norm or non-finite row becomes NaN and gives NaN similarities.
@@ -374,6 +395,11 @@ int txe_mlp_score_count_block(const float* Ap, const int* flag_a, int G, const f
 int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
                              const float* mw, int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws,
                              int* out_idx, float* out_key, void* stream);
+/* model_zoo.py:285-298 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
+ * candidates, txe_score_lse_block's definition, scratch and merge (the pair kernel's tiles are 128 candidates wide too).
+ * TXE_ERR_ARG before any launch: the four entry points' rules, G < 1, a NULL part_max / part_sum / lse.  nq == 0: TXE_OK, no launch. */
+int txe_mlp_score_lse_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                            const float* mw, int larger_is_better, float* part_max, float* part_sum, float* lse, void* stream);
 
 /* ---- all-candidate scoring loop of the NTN matcher (model_zoo.py:331-346 under test_fast.py:121-123 / infer.py:97-99) ---------------
  * W = W.weight [k][l][r], b = W.bias [k], V = V.weight [k][l+r] = [V1 | V2], u = u_R.weight [k].  For candidate g, query q, slice j < k:
@@ -415,6 +441,12 @@ int txe_ntn_score_topk_block(const float* Q, long long ld_q, int nq, const float
                              const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
                              int topk, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx, float* out_key,
                              void* stream);
+/* model_zoo.py:331-346 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
+ * candidates, txe_score_lse_block's definition, scratch and merge.  TXE_ERR_ARG before any launch: the four entry points' rules, G < 1,
+ * a NULL part_max / part_sum / lse.  nq == 0: TXE_OK, no launch. */
+int txe_ntn_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                            const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
+                            float* part_max, float* part_sum, float* lse, void* stream);
 
 /* plain dense product on the fp32 MFMA GEMM (tests / micro-benchmarks).  layout 0: C = A[M][K] B[N][K]^T; 1: C = A[M][K] B[K][N];
  * 2: C = A[K][M]^T B[K][N].  splits > 1: `splits` partial products at C + z*M*ldc.  ws/ws_bytes (optional, txe_gemm_tail_ws_bytes):

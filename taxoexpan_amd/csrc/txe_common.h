@@ -140,6 +140,13 @@ __device__ __forceinline__ float topk_key_of(float x, bool larger) {
     return (k != k) ? -INFINITY : k;                 // NaN compares false with everything: it ranks last
 }
 
+// ---- (max, sum) pairs of the log-partition (lse mode of the scoring loop) -------------------------------------------------------
+// A set of values z is carried as (m, s): m = max z, s = sum exp(z - m), so that log sum exp z = m + log s.  Special cases by m alone:
+// NaN = the set holds a NaN; +Inf = it holds +Inf; -Inf = it is empty or all -Inf (s = 0).  s only counts while m is finite.
+// lse_max: the maximum that keeps a NaN (the hardware max drops it)
+__device__ __forceinline__ float lse_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
+// exp(z - m) for a z of the set whose maximum is m: exactly 0 unless m is finite (no exp(-Inf - -Inf), no Inf - Inf)
+__device__ __forceinline__ float lse_term(float z, float m) { return (fabsf(m) < INFINITY) ? expf(z - m) : 0.f; }
 
 // ---- optional per-launch timing (txe_profile.hip); a no-op unless txe_profile_enable(1) was called ----
 bool prof_enabled();

@@ -97,10 +97,14 @@ struct Epi {
     //   topk_key / topk_idx [M][column tiles][topk_k]; a merge kernel (txe_topk_merge) picks each row's best k among the tiles' lists
     int cnt_mode;
     int topk_k;
-    float* topk_key;
-    int* topk_idx;
+    union { float* topk_key; float* lse_m; };        // (one mode per launch: the lse mode's outputs share the best-k lists' slots)
+    union { int* topk_idx; float* lse_s; };
     int* topk_floor;           // [M] ordered-int keys (topk_ord): a lower bound of each row's final k-th best key, raised by every tile
-    int force_bn128;           // 1: 128-wide column tiles whatever the shape (the top-k scratch is laid out by them)
+    int force_bn128;           // 1: 128-wide column tiles whatever the shape (the top-k and lse scratch is laid out by them)
+    // lse mode (cnt_mode 6: larger is better, z = value; 7: smaller is better, z = -value; the scoring loop's log-partition, the exact
+    //   form of loss.py:52-57 over test_fast.py:121-123): nothing of the product is stored; every tile leaves, per row, the pair
+    //   (max z, sum exp(z - max)) over its columns < N at lse_m / lse_s [M][column tiles] (txe_common.h: lse_max / lse_term name the
+    //   special values); a merge kernel (txe_lse_merge) combines a row's pairs in tile order
     const int* cnt_off;
     const float* cnt_thr;
     int* cnt_out;
@@ -462,7 +466,9 @@ __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(const Epi E, const
 // for the count mode) -- plain / exp / mask / activation stores, the pick, count and best-k modes.  Shared by gemm_kernel and the
 // bf16-pipe product of txe_gemm_split.hip (the scoring loop's four entry points must produce bit-identical scores: ONE epilogue).
 // cnt_pb / cnt_np / cnt_th: the count mode's per-row positive range and first thresholds, fetched by the caller before its k-loop.
-template <int BN, int SMEM>
+// LSE: the lse mode (cnt_mode 6 / 7) and nothing else -- its own instantiation of every kernel that ends here, so that the code of the
+// other modes (the training GEMMs among them) is what it was without it.
+template <int BN, int SMEM, bool LSE = false>
 __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, const int m0, const int n0, const int M, const int N, const int tn,
                                                    const int nbn, const int zslice, const int cnt_pb, const int cnt_np, const float (&cnt_th)[8]) {
     constexpr int CLD = BN + 4;
@@ -538,6 +544,54 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
                 if (t < E.topk_k) { E.topk_key[o + t] = bk[t]; E.topk_idx[o + t] = bi[t]; kth = bk[t]; kth_i = bi[t]; }
             // this tile holds k real entries at or above kth: the row's final k-th best key cannot be lower
             if (kth_i != 0x7fffffff && kth > floor_key) atomicMax(E.topk_floor + m, topk_ord(kth));
+        }
+        return;
+    }
+    if constexpr (LSE) {
+        // log-partition: two threads per row, each walks its half row twice (ascending columns): the maximum of z over the columns < N
+        // -- the pair then shares the larger one, NaN kept -- and the sum of exp(z - max) in four interleaved chains; the even thread
+        // adds the pair's sums (its own first) and writes the row's (max, sum) of this column tile.  A row's pair depends on the row's
+        // scores alone: not on the tile row it sits in, not on the launch.
+        static_assert(GEMM_THREADS == 2 * GEMM_BM, "two threads per tile row");
+        constexpr int HW = BN / 2;
+        const int row = threadIdx.x >> 1, half = threadIdx.x & 1;
+        const int m = m0 + row, nb = n0 + half * HW;
+        const bool larger = E.cnt_mode == 6;
+        const float* src = Cs + row * CLD + half * HW;
+        float mx = -INFINITY;
+        bool bad = false;
+#pragma unroll 4
+        for (int j = 0; j < HW / 4; ++j) {
+            const float4 t4 = *reinterpret_cast<const float4*>(src + 4 * j);
+            const float v4[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float x = E.apply_exp ? __expf(v4[q]) : v4[q];
+                const float z = larger ? x : -x;
+                const bool in = nb + 4 * j + q < N;
+                bad |= in & (z != z);
+                mx = in ? fmaxf(mx, z) : mx;
+            }
+        }
+        mx = bad ? __builtin_nanf("") : mx;
+        mx = lse_max(mx, __shfl_xor(mx, 1, 64));
+        float sp[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int j = 0; j < HW / 4; ++j) {
+            const float4 t4 = *reinterpret_cast<const float4*>(src + 4 * j);
+            const float v4[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float x = E.apply_exp ? __expf(v4[q]) : v4[q];
+                sp[q] += (nb + 4 * j + q < N) ? lse_term(larger ? x : -x, mx) : 0.f;
+            }
+        }
+        const float s = (sp[0] + sp[1]) + (sp[2] + sp[3]);
+        const float so = __shfl_xor(s, 1, 64);
+        if (half == 0 && m < M) {
+            const long long o = (long long)m * nbn + tn;
+            E.lse_m[o] = mx;
+            E.lse_s[o] = s + so;
         }
         return;
     }
@@ -666,9 +720,14 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
     }
 }
 
-template <bool AK, bool BKC, int VA, int VB, int BN>
+// BNX: the tile width BN, or GEMM_BN_LSE -- 128-wide tiles that end in the epilogue's lse mode (an instantiation of its own; a further
+// template parameter would rename every kernel the profiles know)
+constexpr int GEMM_BN_LSE = -128;
+template <bool AK, bool BKC, int VA, int VB, int BNX>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(VMat A, VMat B, const Epi E, const int M, const int N,
                                                                 const int K, const int ksplit, const Tail T) {
+    constexpr int BN = BNX < 0 ? -BNX : BNX;
+    constexpr bool LSE = BNX < 0;
     using GA = StageGeom<AK, VA, GEMM_BM>;
     using GB = StageGeom<BKC, VB, BN>;
     constexpr int ASZ = GA::LDS, BSZ = GB::LDS;
@@ -864,7 +923,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(VMat A, VMat B, c
         }
         return;
     }
-    gemm_tile_epilogue<BN, SMEM>(E, smem, m0, n0, M, N, tn, nbn, zslice, cnt_pb, cnt_np, cnt_th);
+    gemm_tile_epilogue<BN, SMEM, LSE>(E, smem, m0, n0, M, N, tn, nbn, zslice, cnt_pb, cnt_np, cnt_th);
 }
 
 // ---- whole rounds of a plain product: persistent workgroups, the C tile drained under the NEXT tile's k-loop ---------------------
@@ -1147,6 +1206,15 @@ static inline void gemm_launch_v(int bn, dim3 grid, hipStream_t stream, const VM
         init = true;
     }
     name = names[bn == 128 ? 0 : (bn == 64 ? 1 : 2)];
+    if constexpr (AK && BKC) {                       // (the lse mode: NT products on 128-wide tiles -- gemm_launch_layout refuses any other)
+        if (E.cnt_mode == 6 || E.cnt_mode == 7) {
+            static char lse_name[48];
+            if (!lse_name[0]) snprintf(lse_name, sizeof(lse_name), "gemm_kernel<true, true, %d, %d, %d>", VA, VB, GEMM_BN_LSE);
+            ProfScope prof(lse_name, stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
+            hipLaunchKernelGGL((gemm_kernel<AK, BKC, VA, VB, GEMM_BN_LSE>), grid, dim3(GEMM_THREADS), 0, stream, A, B, E, M, N, K, ksplit, T);
+            return;
+        }
+    }
     ProfScope prof(name, stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
     if constexpr (!BKC && VA == 4 && VB == 4) {      // (160-wide tiles: B row-contiguous -- weight gradients (TN), dZ = d_hg W (NN))
         if (bn == 160) {
@@ -1174,6 +1242,8 @@ template <bool AK, bool BKC>
 static inline int gemm_launch_layout(const VMat& A, const VMat& B, const Epi& E_in, int M, int N, int K, int splits,
                                      hipStream_t stream, void* tail_ws = nullptr, size_t tail_ws_bytes = 0) {
     if (M <= 0 || N <= 0) return TXE_OK;
+    // the lse mode exists for NT products on 128-wide tiles only (gemm_launch_v); no other instance has its epilogue
+    if ((E_in.cnt_mode == 6 || E_in.cnt_mode == 7) && !(AK && BKC && E_in.force_bn128 && splits <= 1)) return TXE_ERR_ARG;
     Epi E = E_in;
     {   // the epilogue loads its extras unconditionally: give the unused ones a readable dummy address
         const void* valid = E.c ? (const void*)E.c : (const void*)E.c2;

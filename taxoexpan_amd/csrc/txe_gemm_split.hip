@@ -158,7 +158,7 @@ __device__ __forceinline__ void gemm_nt_split_slow_tile(const char* __restrict__
 }
 
 // EPI: 0 = plain stores from the accumulators; 1 = the same with the dropout-mask / activation factors; 2 = the tile goes through LDS into
-// gemm_kernel's own epilogue (txe_gemm.h gemm_tile_epilogue: exp, pick, count and best-k modes -- the scoring loop), E = its arguments
+// gemm_kernel's own epilogue (txe_gemm.h gemm_tile_epilogue: exp, pick, count and best-k modes -- the scoring loop), E = its arguments; 3 = as 2, into that epilogue's lse mode
 template <int MI, int NST, int MINB, int EPI = 0>
 __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGemm p, const Epi E) {
     constexpr int NA = 2 * MI, NB = 4;                      // A / B fragment blocks per tile
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGem
     uint4* const st0 = smem_u4;
     uint4* const st1 = smem_u4 + STAGE_U4;
     uint4* const st2 = smem_u4 + (NST == 3 ? 2 : 0) * STAGE_U4;
-    static_assert(EPI != 2 || (MI == 2 && NST * STAGE_U4 * 4 >= 128 * 132 + 128 * 10), "the epilogue's C tile + count scratch live in the stages");
+    static_assert(EPI < 2 || (MI == 2 && NST * STAGE_U4 * 4 >= 128 * 132 + 128 * 10), "the epilogue's C tile + count scratch live in the stages");
     typedef __attribute__((address_space(3))) uint4 lds_u4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGem
     // positive ranges and first thresholds are fetched now, under the k-loop
     int cnt_pb = 0, cnt_np = 0;
     float cnt_th[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if constexpr (EPI == 2) {
+    if constexpr (EPI >= 2) {
         const int m0 = tm * 128, n0 = tn * SPL_BN;
         if (E.cnt_mode == 3) {
             const int lo = E.cnt_off[m0], hi = E.cnt_off[min(m0 + 128, p.M)];
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGem
         }
     }
 
-    if constexpr (EPI == 2) {
+    if constexpr (EPI >= 2) {
         float* Cs = reinterpret_cast<float*>(smem_u4);
         __syncthreads();                                 // every wave is done reading the stages
 #pragma unroll
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGem
                     Cs[row * 132 + 64 * wn + 2 * (l & 31) + j] = acc[i][j][e];
                 }
         __syncthreads();
-        gemm_tile_epilogue<128, NST * STAGE_U4 * 4>(E, Cs, tm * 128, tn * SPL_BN, p.M, p.N, tn, p.nbn, 0, cnt_pb, cnt_np, cnt_th);
+        gemm_tile_epilogue<128, NST * STAGE_U4 * 4, EPI == 3>(E, Cs, tm * 128, tn * SPL_BN, p.M, p.N, tn, p.nbn, 0, cnt_pb, cnt_np, cnt_th);
         return;
     }
     // accumulator register e of block (i, j): row 32 i + (e & 3) + 8 (e >> 2) + 4 (lane >> 5), slot lane & 31 of B fragment 2 wn + j =
@@ -703,7 +703,7 @@ int gemm_nt_split_launch(const void* Ap, const void* Bp, int M, int N, int K, fl
     return TXE_OK;
 }
 
-// C = A B^T through gemm_kernel's epilogue E (E.c / E.ldc, exp, pick / count / best-k modes: the scoring loop's four entry points)
+// C = A B^T through gemm_kernel's epilogue E (E.c / E.ldc, exp, pick / count / best-k / lse modes: the scoring loop's entry points)
 int gemm_nt_split_epi_launch(const void* Ap, const void* Bp, const Epi& E, int M, int N, int K, hipStream_t stream) {
     if (!Ap || !Bp || M < 1 || N < 1 || K < 1 || E.mask_on || E.act_on || E.c2) return TXE_ERR_ARG;
     SplitGemm p;
@@ -716,6 +716,12 @@ int gemm_nt_split_epi_launch(const void* Ap, const void* Bp, const Epi& E, int M
         const void* valid = E2.c ? (const void*)E2.c : (const void*)Ap;
         E2.act_src = (const float*)valid;
         E2.mask = (const unsigned*)valid;
+    }
+    if (E.cnt_mode == 6 || E.cnt_mode == 7) {           // the lse mode: its own instantiation (gemm_tile_epilogue's LSE)
+        ProfScope prof("gemm_nt_split_kernel<2, 3, 2, 3>", stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
+        hipLaunchKernelGGL((gemm_nt_split_kernel<2, 3, 2, 3>), dim3(p.nbm * p.nbn), dim3(256), 0, stream, p, E2);
+        TXE_CHECK_LAUNCH();
+        return TXE_OK;
     }
     ProfScope prof("gemm_nt_split_kernel<2, 3, 2, 2>", stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
     // (plain / exp stores straight from the accumulators -- EPI 0 with the exp -- measured SLOWER than the LDS-staged 16-byte row stores:

@@ -897,4 +897,32 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
     return txe_topk_merge(part_key, part_idx, nq, (long long)txe_score_topk_tiles(G) * k, k, idx_base, out_idx, out_key, stream);
 }
 
+// Fused scoring + log-partition of one block of the loop (model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99: the exact
+// form of the InfoNCE denominator, every candidate instead of the sampled negatives): lse[q] = log sum_{g < G} exp(z[q][g]),
+// z = the score (larger is better) or its negative.  The score tile never leaves the workgroup; every 128 x 128 tile leaves each row's
+// (max z, sum exp(z - max)) at part_max / part_sum [nq][txe_score_topk_tiles(G)] (scratch), txe_lse_merge combines them in tile order.
+// The same MFMA kernel and k order as txe_score_block: the scores behind the sum are bit-identical to the materialised ones.  G >= 1.
+int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
+
+int txe_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
+                        int larger_is_better, float* part_max, float* part_sum, float* lse, void* sws, size_t sws_bytes,
+                        const void* u_packed, void* stream) {
+    if (nq < 0 || G < 1 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || !Q || !U || !part_max || !part_sum || !lse) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
+    VMat A = vmat_plain(Q, ld_q, nq, r);
+    VMat B = vmat_plain(U, ld_u, G, r);
+    Epi E = epi_plain(part_max, 0, G);                              // c is never written in lse mode
+    E.apply_exp = apply_exp;
+    E.cnt_mode = larger_is_better ? 6 : 7;
+    E.lse_m = part_max; E.lse_s = part_sum;
+    E.force_bn128 = 1;                                              // (the scratch layout counts 128-wide column tiles)
+    int rc = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, (hipStream_t)stream);
+    if (rc < 0) return rc;
+    if (rc == 0) rc = gemm_nt(A, B, E, nq, G, r, 1, (hipStream_t)stream);
+    else rc = TXE_OK;
+    if (rc) return rc;
+    return txe_lse_merge(part_max, part_sum, nq, (long long)txe_score_topk_tiles(G), lse, stream);
+}
+
 }  // extern "C"

@@ -6,7 +6,7 @@
 //             = c[q] + sum_h w2[h] max(A[g][h], -B[q][h]),    c[q] = b2 + sum_h w2[h] B[q][h]      (relu(a + b) = max(a, -b) + b)
 // The pair term is not a product: one v_max_f32 and one FMA per (pair, h), no matrix pipe.  Every pair's score is a pure function of
 // its A row, its -B row, w2 and c[q], summed over h = 0 .. Hp-1 in ascending order by one FMA chain -- never split over h -- so the
-// store, positives, count and top-k modes see bit-identical scores wherever a pair lands.  H is zero-padded to Hp (a multiple of the
+// store, positives, count, top-k and lse modes see bit-identical scores wherever a pair lands.  H is zero-padded to Hp (a multiple of the
 // 16-wide k-step) in A, -B and w2: a padded step is fma(0, max(0, 0), acc) = acc.
 // The identity is exact only in the finite domain: the hardware max returns the non-NaN operand, and max(a, -b) + b hides an overflow
 // of a + b.  Rows of A and of B that hold NaN, +-Inf or a magnitude above lim = 2^120 / max(1, sum_h |w2[h]|) are flagged, and every
@@ -161,9 +161,10 @@ struct MlpArgs {
     float* S; long long ld_s;                       // store
     const int* pos_off; const float* thr; int* counts; int larger;   // count
     int k; float* part_key; int* part_idx; int* floor_ws;            // top-k
+    float* part_max; float* part_sum;                                // lse
 };
 
-enum { MLP_STORE = 0, MLP_COUNT = 1, MLP_TOPK = 2 };
+enum { MLP_STORE = 0, MLP_COUNT = 1, MLP_TOPK = 2, MLP_LSE = 3 };
 
 // One 128-candidate x 64-query tile per workgroup of 256 threads; thread (tg, tq) = (tid & 15, tid >> 4) owns candidates
 // g0 + {tg*4 .. tg*4+3, 64 + tg*4 .. 64 + tg*4+3} and queries q0 + tq*4 .. tq*4+3: 32 pairs.  A and -B go through LDS in 16-step
@@ -285,6 +286,37 @@ __global__ __launch_bounds__(256) void mlp_pair_kernel(const MlpArgs a) {
                 if (tg == 0 && cnt) atomicAdd(a.counts + p, cnt);
             }
         }
+    } else if constexpr (MODE == MLP_LSE) {
+        // log-partition: (max z, sum exp(z - max)) of every query row over this tile's candidates, z = the score or its negative.  Each
+        // thread's 8 columns, then a butterfly over the 16 threads of the row, once for the maximum (NaN kept) and once for the sum --
+        // a fixed order: a row's pair depends on the row's scores alone
+        const int nbn = (a.G + MLP_BG - 1) / MLP_BG;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = q0 + tq * 4 + i;
+            float mx = -INFINITY;
+            bool bad = false;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float z = a.larger ? acc[i][j] : -acc[i][j];
+                const bool in = gcol[j] < a.G;
+                bad |= in & (z != z);
+                mx = in ? fmaxf(mx, z) : mx;
+            }
+            mx = bad ? __builtin_nanf("") : mx;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) mx = lse_max(mx, __shfl_xor(mx, o, 64));
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += (gcol[j] < a.G) ? lse_term(a.larger ? acc[i][j] : -acc[i][j], mx) : 0.f;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
+            if (tg == 0 && q < a.nq) {
+                const long long o = (long long)q * nbn + blockIdx.x;
+                a.part_max[o] = mx;
+                a.part_sum[o] = s;
+            }
+        }
     } else {
         // best-k of this tile per query row: each thread's 8 columns, then a butterfly over the 16 threads of the row (all lanes
         // take part: the shuffles stay uniform); the row's rising floor skips values another tile has already beaten k times
@@ -378,6 +410,7 @@ using namespace txe;
 extern "C" {
 
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key, void* stream);
+int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
 
 int txe_mlp_padded_h(int H) { return H < 1 ? 0 : mlp_padded(H); }
 
@@ -448,6 +481,20 @@ int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const fl
     const int rc = mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]");
     if (rc) return rc;
     return txe_topk_merge(part_key, part_idx, nq, (long long)((G + MLP_BG - 1) / MLP_BG) * k, k, idx_base, out_idx, out_key, stream);
+}
+
+// model_zoo.py:285-298 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
+// candidates, txe_score_lse_block's conventions: part_max / part_sum [nq][txe_score_topk_tiles(G)] scratch, lse [nq]
+int txe_mlp_score_lse_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                            const float* mw, int larger_is_better, float* part_max, float* part_sum, float* lse, void* stream) {
+    if (!TXE_MLP_ARGS_OK || G < 1 || !part_max || !part_sum || !lse) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
+    a.larger = larger_is_better ? 1 : 0; a.part_max = part_max; a.part_sum = part_sum;
+    const int rc = mlp_launch<MLP_LSE>(a, s, "mlp_pair_kernel[lse]");
+    if (rc) return rc;
+    return txe_lse_merge(part_max, part_sum, nq, (long long)((G + MLP_BG - 1) / MLP_BG), lse, stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 // M, candidates along N, the tile geometry, operand loaders and fragment maps of gemm_kernel) and runs gemm_kernel's k-loop once per
 // slice over U_j; after slice j every accumulator goes through  s = fma(u_j, tanh((acc + a_j[n]) + c_j[m]), s)  and is cleared.  After
 // the last slice s IS the tile the GEMM's epilogue receives: gemm_tile_epilogue stores it, picks the positives' pairs out of it
-// (cnt_mode 3), counts (1 / 2) or keeps its best k (4 / 5).  No [Q x G x k] pre-activation is ever written, and nothing is split
+// (cnt_mode 3), counts (1 / 2), keeps its best k (4 / 5) or reduces its rows to (max, sum exp) pairs (6 / 7).  No [Q x G x k] pre-activation is ever written, and nothing is split
 // along the reduction: a score is a function of its two rows' values only (an MFMA accumulator is a k-ordered fmaf chain over its own
 // row and column), so the four modes see bit-identical scores wherever a pair lands -- in another tile, another launch, or among the
 // gathered rows of the positives.
@@ -50,7 +50,8 @@ struct NtnArgs {
 // buffered, one barrier per k-tile).  The k * nk k-tiles of the k slices form one software-pipelined stream: the first k-tile of slice
 // j + 1 is fetched under the last MFMA block of slice j.  A k-tile that lies wholly inside K takes the 16-byte row loader, a ragged
 // last one the element loader (both zero what lies past M / N / K).  V: the operands' common vector width (4, or 1 on odd pitches).
-template <int V>
+// LSE: the tile ends in the epilogue's lse mode (Epi: cnt_mode 6 / 7) -- an instantiation of its own
+template <int V, bool LSE = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void ntn_score_kernel(const VMat A, VMat B, const NtnArgs P, const Epi E, const int M, const int N,
                                                                     const int K) {
     constexpr int BN = 128, MI = 2, NJ = 2, CLD = BN + 4;
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void ntn_score_kernel(const VMat A
                 Cs[row * CLD + wn0 + j * 32 + (l & 31)] = sc[i][j][e];
             }
     __syncthreads();
-    gemm_tile_epilogue<BN, SMEM>(E, smem, m0, n0, M, N, tn, nbn, 0, cnt_pb, cnt_np, cnt_th);
+    gemm_tile_epilogue<BN, SMEM, LSE>(E, smem, m0, n0, M, N, tn, nbn, 0, cnt_pb, cnt_np, cnt_th);
 }
 
 // out[j][i] = <Wv[j], X[i]> (+ bias[j]) for i < n, j < k: the candidate side's a (X = hg, Wv = V1, bias = W.bias) and the query side's c
@@ -260,7 +261,10 @@ static int ntn_launch(const NtnCall& n, int N, Epi E, hipStream_t s, const char*
     // 16-byte loaders when every row of both operands starts on a 16-byte boundary -- every slice's too
     const bool v4 = vmat_vec(A) == 4 && vmat_vec(B) == 4 && (n.k == 1 || n.slice_u % 4 == 0);
     ProfScope prof(name, s, 2.0 * n.nq * (double)N * n.r * n.k, 0);
-    if (v4) hipLaunchKernelGGL((ntn_score_kernel<4>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
+    if (E.cnt_mode == 6 || E.cnt_mode == 7) {
+        if (v4) hipLaunchKernelGGL((ntn_score_kernel<4, true>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
+        else hipLaunchKernelGGL((ntn_score_kernel<1, true>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
+    } else if (v4) hipLaunchKernelGGL((ntn_score_kernel<4>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
     else hipLaunchKernelGGL((ntn_score_kernel<1>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
     TXE_CHECK_LAUNCH();
     return TXE_OK;
@@ -279,6 +283,7 @@ extern "C" {
 
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key, void* stream);
 int txe_score_topk_tiles(int G);
+int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
 
 int txe_ntn_project(const float* hg, long long ld_hg, int G, int l, const float* V1, long long ld_v, const float* b, int k, float* a,
                     long long ld_a, void* stream) {
@@ -346,6 +351,22 @@ int txe_ntn_score_topk_block(const float* Q, long long ld_q, int nq, const float
     const int rc = ntn_launch(n, G, E, s, "ntn_score_kernel[topk]");
     if (rc) return rc;
     return txe_topk_merge(part_key, part_idx, nq, (long long)txe_score_topk_tiles(G) * topk, topk, idx_base, out_idx, out_key, stream);
+}
+
+// model_zoo.py:331-346 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
+// candidates, txe_score_lse_block's conventions: the finished tile's rows leave (max z, sum exp(z - max)), txe_lse_merge combines them
+int txe_ntn_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                            const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
+                            float* part_max, float* part_sum, float* lse, void* stream) {
+    TXE_NTN_CALL;
+    if (!ntn_call_ok(n) || G < 1 || !part_max || !part_sum || !lse) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    Epi E = epi_plain(part_max, 0, G);                              // c is never written in lse mode
+    E.cnt_mode = larger_is_better ? 6 : 7;
+    E.lse_m = part_max; E.lse_s = part_sum;
+    const int rc = ntn_launch(n, G, E, (hipStream_t)stream, "ntn_score_kernel[lse]");
+    if (rc) return rc;
+    return txe_lse_merge(part_max, part_sum, nq, (long long)txe_score_topk_tiles(G), lse, stream);
 }
 
 #undef TXE_NTN_CALL

@@ -165,6 +165,33 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     }
 }
 
+// lse[q] = log sum exp z of row q from its `cnt` (max, sum) pairs (txe_common.h: m = max z, s = sum exp(z - m) of a part of the row; NaN /
+// +Inf / -Inf in m name the special cases, (-Inf, 0) is an empty part) -- the per-tile pairs of the score kernels' lse epilogue, or the
+// per-rank pairs of a candidate-sharded loop.  One wave per row, in float64: M = the largest m (NaN kept), then the lanes' strided
+// shares of sum s * exp(m - M) in ascending order and a fixed butterfly -- no atomics, no dependence on the order of arrival.
+// A sum of exactly 1 (one candidate, or a leader so far ahead that the rest vanish beside it) returns M itself, bit for bit.
+__global__ __launch_bounds__(256) void lse_merge_kernel(const float* __restrict__ pm, const float* __restrict__ ps, int nq, long long cnt,
+                                                        float* __restrict__ lse) {
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (q >= nq) return;                             // (whole waves leave: the shuffles below stay uniform)
+    const float* mp = pm + (long long)q * cnt;
+    const float* sp = ps + (long long)q * cnt;
+    float M = -INFINITY;
+    for (long long e = l; e < cnt; e += 64) M = lse_max(M, mp[e]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = lse_max(M, __shfl_xor(M, o, 64));
+    double S = 0.0;
+    if (fabsf(M) < INFINITY)
+        for (long long e = l; e < cnt; e += 64) {
+            const float m = mp[e];
+            S += (m == -INFINITY) ? 0.0 : (double)sp[e] * exp((double)m - (double)M);
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o, 64);
+    // M is NaN, +Inf or -Inf: that is the result (NaN in a row; a +Inf term; no term above -Inf)
+    if (l == 0) lse[q] = (fabsf(M) < INFINITY && S != 1.0) ? (float)((double)M + log(S)) : M;
+}
+
 }  // namespace txe
 
 using namespace txe;
@@ -179,6 +206,17 @@ int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int
     if (nq == 0) return TXE_OK;
     ProfScope prof("topk_merge_kernel", (hipStream_t)stream, 8.0 * nq * (double)cnt, 1);
     hipLaunchKernelGGL(topk_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, keys, idx, nq, cnt, k, idx_base, out_idx, out_key);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
+// part_max / part_sum [nq][cnt] -> lse [nq] (model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99).  cnt == 0 runs the same
+// kernel (no pair is read): every lse is -Inf, the log of an empty sum.
+int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream) {
+    if (nq < 0 || cnt < 0 || !part_max || !part_sum || !lse) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    ProfScope prof("lse_merge_kernel", (hipStream_t)stream, 8.0 * nq * (double)cnt, 1);
+    hipLaunchKernelGGL(lse_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, part_max, part_sum, nq, cnt, lse);
     TXE_CHECK_LAUNCH();
     return TXE_OK;
 }

@@ -1965,6 +1965,52 @@ def topk_merge(keys, idx, k):
     return out_i, out_k
 
 
+def _lse_scratch(sc, need, ref):
+    """the log-partition entry points' per-tile (max, sum) pairs (two fp32 [need]) in the dict a loop over blocks passes along (None: for
+    this call only), grown when a block needs more or the device changed"""
+    sc = sc if sc is not None else {}
+    if sc.get("lse_n", 0) < need or sc["lse_max"].device != ref.device:
+        sc["lse_max"], sc["lse_sum"], sc["lse_n"] = _empty((need,), ref), _empty((need,), ref), need
+    return sc
+
+
+def score_lse_block(Q, U, apply_exp, larger_is_better=True, q_padded=False, scratch=None):
+    """fused scoring + log-partition of one query block against a candidate matrix U (txe_score_lse_block): fp32 [nq],
+    lse[q] = log sum_g exp(z[q][g]) with z the score (larger is better) or its negative -- the exact denominator of loss.py:52-57 over
+    every candidate.  No [nq x G] block is materialised.  G >= 1.  A NaN score gives NaN, a z = +Inf gives +Inf, all z = -Inf gives
+    -Inf.  q_padded: as in score_count_block.  scratch: dict reused across the blocks of a loop (the per-tile pairs)."""
+    prep = _as_prepared(U)
+    _need_cuda(Q, prep.full)
+    G = prep.G
+    assert G >= 1, "score_lse_block: at least one candidate"
+    Q, ldq, K = _lay_queries(Q, prep, q_padded)
+    nq = Q.shape[0]
+    lse = _empty((nq,), Q)
+    if nq == 0:
+        return lse
+    with _lib.on_device(Q.device):
+        up = _planes(prep, K)
+        sws, swb = _score_sws(nq, G, K, Q, up is not None)
+        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), Q)
+        call("txe_score_lse_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), int(larger_is_better),
+             ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse), ptr(sws), swb, ptr(up), _lib.stream_ptr())
+    return lse
+
+
+def lse_merge(part_max, part_sum):
+    """lse [nq] of rows given as (max, sum exp(z - max)) pairs (txe_lse_merge; two fp32 [nq, cnt]; (-inf, 0) is an empty slot): the
+    merge of the per-tile pairs of the score kernels, or of the per-rank pairs of a candidate-sharded loop"""
+    _need_cuda(part_max, part_sum)
+    part_max, part_sum = _f32(part_max), _f32(part_sum)
+    assert part_max.dim() == 2 and part_max.shape == part_sum.shape
+    nq, cnt = part_max.shape
+    lse = _empty((nq,), part_max)
+    if nq > 0:
+        with _lib.on_device(part_max.device):
+            call("txe_lse_merge", ptr(part_max), ptr(part_sum), nq, cnt, ptr(lse), _lib.stream_ptr())
+    return lse
+
+
 SELECT_K_MAX = 4096     # txe_select_k keeps its survivors in LDS
 
 
@@ -2203,6 +2249,22 @@ def mlp_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=
     return idx, key
 
 
+def mlp_score_lse_block(Q, prep, larger_is_better=True, scratch=None):
+    """fused scoring + log-partition of one query block (txe_mlp_score_lse_block): fp32 [nq] in score_lse_block's definition and
+    conventions.  G >= 1.  scratch: dict reused across blocks."""
+    qp = mlp_prepare_queries(Q, prep)
+    G, nq = prep.G, qp.n
+    assert G >= 1, "mlp_score_lse_block: at least one candidate"
+    lse = _empty((nq,), prep.Ap)
+    if nq == 0:
+        return lse
+    with _lib.on_device(prep.Ap.device):
+        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), prep.Ap)
+        call("txe_mlp_score_lse_block", *_mlp_args(qp, prep), int(larger_is_better), ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse),
+             _lib.stream_ptr())
+    return lse
+
+
 # ================================================================================================================
 # NTN matcher (model_zoo.py:331-346) on the all-candidate loop: txe_ntn_* (the score GEMM's tile once per bilinear slice, tanh and the
 # sum over slices in its registers, the score GEMM's own store / pick / count / best-k epilogue)
@@ -2374,3 +2436,19 @@ def ntn_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=
         call("txe_ntn_score_topk_block", *_ntn_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]),
              ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
     return idx, key
+
+
+def ntn_score_lse_block(Q, prep, larger_is_better=True, scratch=None):
+    """fused scoring + log-partition of one query block (txe_ntn_score_lse_block): fp32 [nq] in score_lse_block's definition and
+    conventions.  G >= 1.  scratch: dict reused across blocks."""
+    qp = ntn_prepare_queries(Q, prep)
+    G, nq = prep.G, qp.n
+    assert G >= 1, "ntn_score_lse_block: at least one candidate"
+    lse = _empty((nq,), prep.full)
+    if nq == 0:
+        return lse
+    with _lib.on_device(prep.full.device):
+        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), prep.full)
+        call("txe_ntn_score_lse_block", *_ntn_args(qp, prep), int(larger_is_better), ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse),
+             _lib.stream_ptr())
+    return lse

@@ -36,6 +36,9 @@ class _PreparedBilinear:
     def topk(self, qb, k, larger_is_better, idx_base, scratch):
         return ops.score_topk_block(qb, self.prep, self.exp, k, larger_is_better, idx_base=idx_base, q_padded=True, scratch=scratch)
 
+    def lse(self, qb, larger_is_better, scratch):
+        return ops.score_lse_block(qb, self.prep, self.exp, larger_is_better, q_padded=True, scratch=scratch)
+
 
 class _PreparedMLP:
     """the MLP matcher over a candidate set: A = hg W1a^T + b1 once (ops.mlp_project), every query block through the VALU pair kernel
@@ -58,6 +61,9 @@ class _PreparedMLP:
 
     def topk(self, qb, k, larger_is_better, idx_base, scratch):
         return ops.mlp_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
+
+    def lse(self, qb, larger_is_better, scratch):
+        return ops.mlp_score_lse_block(qb, self.prep, larger_is_better, scratch=scratch)
 
 
 class _PreparedNTN:
@@ -84,6 +90,9 @@ class _PreparedNTN:
     def topk(self, qb, k, larger_is_better, idx_base, scratch):
         return ops.ntn_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
 
+    def lse(self, qb, larger_is_better, scratch):
+        return ops.ntn_score_lse_block(qb, self.prep, larger_is_better, scratch=scratch)
+
 
 def _ntn_fused_ok(match):
     """an NTN whose non-linearity is the tanh the kernel evaluates, with a slice count its entry points accept"""
@@ -100,8 +109,8 @@ def fused_matcher_ok(match):
 
 
 def prepare_matcher(match, hg):
-    """the one place that dispatches on the matcher: a prepared candidate side with score / positives / count / topk over query blocks
-    (blocks of .queries(all queries) for the last three)"""
+    """the one place that dispatches on the matcher: a prepared candidate side with score / positives / count / topk / lse over query
+    blocks (blocks of .queries(all queries) for the last four)"""
     from .model_zoo import MLP, NTN
     if isinstance(match, NTN):
         if not _ntn_fused_ok(match):
@@ -154,6 +163,53 @@ def score_all(match, hg, queries, block=None, out=None):
     for q0 in range(0, Q, block):
         pm.score(queries[q0:q0 + block], out=S[q0:q0 + block])
     return S
+
+
+def host_log_partition(S, larger_is_better=True):
+    """log_partition_fused on the host, in float64 (the host_retrieve / host_ntn_scores pattern: the tests' reference and any CPU
+    caller's route): per row of the score array S [Q, G], lse = log sum_g exp(z) with z = S (larger is better) or -S, as a float64
+    numpy array [Q].  A NaN in the row gives NaN; otherwise a z = +Inf gives +Inf; otherwise all z = -Inf (or G = 0) gives -Inf;
+    otherwise M + log(sum exp(z - M)), M = max z."""
+    import numpy as np
+    z = np.asarray(torch.as_tensor(S).detach().cpu(), dtype=np.float64)
+    z = z if larger_is_better else -z
+    out = np.full(z.shape[0], -np.inf, dtype=np.float64)
+    for q in range(z.shape[0]):
+        row = z[q]
+        if row.size == 0:
+            continue
+        M = row.max()                                             # (numpy's max keeps a NaN)
+        if np.isnan(M) or np.isinf(M):
+            out[q] = M
+        else:
+            out[q] = M + np.log(np.exp(row - M).sum())
+    return out
+
+
+def log_partition_fused(match, hg, queries, larger_is_better=True, block=None):
+    """lse[q] = log sum_g exp(z(q, g)) over ALL candidates g, z = the matcher's score (larger is better) or its negative: the exact
+    denominator of the likelihood p(a | q) = exp(z(q, a)) / sum_a' exp(z(q, a')) that info_nce_loss (loss.py:52-57) estimates from
+    sampled negatives.  BIM / LBM / MLP / NTN: per query block ONE launch of the score kernel whose epilogue reduces every tile row to a
+    (max, sum exp) pair + a merge launch (txe_*_score_lse_block) -- no [Q, G] scores.  Any other matcher is scored block by block
+    (evaluate._score_blocks) and reduced with torch.logsumexp.  Returns fp32 [Q] on hg's device; special values as host_log_partition
+    (no candidate at all: -inf).  block: queries per launch, rank_all_fused's default.  Candidates are not sharded here."""
+    dev = hg.device
+    Q, G = queries.shape[0], hg.shape[0]
+    if block is None:
+        block = 1024 if Q > 4096 else max(int(Q), 1)
+    if Q == 0 or G == 0:
+        return torch.full((Q,), -float("inf"), dtype=torch.float32, device=dev)
+    if fused_matcher_ok(match):
+        pm = prepare_matcher(match, hg)
+        Qp = pm.queries(queries)
+        scratch = {}
+        return torch.cat([pm.lse(Qp[q0:q0 + block], larger_is_better, scratch) for q0 in range(0, Q, block)])
+    import types
+    from .evaluate import _score_blocks
+    out = []
+    for _q0, S in _score_blocks(types.SimpleNamespace(match=match), hg, queries, block):
+        out.append(torch.logsumexp(S.float() if larger_is_better else -S.float(), dim=1))
+    return torch.cat(out)
 
 
 def encode_candidates(model, graph, chunk=None, device=None):
@@ -283,7 +339,7 @@ def _sharded_call(group, sharded):
 
 
 def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_better=True, group=None, shard_lo=0, local_fns=None,
-                   sharded=False):
+                   sharded=False, return_thresholds=False):
     """Ranks of every query's true parents among ALL candidates without materialising the score matrix.
     hg: this rank's candidate representations (rows [shard_lo, shard_lo + len) of the global candidate list; the whole list when
     not distributed).  pos_off [Q+1] / pos_idx: GLOBAL candidate columns of each query's true parents.
@@ -291,7 +347,8 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
     counts = fused score-and-compare over the local shard (summed over ranks), ranks = 1 + counts - own positives that beat it.
     The only collectives are two all-reduces of [n_positives] vectors per block -- instead of the [queries x candidates] all-gather.
     Sharded ONLY when asked: `group` given, or sharded=True (the default group) -- see _sharded_call.
-    local_fns = (positive_scores, score_count) is injectable so that the collective logic is testable without a GPU."""
+    local_fns = (positive_scores, score_count) is injectable so that the collective logic is testable without a GPU.
+    return_thresholds: (ranks, thr) -- thr fp32 [n_positives] = the positives' own scores, the values the counts compared against."""
     dev = hg.device
     distributed = _sharded_call(group, sharded)
     if block is None:
@@ -299,7 +356,8 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
         # a query set of a few thousand goes in ONE block: five launches in all instead of five per 1,024 queries
         block = 1024 if queries.shape[0] > 4096 else max(int(queries.shape[0]), 1)
     if local_fns is None and hg.shape[0] > 0:
-        return _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_is_better, group, shard_lo, distributed)
+        ranks, thr = _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_is_better, group, shard_lo, distributed)
+        return (ranks, thr) if return_thresholds else ranks
     if local_fns is None:                                          # (an empty shard: it scores nothing, but joins the collectives)
         def f_thr(qb, off, idx_local):
             return torch.zeros(idx_local.numel(), device=dev)
@@ -313,9 +371,10 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
     idx_all = torch.as_tensor(pos_idx).to(torch.int64).to(dev) - shard_lo
     n_local = hg.shape[0]
     idx_all = torch.where((idx_all >= 0) & (idx_all < n_local), idx_all, torch.full_like(idx_all, -1)).to(torch.int32)
-    out = []
+    out, thrs = [], []
     if idx_all.numel() == 0:                                       # (the same early exit and the same skipped blocks as the device
-        return torch.zeros(0, dtype=torch.int32, device=dev)       #  path: a rank with an empty shard issues the same collectives)
+        ranks = torch.zeros(0, dtype=torch.int32, device=dev)      #  path: a rank with an empty shard issues the same collectives)
+        return (ranks, torch.zeros(0, dtype=torch.float32, device=dev)) if return_thresholds else ranks
     for q0 in range(0, queries.shape[0], block):
         q1 = min(q0 + block, queries.shape[0])
         lo, hi = int(pos_off_h[q0]), int(pos_off_h[q1])
@@ -327,6 +386,7 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
         thr = f_thr(qb, off, idx_local)
         if distributed:
             dist.all_reduce(thr, op=dist.ReduceOp.SUM, group=group)          # each positive lives in exactly one shard
+        thrs.append(thr)
         counts = f_cnt(qb, off, thr)[:hi - lo]
         if distributed:
             dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
@@ -334,7 +394,10 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
             out.append(ops.rank_finalize(off, thr, counts, larger_is_better))
         else:
             out.append(_rank_finalize_host(off, thr, counts, larger_is_better))
-    return torch.cat(out) if out else torch.zeros(0, dtype=torch.int32, device=dev)
+    ranks = torch.cat(out) if out else torch.zeros(0, dtype=torch.int32, device=dev)
+    if not return_thresholds:
+        return ranks
+    return ranks, (torch.cat(thrs).to(torch.float32) if thrs else torch.zeros(0, dtype=torch.float32, device=dev))
 
 
 def _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_is_better, group, shard_lo, distributed):
@@ -350,7 +413,7 @@ def _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_i
     idx_h = np.asarray(torch.as_tensor(pos_idx).cpu(), dtype=np.int64) - int(shard_lo)
     n_pos = int(idx_h.shape[0])
     if n_pos == 0 or Q == 0:
-        return torch.zeros(0, dtype=torch.int32, device=dev)
+        return torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float32, device=dev)
     nblk = (Q + block - 1) // block
     q0s = np.minimum(np.arange(nblk + 1) * block, Q)
     lo_b = off_h[q0s]                                                     # first positive of every block (+ the end)
@@ -385,7 +448,7 @@ def _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_i
         if distributed:
             dist.all_reduce(counts[lo:hi], op=dist.ReduceOp.SUM, group=group)
         ops.rank_finalize(off, thr, counts[lo:hi], larger_is_better, out=ranks[lo:hi])
-    return ranks
+    return ranks, thr_all
 
 
 def _rank_finalize_host(off, thr, counts, larger_is_better):
@@ -546,7 +609,8 @@ class overlapped_gradient_allreduce:
         self._pending = []
 
 
-def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_better=True, block=None, group=None, shard_lo=0, sharded=False):
+def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_better=True, block=None, group=None, shard_lo=0, sharded=False,
+                       return_scores=False):
     """infer.py:96-106 / test_fast.py:121-131 without the score matrix: per query block ONE launch of the score GEMM whose epilogue keeps
     each tile's best k columns per row (txe_score_topk_block) + a merge launch -- no [Q, G] scores, no [Q, G] index temporaries (the
     torch composite topk_parents below needs two int64 [Q, G] ones: 3.5 GB per 1,024-query block on MAG-Full).  Same selection and
@@ -555,7 +619,9 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
     [shard_lo, shard_lo + len) of the global list).  Candidate-sharded (ONLY when asked: `group` given or sharded=True, _sharded_call
     -- every rank then holds a DISJOINT slice, which the merge relies on): every rank's [Q, k] lists
     are all-gathered (k * 8 bytes per query instead of the [queries x candidates] block) and merged by the same kernel.
-    Returns candidate_ids[...] (or the positions themselves when candidate_ids is None) [Q, min(k, G)]."""
+    Returns candidate_ids[...] (or the positions themselves when candidate_ids is None) [Q, min(k, G)].
+    return_scores: (ids, scores) -- scores fp32 [Q, min(k, G)] = the matcher's own values of the chosen pairs, un-negated, bit-equal to
+    score_all's entries (a NaN score, which ranks last, is reported as the worst value: -inf, or +inf when smaller is better)."""
     dev = hg.device
     distributed = _sharded_call(group, sharded)
     Q, G = queries.shape[0], hg.shape[0]
@@ -592,9 +658,11 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
         n_real = int((cat_i[0] != 0x7fffffff).sum().item()) if Q > 0 else 0      # = min(total candidates, world * kk): the same for every query
         idx, key = ops.topk_merge(cat_k, cat_i, kk) if Q > 0 else (cat_i, cat_k)
         idx = idx[:, :min(kk, n_real)]
-    if candidate_ids is None:
-        return idx.long()
-    return candidate_ids.to(dev)[idx.long()]
+    ids = idx.long() if candidate_ids is None else candidate_ids.to(dev)[idx.long()]
+    if not return_scores:
+        return ids
+    key = key[:, :idx.shape[1]]
+    return ids, (key if larger_is_better else -key)
 
 
 # ---------------------------------------------------------------------------------------------------------------
