@@ -331,6 +331,28 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
 int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
                    void* stream);
 
+/* ---- best-k parents, 9 <= k <= 64: infer.py:96-106 / test_fast.py:121-131 with a longer slice (`sorted(enumerate(scores), key=...)[:k]`:
+ * a curator's list of 10 or 20, a re-ranking stage's 50) -- still without the [nq x G] score block.
+ * The order is total over (key, column), so a row's best k are its best 8, then the best 8 among the entries strictly worse than the 8th
+ * chosen, and so on: ceil(k / 8) rounds of the k <= 8 path (floor initialisation, score tiles, merge), each under a per-row ceiling
+ * (key, column) that the round before left -- its last slot as it stands; an empty slot (-inf, INT_MAX) has nothing below it.  One
+ * pass of the score tiles per round; the lists, the scratch layout [nq][txe_score_topk_tiles(G)][<= 8] and the k <= 8 entry points are
+ * what they were.  Exact and deterministic as they are: the result is a pure function of the scores.
+ * txe_score_topk_wide_block: txe_score_topk_block's arguments, order and conventions with 1 <= k <= txe_topk_wide_max() = 64;
+ * part_key / part_idx hold [nq][txe_score_topk_tiles(G)][min(k, 8)]; out_idx / out_key [nq][k]; ceil_ws: 8 * nq bytes of scratch ([nq]
+ * float keys, then [nq] int columns of this candidate set: idx_base is added on output only).  Every round is enqueued by the one
+ * call, nothing is read back; on the bf16 pipe (sws) the operands are packed once.  For k <= 8 the result is txe_score_topk_block's,
+ * bit for bit.  TXE_ERR_ARG / TXE_ERR_WORKSPACE before any launch: txe_score_topk_block's rules with k < 1, k > 64, G < 1, a NULL ceil_ws.
+ * txe_topk_merge_wide: txe_topk_merge with 1 <= k <= 64 and the same ceil_ws -- the same rounds over given lists (the per-rank lists of
+ * a candidate-sharded loop; idx must be distinct within a row).  TXE_ERR_ARG: nq < 0, cnt < 0, k < 1, k > 64, a NULL keys / idx / out_idx /
+ * ceil_ws. */
+int txe_topk_wide_max(void);
+int txe_score_topk_wide_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
+                              int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,
+                              float* out_key, void* sws, size_t sws_bytes, const void* u_packed, void* ceil_ws, void* stream);
+int txe_topk_merge_wide(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
+                        void* ceil_ws, void* stream);
+
 /* ---- log-partition of the scoring loop: model/loss.py:52-57 (info_nce_loss: F.cross_entropy over [positive | sampled negatives]) over
  * test_fast.py:121-123 / infer.py:97-99 (the scores of ALL candidates) -- the exact denominator of p(a | q) = exp(z(q, a)) / sum_a' exp(z(q, a')).
  * Fused scoring + reduction of one query block: no [nq x G] score block is materialised.  s = the score kernel's own value (the kernel
@@ -395,6 +417,12 @@ int txe_mlp_score_count_block(const float* Ap, const int* flag_a, int G, const f
 int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
                              const float* mw, int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws,
                              int* out_idx, float* out_key, void* stream);
+/* model_zoo.py:285-298 under infer.py:100-106 with a longer slice -- txe_mlp_score_topk_block for 1 <= k <= 64: txe_score_topk_wide_block's
+ * rounds, scratch (part_key / part_idx [nq][txe_score_topk_tiles(G)][min(k, 8)], ceil_ws 8 * nq bytes) and refusals; k <= 8 bit-equal
+ * to txe_mlp_score_topk_block */
+int txe_mlp_score_topk_wide_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                                  const float* mw, int larger_is_better, int k, int idx_base, float* part_key, int* part_idx,
+                                  int* floor_ws, int* out_idx, float* out_key, void* ceil_ws, void* stream);
 /* model_zoo.py:285-298 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
  * candidates, txe_score_lse_block's definition, scratch and merge (the pair kernel's tiles are 128 candidates wide too).
  * TXE_ERR_ARG before any launch: the four entry points' rules, G < 1, a NULL part_max / part_sum / lse.  nq == 0: TXE_OK, no launch. */
@@ -441,6 +469,13 @@ int txe_ntn_score_topk_block(const float* Q, long long ld_q, int nq, const float
                              const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
                              int topk, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx, float* out_key,
                              void* stream);
+/* model_zoo.py:331-346, test_fast.py:121-123 / infer.py:100-106 with a longer slice -- txe_ntn_score_topk_block for 1 <= topk <= 64:
+ * txe_score_topk_wide_block's rounds, scratch (part_key / part_idx [nq][txe_score_topk_tiles(G)][min(topk, 8)], ceil_ws 8 * nq bytes) and
+ * refusals; topk <= 8 bit-equal to txe_ntn_score_topk_block */
+int txe_ntn_score_topk_wide_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                                  const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k,
+                                  int larger_is_better, int topk, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,
+                                  float* out_key, void* ceil_ws, void* stream);
 /* model_zoo.py:331-346 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
  * candidates, txe_score_lse_block's definition, scratch and merge.  TXE_ERR_ARG before any launch: the four entry points' rules, G < 1,
  * a NULL part_max / part_sum / lse.  nq == 0: TXE_OK, no launch. */

@@ -74,6 +74,9 @@ SIGNATURES = {
     "txe_score_topk_tiles": (I, [I]),
     "txe_score_topk_block": (I, [P, L, I, P, L, I, I, I, I, I, I, P, P, P, P, P, P, SZ, P, P]),
     "txe_topk_merge": (I, [P, P, I, L, I, I, P, P, P]),
+    "txe_topk_wide_max": (I, []),
+    "txe_score_topk_wide_block": (I, [P, L, I, P, L, I, I, I, I, I, I, P, P, P, P, P, P, SZ, P, P, P]),
+    "txe_topk_merge_wide": (I, [P, P, I, L, I, I, P, P, P, P]),
     "txe_score_lse_block": (I, [P, L, I, P, L, I, I, I, I, P, P, P, P, SZ, P, P]),
     "txe_lse_merge": (I, [P, P, I, L, P, P]),
     "txe_bilinear_stacked_fwd": (I, [P, L, P, L, P, P, I, I, I, P, I, P, P, P]),
@@ -92,6 +95,7 @@ SIGNATURES = {
     "txe_mlp_score_positives": (I, [P, P, I, P, P, P, I, I, P, P, P, I, P, P]),
     "txe_mlp_score_count_block": (I, [P, P, I, P, P, P, I, I, P, P, P, I, P, P]),
     "txe_mlp_score_topk_block": (I, [P, P, I, P, P, P, I, I, P, I, I, I, P, P, P, P, P, P]),
+    "txe_mlp_score_topk_wide_block": (I, [P, P, I, P, P, P, I, I, P, I, I, I, P, P, P, P, P, P, P]),
     "txe_mlp_score_lse_block": (I, [P, P, I, P, P, P, I, I, P, I, P, P, P, P]),
     "txe_ntn_project": (I, [P, L, I, I, P, L, P, I, P, L, P]),
     "txe_ntn_query_project": (I, [P, L, I, I, P, L, I, P, L, P]),
@@ -99,6 +103,7 @@ SIGNATURES = {
     "txe_ntn_score_positives": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, P, P, P]),
     "txe_ntn_score_count_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, P, P, I, P, P]),
     "txe_ntn_score_topk_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, I, I, P, P, P, P, P, P]),
+    "txe_ntn_score_topk_wide_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, I, I, P, P, P, P, P, P, P]),
     "txe_ntn_score_lse_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, P, P, P, P]),
     "txe_score_split_ws_bytes": (SZ, [I, I, I]),
     "txe_score_count_block": (I, [P, L, I, P, L, I, I, I, P, P, I, P, P, SZ, P, P]),
@@ -222,7 +227,7 @@ def ref(desc):
 
 _ERR = {-1: "TXE_ERR_ARG", -2: "TXE_ERR_LAUNCH", -3: "TXE_ERR_WORKSPACE"}
 VALUE_RETURNING = {"txe_gat_padded_k", "txe_gat_collapse_e_tiles", "txe_gat_padded_f", "txe_gcn_padded_f", "txe_profile_count", "txe_gat_fused_bwd_supported",
-                   "txe_gat_aggregate_table_supported", "txe_gat_dx_streams", "txe_score_topk_tiles",
+                   "txe_gat_aggregate_table_supported", "txe_gat_dx_streams", "txe_score_topk_tiles", "txe_topk_wide_max",
                    "txe_mlp_padded_h"}   # int results that are not status codes
 
 _lib = None

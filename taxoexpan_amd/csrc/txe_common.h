@@ -140,6 +140,17 @@ __device__ __forceinline__ float topk_key_of(float x, bool larger) {
     return (k != k) ? -INFINITY : k;                 // NaN compares false with everything: it ranks last
 }
 
+// A best-k wider than TOPK_MAX (up to TOPK_WIDE_MAX) is taken in rounds of TOPK_MAX under a ceiling: the order is total over (key,
+// column), so a row's best k are its best 8, then the best 8 among the entries strictly worse than the 8th chosen, and so on.  Each
+// round is the tile epilogue + merge of the k <= 8 path with the row's ceiling (ceil_key, ceil_idx) -- an entry (key, n) is eligible
+// only if topk_better(ceil_key, ceil_idx, key, n) -- and the round's last slot is the next round's ceiling exactly as it stands: an
+// empty slot (-inf, INT_MAX) has nothing below it, so an exhausted row stays exhausted.  The lists, the scratch layout and TOPK_MAX
+// stay what they are; a round costs one pass of the score tiles.
+constexpr int TOPK_WIDE_MAX = 64;
+// one round's merge (txe_rank.hip: topk_merge_round_kernel); the ceilings in and out may be the same buffers
+int topk_merge_round(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
+                     long long pitch, const float* ceil_key_in, const int* ceil_idx_in, float* ceil_key_out, int* ceil_idx_out, hipStream_t s);
+
 // ---- (max, sum) pairs of the log-partition (lse mode of the scoring loop) -------------------------------------------------------
 // A set of values z is carried as (m, s): m = max z, s = sum exp(z - m), so that log sum exp z = m + log s.  Special cases by m alone:
 // NaN = the set holds a NaN; +Inf = it holds +Inf; -Inf = it is empty or all -Inf (s = 0).  s only counts while m is finite.

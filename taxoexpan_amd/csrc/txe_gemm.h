@@ -105,8 +105,11 @@ struct Epi {
     //   form of loss.py:52-57 over test_fast.py:121-123): nothing of the product is stored; every tile leaves, per row, the pair
     //   (max z, sum exp(z - max)) over its columns < N at lse_m / lse_s [M][column tiles] (txe_common.h: lse_max / lse_term name the
     //   special values); a merge kernel (txe_lse_merge) combines a row's pairs in tile order
-    const int* cnt_off;
-    const float* cnt_thr;
+    // the top-k mode's optional ceiling (the rounds of a best-k wider than TOPK_MAX; both NULL: none) shares the slots of the count
+    //   mode's fields, which top-k mode never reads: column n of row m is eligible only if topk_better(topk_ceil_key[m],
+    //   topk_ceil_idx[m], key, n) -- strictly worse, in the total (key, column) order, than the last entry an earlier round chose
+    union { const int* cnt_off; const int* topk_ceil_idx; };
+    union { const float* cnt_thr; const float* topk_ceil_key; };
     int* cnt_out;
     // profiling only: the product's ALGORITHMIC flops when the operands carry tile padding (0: 2*M*N*K as launched)
     double alg_flops;
@@ -509,20 +512,34 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
         const int kk = E.topk_k;
         float wk = -INFINITY;                            // the list's current k-th best: what a candidate has to beat
         int wi = 0x7fffffff;
+        // CEIL: a later round of a best-k wider than TOPK_MAX -- only entries strictly worse than the row's ceiling (the last entry the
+        // round before chose) are eligible; the floor then bounds the k-th best ELIGIBLE key (it was re-initialised for this round), so
+        // the argument above holds unchanged.  An exhausted row's ceiling is the empty slot (-inf, INT_MAX): nothing is below it.
+        // The choice is launch-uniform; without a ceiling the loop is the one it was.
+        auto scan = [&](auto ceil_tag) {
+            constexpr bool CEIL = decltype(ceil_tag)::value;
+            float ck = INFINITY;
+            int ci = -1;
+            if constexpr (CEIL) { ck = E.topk_ceil_key[mf]; ci = E.topk_ceil_idx[mf]; }
 #pragma unroll 4
-        for (int j = 0; j < HW / 4; ++j) {
-            const float4 t4 = *reinterpret_cast<const float4*>(Cs + row * CLD + half * HW + 4 * j);
-            const float v4[4] = {t4.x, t4.y, t4.z, t4.w};
+            for (int j = 0; j < HW / 4; ++j) {
+                const float4 t4 = *reinterpret_cast<const float4*>(Cs + row * CLD + half * HW + 4 * j);
+                const float v4[4] = {t4.x, t4.y, t4.z, t4.w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = nb + 4 * j + q;
-                const float key = topk_key_of(E.apply_exp ? __expf(v4[q]) : v4[q], larger);
-                if (n < N && !(key < floor_key) && topk_better(key, n, wk, wi)) {
-                    topk_insert(bk, bi, key, n);
-                    topk_kth(bk, bi, kk, wk, wi);
+                for (int q = 0; q < 4; ++q) {
+                    const int n = nb + 4 * j + q;
+                    const float key = topk_key_of(E.apply_exp ? __expf(v4[q]) : v4[q], larger);
+                    bool ok = n < N && !(key < floor_key) && topk_better(key, n, wk, wi);
+                    if constexpr (CEIL) ok = ok && topk_better(ck, ci, key, n);
+                    if (ok) {
+                        topk_insert(bk, bi, key, n);
+                        topk_kth(bk, bi, kk, wk, wi);
+                    }
                 }
             }
-        }
+        };
+        if (E.topk_ceil_key != nullptr) scan(std::true_type{});
+        else scan(std::false_type{});
         // the odd thread's list goes to the even one (all lanes shuffle; only the even thread's merge is kept)
 #pragma unroll
         for (int t = 0; t < TOPK_MAX; ++t) {

@@ -897,6 +897,57 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
     return txe_topk_merge(part_key, part_idx, nq, (long long)txe_score_topk_tiles(G) * k, k, idx_base, out_idx, out_key, stream);
 }
 
+// txe_score_topk_block for 1 <= k <= 64 (a curator's list of 10 or 20, a re-ranker's 50: infer.py:100-106 with a longer slice): rounds
+// of 8 under a ceiling (txe_common.h) -- per round the floors are re-initialised, the score tiles run with the rows' ceilings in their
+// top-k epilogue (none in the first round) and topk_merge_round_kernel writes columns [8 * round, ...) of out_idx / out_key [nq][k] and
+// the next ceilings.  All enqueued, nothing read back.  part_key / part_idx: [nq][txe_score_topk_tiles(G)][min(k, 8)].  ceil_ws: 8 * nq
+// bytes ([nq] float keys, then [nq] int columns -- local to this candidate set: idx_base is added on output only).  On the bf16 pipe
+// the operands are packed once, for all rounds.  k <= 8: the one round is txe_score_topk_block's selection, bit for bit.
+int txe_score_topk_wide_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
+                              int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,
+                              float* out_key, void* sws, size_t sws_bytes, const void* u_packed, void* ceil_ws, void* stream) {
+    if (nq < 0 || G < 1 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || k < 1 || k > TOPK_WIDE_MAX || !Q || !U || !part_key || !part_idx ||
+        !floor_ws || !out_idx || !ceil_ws)
+        return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
+    hipStream_t s = (hipStream_t)stream;
+    float* ck = reinterpret_cast<float*>(ceil_ws);
+    int* ci = reinterpret_cast<int*>(ck + nq);
+    VMat A = vmat_plain(Q, ld_q, nq, r);
+    VMat B = vmat_plain(U, ld_u, G, r);
+    Epi E = epi_plain(part_key, 0, G);                              // c is never written in top-k mode
+    E.apply_exp = apply_exp;
+    E.cnt_mode = larger_is_better ? 4 : 5;
+    E.topk_key = part_key; E.topk_idx = part_idx; E.topk_floor = floor_ws;
+    E.force_bn128 = 1;                                              // (the scratch layout counts 128-wide column tiles)
+    const void* up = u_packed;
+    if (sws) {                                                      // score_split's packing, once
+        int rc = split_pack_launch(Q, ld_q, nq, r, 0, sws, s);
+        if (rc) return rc;
+        if (!up) {
+            char* w = (char*)sws + (split_packed_bytes(nq, r) + 255) / 256 * 256;
+            rc = split_pack_launch(U, ld_u, G, r, 1, w, s);
+            if (rc) return rc;
+            up = w;
+        }
+    }
+    const long long tiles = txe_score_topk_tiles(G);
+    for (int k0 = 0; k0 < k; k0 += TOPK_MAX) {
+        const int kr = (k - k0 < TOPK_MAX) ? k - k0 : TOPK_MAX;
+        hipLaunchKernelGGL(topk_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
+        TXE_CHECK_LAUNCH();
+        E.topk_k = kr;
+        E.topk_ceil_key = k0 ? ck : nullptr; E.topk_ceil_idx = k0 ? ci : nullptr;
+        int rc = sws ? gemm_nt_split_epi_launch(sws, up, E, nq, G, r, s) : gemm_nt(A, B, E, nq, G, r, 1, s);
+        if (rc) return rc;
+        rc = topk_merge_round(part_key, part_idx, nq, tiles * kr, kr, idx_base, out_idx + k0, out_key ? out_key + k0 : nullptr, k,
+                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
+        if (rc) return rc;
+    }
+    return TXE_OK;
+}
+
 // Fused scoring + log-partition of one block of the loop (model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99: the exact
 // form of the InfoNCE denominator, every candidate instead of the sampled negatives): lse[q] = log sum_{g < G} exp(z[q][g]),
 // z = the score (larger is better) or its negative.  The score tile never leaves the workgroup; every 128 x 128 tile leaves each row's

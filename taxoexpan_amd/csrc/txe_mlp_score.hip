@@ -161,10 +161,13 @@ struct MlpArgs {
     float* S; long long ld_s;                       // store
     const int* pos_off; const float* thr; int* counts; int larger;   // count
     int k; float* part_key; int* part_idx; int* floor_ws;            // top-k
+    const float* ceil_key; const int* ceil_idx;                      // top-k: the rows' ceilings of a wide best-k's later rounds (NULL: none)
     float* part_max; float* part_sum;                                // lse
 };
 
-enum { MLP_STORE = 0, MLP_COUNT = 1, MLP_TOPK = 2, MLP_LSE = 3 };
+// (MLP_TOPK_CEIL: MLP_TOPK under the rows' ceilings, a later round of a wide best-k -- an instantiation of its own, so that the k <= 8
+//  path's kernel keeps its registers and its occupancy)
+enum { MLP_STORE = 0, MLP_COUNT = 1, MLP_TOPK = 2, MLP_LSE = 3, MLP_TOPK_CEIL = 4 };
 
 // One 128-candidate x 64-query tile per workgroup of 256 threads; thread (tg, tq) = (tid & 15, tid >> 4) owns candidates
 // g0 + {tg*4 .. tg*4+3, 64 + tg*4 .. 64 + tg*4+3} and queries q0 + tq*4 .. tq*4+3: 32 pairs.  A and -B go through LDS in 16-step
@@ -332,11 +335,20 @@ __global__ __launch_bounds__(256) void mlp_pair_kernel(const MlpArgs a) {
             topk_init(bk, bi);
             float wk = -INFINITY;
             int wi = 0x7fffffff;
+            // the row's ceiling (Epi::topk_ceil_key's rule: only entries strictly worse than it are eligible)
+            float ck = INFINITY;
+            int ci = -1;
+            if constexpr (MODE == MLP_TOPK_CEIL) {
+                ck = qok ? a.ceil_key[q] : INFINITY;
+                ci = qok ? a.ceil_idx[q] : -1;
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int n = gcol[j];
                 const float key = topk_key_of(acc[i][j], larger);
-                if (n < a.G && !(key < floor_key) && topk_better(key, n, wk, wi)) {
+                bool take = n < a.G && !(key < floor_key) && topk_better(key, n, wk, wi);
+                if constexpr (MODE == MLP_TOPK_CEIL) take = take && topk_better(ck, ci, key, n);
+                if (take) {
                     topk_insert(bk, bi, key, n);
                     topk_kth(bk, bi, kk, wk, wi);
                 }
@@ -481,6 +493,33 @@ int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const fl
     const int rc = mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]");
     if (rc) return rc;
     return txe_topk_merge(part_key, part_idx, nq, (long long)((G + MLP_BG - 1) / MLP_BG) * k, k, idx_base, out_idx, out_key, stream);
+}
+
+// model_zoo.py:285-298 under infer.py:100-106 with a longer list -- txe_mlp_score_topk_block for 1 <= k <= 64, txe_score_topk_wide_block's
+// rounds, scratch (part_key / part_idx [nq][tiles][min(k, 8)], ceil_ws 8 * nq bytes) and conventions
+int txe_mlp_score_topk_wide_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                                  const float* mw, int larger_is_better, int k, int idx_base, float* part_key, int* part_idx,
+                                  int* floor_ws, int* out_idx, float* out_key, void* ceil_ws, void* stream) {
+    if (!TXE_MLP_ARGS_OK || G < 1 || k < 1 || k > TOPK_WIDE_MAX || !part_key || !part_idx || !floor_ws || !out_idx || !ceil_ws) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    float* ck = reinterpret_cast<float*>(ceil_ws);
+    int* ci = reinterpret_cast<int*>(ck + nq);
+    MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
+    a.larger = larger_is_better ? 1 : 0; a.part_key = part_key; a.part_idx = part_idx; a.floor_ws = floor_ws;
+    const long long tiles = (G + MLP_BG - 1) / MLP_BG;
+    for (int k0 = 0; k0 < k; k0 += TOPK_MAX) {
+        const int kr = (k - k0 < TOPK_MAX) ? k - k0 : TOPK_MAX;
+        hipLaunchKernelGGL(mlp_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
+        TXE_CHECK_LAUNCH();
+        a.k = kr; a.ceil_key = k0 ? ck : nullptr; a.ceil_idx = k0 ? ci : nullptr;
+        int rc = k0 ? mlp_launch<MLP_TOPK_CEIL>(a, s, "mlp_pair_kernel[topk]") : mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]");
+        if (rc) return rc;
+        rc = topk_merge_round(part_key, part_idx, nq, tiles * kr, kr, idx_base, out_idx + k0, out_key ? out_key + k0 : nullptr, k,
+                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
+        if (rc) return rc;
+    }
+    return TXE_OK;
 }
 
 // model_zoo.py:285-298 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all

@@ -353,6 +353,38 @@ int txe_ntn_score_topk_block(const float* Q, long long ld_q, int nq, const float
     return txe_topk_merge(part_key, part_idx, nq, (long long)txe_score_topk_tiles(G) * topk, topk, idx_base, out_idx, out_key, stream);
 }
 
+// model_zoo.py:331-346 under infer.py:100-106 with a longer list -- txe_ntn_score_topk_block for 1 <= topk <= 64, txe_score_topk_wide_block's
+// rounds, scratch (part_key / part_idx [nq][tiles][min(topk, 8)], ceil_ws 8 * nq bytes) and conventions
+int txe_ntn_score_topk_wide_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                                  const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k,
+                                  int larger_is_better, int topk, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,
+                                  float* out_key, void* ceil_ws, void* stream) {
+    TXE_NTN_CALL;
+    if (!ntn_call_ok(n) || G < 1 || topk < 1 || topk > TOPK_WIDE_MAX || !part_key || !part_idx || !floor_ws || !out_idx || !ceil_ws)
+        return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    float* ck = reinterpret_cast<float*>(ceil_ws);
+    int* ci = reinterpret_cast<int*>(ck + nq);
+    Epi E = epi_plain(part_key, 0, G);                              // c is never written in top-k mode
+    E.cnt_mode = larger_is_better ? 4 : 5;
+    E.topk_key = part_key; E.topk_idx = part_idx; E.topk_floor = floor_ws;
+    const long long tiles = txe_score_topk_tiles(G);
+    for (int k0 = 0; k0 < topk; k0 += TOPK_MAX) {
+        const int kr = (topk - k0 < TOPK_MAX) ? topk - k0 : TOPK_MAX;
+        hipLaunchKernelGGL(ntn_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
+        TXE_CHECK_LAUNCH();
+        E.topk_k = kr;
+        E.topk_ceil_key = k0 ? ck : nullptr; E.topk_ceil_idx = k0 ? ci : nullptr;
+        int rc = ntn_launch(n, G, E, s, "ntn_score_kernel[topk]");
+        if (rc) return rc;
+        rc = topk_merge_round(part_key, part_idx, nq, tiles * kr, kr, idx_base, out_idx + k0, out_key ? out_key + k0 : nullptr, topk,
+                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
+        if (rc) return rc;
+    }
+    return TXE_OK;
+}
+
 // model_zoo.py:331-346 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
 // candidates, txe_score_lse_block's conventions: the finished tile's rows leave (max z, sum exp(z - max)), txe_lse_merge combines them
 int txe_ntn_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,

@@ -165,6 +165,79 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     }
 }
 
+// One round of a best-k wider than TOPK_MAX (txe_common.h: rounds of 8 under a ceiling).  topk_merge_kernel's selection over the
+// entries strictly worse than the row's ceiling (ceil_key_in / ceil_idx_in [nq]; NULL: the first round, every entry is eligible): the
+// row's best k (<= TOPK_MAX) of them go to out_idx / out_key + q * pitch (the caller has added the round's column offset), and the last
+// of them -- empty slot (-inf, INT_MAX) included, as it stands -- becomes the row's next ceiling (ceil_*_out; may be the buffers read:
+// a row's ceiling is read and written by its own wave only, the write after the last use of what was read).  Ceiling columns are
+// the lists' own (local) columns: idx_base is added on output only.
+__global__ __launch_bounds__(256) void topk_merge_round_kernel(const float* __restrict__ pkey, const int* __restrict__ pidx, int nq, long long cnt,
+                                                               int k, int idx_base, int* __restrict__ out_idx, float* __restrict__ out_key,
+                                                               long long pitch, const float* ceil_key_in, const int* ceil_idx_in,
+                                                               float* ceil_key_out, int* ceil_idx_out) {
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (q >= nq) return;
+    const float* kp = pkey + (long long)q * cnt;
+    const int* ip = pidx + (long long)q * cnt;
+    const float ck = ceil_key_in ? ceil_key_in[q] : INFINITY;   // (+inf, -1): better than every entry
+    const int ci = ceil_key_in ? ceil_idx_in[q] : -1;
+    float bk[TOPK_MAX];
+    int bi[TOPK_MAX];
+    topk_init(bk, bi);
+    float wk = -INFINITY;                                        // the lane's current k-th best
+    int wi = 0x7fffffff;
+    for (long long e0 = 0; e0 < cnt; e0 += 4 * 64) {
+        float kv[4];
+        int iv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long e = e0 + u * 64 + l;
+            const long long ec = e < cnt ? e : cnt - 1;
+            kv[u] = kp[ec]; iv[u] = (e < cnt) ? ip[ec] : 0x7fffffff;
+            kv[u] = (kv[u] != kv[u]) ? -INFINITY : kv[u];       // a NaN key ranks last, as -inf
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (iv[u] != 0x7fffffff && topk_better(ck, ci, kv[u], iv[u]) && topk_better(kv[u], iv[u], wk, wi)) {
+                topk_insert(bk, bi, kv[u], iv[u]);
+                topk_kth(bk, bi, k, wk, wi);
+            }
+    }
+    float last_k = -INFINITY;
+    int last_i = 0x7fffffff;
+    for (int t = 0; t < k; ++t) {
+        float wk = bk[0];
+        int wi = bi[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ok = __shfl_xor(wk, o, 64);
+            const int oi = __shfl_xor(wi, o, 64);
+            const bool take = topk_better(ok, oi, wk, wi);
+            wk = take ? ok : wk; wi = take ? oi : wi;
+        }
+        if (bi[0] == wi && wi != 0x7fffffff) {                  // (columns are unique: exactly one lane holds the winner) pop it
+#pragma unroll
+            for (int j = 0; j + 1 < TOPK_MAX; ++j) { bk[j] = bk[j + 1]; bi[j] = bi[j + 1]; }
+            bk[TOPK_MAX - 1] = -INFINITY; bi[TOPK_MAX - 1] = 0x7fffffff;
+        }
+        if (l == 0) {
+            out_idx[(long long)q * pitch + t] = (wi == 0x7fffffff) ? -1 : wi + idx_base;
+            if (out_key) out_key[(long long)q * pitch + t] = wk;
+        }
+        last_k = wk; last_i = wi;
+    }
+    if (l == 0) { ceil_key_out[q] = last_k; ceil_idx_out[q] = last_i; }
+}
+
+int topk_merge_round(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
+                     long long pitch, const float* ceil_key_in, const int* ceil_idx_in, float* ceil_key_out, int* ceil_idx_out, hipStream_t s) {
+    ProfScope prof("topk_merge_round_kernel", s, 8.0 * nq * (double)cnt, 1);
+    hipLaunchKernelGGL(topk_merge_round_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, keys, idx, nq, cnt, k, idx_base, out_idx, out_key, pitch,
+                       ceil_key_in, ceil_idx_in, ceil_key_out, ceil_idx_out);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
 // lse[q] = log sum exp z of row q from its `cnt` (max, sum) pairs (txe_common.h: m = max z, s = sum exp(z - m) of a part of the row; NaN /
 // +Inf / -Inf in m name the special cases, (-Inf, 0) is an empty part) -- the per-tile pairs of the score kernels' lse epilogue, or the
 // per-rank pairs of a candidate-sharded loop.  One wave per row, in float64: M = the largest m (NaN kept), then the lanes' strided
@@ -207,6 +280,25 @@ int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int
     ProfScope prof("topk_merge_kernel", (hipStream_t)stream, 8.0 * nq * (double)cnt, 1);
     hipLaunchKernelGGL(topk_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, keys, idx, nq, cnt, k, idx_base, out_idx, out_key);
     TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
+int txe_topk_wide_max(void) { return TOPK_WIDE_MAX; }
+
+// txe_topk_merge for 1 <= k <= 64 (infer.py:100-106 with a longer list): ceil(k / 8) rounds of topk_merge_round_kernel over the same
+// lists, each under the ceiling the round before left in ceil_ws ([nq] float keys, then [nq] int columns: 8 * nq bytes of scratch).
+// out_idx / out_key [nq][k], txe_topk_merge's conventions; for k <= 8 the one round is that kernel's selection, bit for bit.
+int txe_topk_merge_wide(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key,
+                        void* ceil_ws, void* stream) {
+    if (nq < 0 || cnt < 0 || k < 1 || k > TOPK_WIDE_MAX || !keys || !idx || !out_idx || !ceil_ws) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    float* ck = reinterpret_cast<float*>(ceil_ws);
+    int* ci = reinterpret_cast<int*>(ck + nq);
+    for (int k0 = 0; k0 < k; k0 += TOPK_MAX) {
+        const int rc = topk_merge_round(keys, idx, nq, cnt, (k - k0 < TOPK_MAX) ? k - k0 : TOPK_MAX, idx_base, out_idx + k0,
+                                        out_key ? out_key + k0 : nullptr, k, k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, (hipStream_t)stream);
+        if (rc) return rc;
+    }
     return TXE_OK;
 }
 

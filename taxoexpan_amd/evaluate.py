@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from .graph import device_egonet_batch
+from . import scoring
 from .scoring import (_retrieve_args, encode_candidates, fused_matcher_ok, log_partition_fused, prepare_matcher, rank_all_fused,
                       retrieve_candidates, topk_parents, topk_parents_fused)
 
@@ -45,11 +46,35 @@ def _score_blocks(model, hg, qf, qblock):
 
 
 def _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock, with_scores=False):
-    """the `topk` best candidates of every query, best first (infer.py:100-106 / test_fast.py:125-131): BIM / LBM / MLP / NTN with topk <= 8
-    through the fused score + select kernels (no score matrix), anything else by materialising score blocks.
-    with_scores: (ids, fp32 scores of the chosen pairs -- the matcher's own values)"""
-    if fused_matcher_ok(model.match) and 1 <= topk <= 8 and hg.shape[0] > 0 and qf.shape[0] > 0:
+    """the `topk` best candidates of every query, best first (infer.py:100-106 / test_fast.py:125-131).  BIM / LBM / MLP / NTN: up to
+    scoring.TOPK_FUSED_MAX through the fused score + select kernels (no score matrix; above 8 in rounds of 8 under a ceiling); above
+    that and up to 4,096 the retrieval stage's kernels on model scores -- score blocks of at most scoring.RETRIEVE_BLOCK_BYTES, then
+    ops.select_k (the same order: ties by ascending column, NaN last; no [Q, G] index temporaries).  Anything else (a wider list, a
+    matcher without a fused route) by materialising score blocks for the torch composite topk_parents.
+    with_scores: (ids, fp32 scores of the chosen pairs -- the matcher's own values; on the first two routes a NaN score, which ranks
+    last, is reported as the worst value)"""
+    from . import ops
+    fused = fused_matcher_ok(model.match) and hg.shape[0] > 0 and qf.shape[0] > 0
+    if fused and 1 <= topk <= scoring.TOPK_FUSED_MAX:
         return topk_parents_fused(model.match, hg, qf, cand_ids, topk, larger_is_better, block=qblock, return_scores=with_scores)
+    if fused and topk <= ops.SELECT_K_MAX:
+        G = hg.shape[0]
+        kk = min(int(topk), G)
+        pm = prepare_matcher(model.match, hg)
+        block = max(1, min(qf.shape[0], scoring.RETRIEVE_BLOCK_BYTES // (4 * G)))
+        pitch = (G + 3) // 4 * 4                                           # 16-byte row pitch, as score_block's own blocks
+        S = torch.empty((block, pitch), dtype=torch.float32, device=hg.device)
+        top, sc = [], []
+        for q0 in range(0, qf.shape[0], block):
+            qb = qf[q0:q0 + block]
+            Sb = pm.score(qb, out=S[:qb.shape[0], :G])
+            if not larger_is_better:
+                Sb.neg_()
+            idx, key = ops.select_k(Sb, kk, want_keys=True)
+            top.append(cand_ids.to(idx.device)[idx.long()])
+            sc.append(key if larger_is_better else -key)
+        ids = torch.cat(top)
+        return (ids, torch.cat(sc)) if with_scores else ids
     top, sc = [], []
     cols = torch.arange(hg.shape[0], device=hg.device)
     for _q0, S in _score_blocks(model, hg, qf, qblock or 1024):
@@ -159,7 +184,7 @@ def _best_retrieved(score, ret_dst, ridx, topk, larger_is_better):
     kk = min(int(topk), idx.shape[1])
     if idx.shape[0] == 0 or kk < 1:
         return idx[:, :0]
-    if kk <= 8:
+    if kk <= ops.TOPK_WIDE_MAX:                                             # (above 8: the same merge in rounds of 8 under a ceiling)
         return ops.topk_merge(key, idx, kk)[0]
     o1 = torch.sort(idx, dim=1, stable=True).indices                       # columns ascending (empty slots last), then keys descending
     idx, key = torch.gather(idx, 1, o1), torch.gather(key, 1, o1)
@@ -194,6 +219,9 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     case: test_fast.py's `-c` -- a path (the TSV of :142-147 is written) or a list (the rows are appended): per query its name, true
     parents, the `topk` predicted parents (best first: descending score when larger_is_better, i.e. the info_nce losses, ascending
     otherwise; ties in candidate order like Python's stable sort) and the metrics of `metric_names` on that query alone.
+    topk: any size.  For BIM / LBM / MLP / NTN no [queries x candidates] index temporaries are made up to 4,096: up to
+    scoring.TOPK_FUSED_MAX the list comes from the fused kernels (no score matrix either; above 8 in rounds of 8 under a ceiling), above
+    it from score blocks + ops.select_k (_best_parents).  The order is the same on every route.
     retrieve: None = every positive against ALL candidates, unmasked (test_fast.py; `dataset.test_topk` is ignored).  retrieve=k
     (1 <= k <= 4096, else ValueError before any launch) = the retrieve-then-rank protocol of dataset.py:316-330 (`-k`): a query's
     instance is its true parents plus the k candidates nearest to it by cosine distance of `dataset.node_features` among those
@@ -284,6 +312,8 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     nodes of the dataset's graph (infer.py:80-82 iterates `test_dataset.graph.nodes()`, not `all_positions`), in node order; best =
     descending score for the info_nce losses, ascending otherwise (infer.py:100-106), ties in candidate order like Python's stable
     sort.  Returns [(query, [parent vocab entries])]; `save` writes infer.py's TSV (header `Query\tPredicted parents`).
+    topk: any size (a curator's 10 or 20, a re-ranker's 50): evaluate()'s routes -- fused up to scoring.TOPK_FUSED_MAX, score blocks +
+    ops.select_k up to 4,096, the same order and (with_scores) the same fp32 scores on each.
     retrieve=k (infer.py's `-k`; 1 <= k <= 4096, else ValueError before any launch): the candidates of each new term are its k
     cosine-nearest graph nodes (the new-term vectors against `dataset.node_features`; no masks, a new term has none), and the `topk`
     best parents are chosen among them by matcher score.  Exact distance ties break by ascending node position.

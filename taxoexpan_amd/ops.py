@@ -1928,15 +1928,27 @@ def _topk_scratch(sc, nq, need, ref):
     return sc
 
 
+TOPK_WIDE_MAX = 64          # txe_topk_wide_max(): the widest fused best-k (rounds of 8 under a ceiling; csrc/txe_common.h)
+
+
+def _topk_ceil(sc, nq, ref):
+    """the wide best-k entry points' ceilings (8 * nq bytes: [nq] fp32 keys, then [nq] int32 columns) beside _topk_scratch's buffers"""
+    if sc.get("ceil_nq", 0) < nq or sc["ceil"].device != ref.device:
+        sc["ceil"], sc["ceil_nq"] = torch.empty(2 * nq, dtype=torch.int32, device=ref.device), nq
+    return sc["ceil"]
+
+
 def score_topk_block(Q, U, apply_exp, k, larger_is_better=True, idx_base=0, q_padded=False, scratch=None):
     """fused scoring + best-k selection of one query block against a candidate (shard) matrix U (txe_score_topk_block): returns
     (idx int32 [nq, k] = candidate rows + idx_base, best first, ties by ascending row like Python's stable sort, NaN last;
-    key fp32 [nq, k] = the scores, negated when smaller is better).  No [nq x G] block is materialised.  1 <= k <= min(8, G).
+    key fp32 [nq, k] = the scores, negated when smaller is better).  No [nq x G] block is materialised.  1 <= k <= min(64, G): up to 8
+    the one pass of txe_score_topk_block, above it txe_score_topk_wide_block's ceil(k / 8) rounds of 8 under a ceiling (same order, same
+    scores, one pass of the score tiles per round).
     q_padded: as in score_count_block.  scratch: dict reused across the blocks of a loop (the per-tile lists)."""
     prep = _as_prepared(U)
     _need_cuda(Q, prep.full)
     G = prep.G
-    assert 1 <= k <= 8 and k <= G, "score_topk_block: 1 <= k <= min(8, candidates)"
+    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, "score_topk_block: 1 <= k <= min(64, candidates)"
     Q, ldq, K = _lay_queries(Q, prep, q_padded)
     nq = Q.shape[0]
     idx = torch.empty((nq, k), dtype=torch.int32, device=Q.device)
@@ -1946,22 +1958,32 @@ def score_topk_block(Q, U, apply_exp, k, larger_is_better=True, idx_base=0, q_pa
     with _lib.on_device(Q.device):
         up = _planes(prep, K)
         sws, swb = _score_sws(nq, G, K, Q, up is not None)
-        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * k, Q)
-        call("txe_score_topk_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), int(larger_is_better), int(k),
-             int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), ptr(sws), swb, ptr(up), _lib.stream_ptr())
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), Q)
+        args = (ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), int(larger_is_better), int(k), int(idx_base),
+                ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), ptr(sws), swb, ptr(up))
+        if k <= 8:
+            call("txe_score_topk_block", *args, _lib.stream_ptr())
+        else:
+            call("txe_score_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, Q)), _lib.stream_ptr())
     return idx, key
 
 
 def topk_merge(keys, idx, k):
     """best k of the (key, idx) entries of every row (txe_topk_merge; keys fp32 / idx int32 [nq, cnt], idx == INT_MAX: empty slot):
-    the merge of per-rank best-k lists of a candidate-sharded loop.  Returns (idx [nq, k], key [nq, k])."""
+    the merge of per-rank best-k lists of a candidate-sharded loop.  Returns (idx [nq, k], key [nq, k]).  1 <= k <= 64: above 8
+    txe_topk_merge_wide's rounds of 8 under a ceiling over the same lists (the idx of a row must then be distinct)."""
     _need_cuda(keys, idx)
+    assert 1 <= k <= TOPK_WIDE_MAX, "topk_merge: 1 <= k <= 64"
     keys, idx = _f32(keys), idx.to(torch.int32).contiguous()
     nq, cnt = keys.shape
     out_i = torch.empty((nq, k), dtype=torch.int32, device=keys.device)
     out_k = _empty((nq, k), keys)
     with _lib.on_device(keys.device):
-        call("txe_topk_merge", ptr(keys), ptr(idx), nq, cnt, int(k), 0, ptr(out_i), ptr(out_k), _lib.stream_ptr())
+        if k <= 8:
+            call("txe_topk_merge", ptr(keys), ptr(idx), nq, cnt, int(k), 0, ptr(out_i), ptr(out_k), _lib.stream_ptr())
+        else:
+            ceil = torch.empty(2 * max(nq, 1), dtype=torch.int32, device=keys.device)
+            call("txe_topk_merge_wide", ptr(keys), ptr(idx), nq, cnt, int(k), 0, ptr(out_i), ptr(out_k), ptr(ceil), _lib.stream_ptr())
     return out_i, out_k
 
 
@@ -2233,19 +2255,24 @@ def mlp_score_count_block(Q, prep, pos_off, thr, larger_is_better=True, counts=N
 
 def mlp_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=None):
     """fused scoring + best-k selection of one query block (txe_mlp_score_topk_block): (idx int32 [nq, k] = candidate rows + idx_base,
-    key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(8, G).  scratch: dict reused across blocks."""
+    key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(64, G), above 8 by txe_mlp_score_topk_wide_block's
+    rounds.  scratch: dict reused across blocks."""
     qp = mlp_prepare_queries(Q, prep)
     dev = prep.Ap.device
     G, nq = prep.G, qp.n
-    assert 1 <= k <= 8 and k <= G, "mlp_score_topk_block: 1 <= k <= min(8, candidates)"
+    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, "mlp_score_topk_block: 1 <= k <= min(64, candidates)"
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     key = torch.empty((nq, k), dtype=torch.float32, device=dev)
     if nq == 0:
         return idx, key
     with _lib.on_device(dev):
-        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * k, prep.Ap)
-        call("txe_mlp_score_topk_block", *_mlp_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]),
-             ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), prep.Ap)
+        args = (*_mlp_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx),
+                ptr(key))
+        if k <= 8:
+            call("txe_mlp_score_topk_block", *args, _lib.stream_ptr())
+        else:
+            call("txe_mlp_score_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, prep.Ap)), _lib.stream_ptr())
     return idx, key
 
 
@@ -2422,19 +2449,24 @@ def ntn_score_count_block(Q, prep, pos_off, thr, larger_is_better=True, counts=N
 
 def ntn_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=None):
     """fused scoring + best-k selection of one query block (txe_ntn_score_topk_block): (idx int32 [nq, k] = candidate rows + idx_base,
-    key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(8, G).  scratch: dict reused across blocks."""
+    key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(64, G), above 8 by txe_ntn_score_topk_wide_block's
+    rounds.  scratch: dict reused across blocks."""
     qp = ntn_prepare_queries(Q, prep)
     dev = prep.full.device
     G, nq = prep.G, qp.n
-    assert 1 <= k <= 8 and k <= G, "ntn_score_topk_block: 1 <= k <= min(8, candidates)"
+    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, "ntn_score_topk_block: 1 <= k <= min(64, candidates)"
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     key = torch.empty((nq, k), dtype=torch.float32, device=dev)
     if nq == 0:
         return idx, key
     with _lib.on_device(dev):
-        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * k, prep.full)
-        call("txe_ntn_score_topk_block", *_ntn_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]),
-             ptr(sc["floor"]), ptr(idx), ptr(key), _lib.stream_ptr())
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), prep.full)
+        args = (*_ntn_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx),
+                ptr(key))
+        if k <= 8:
+            call("txe_ntn_score_topk_block", *args, _lib.stream_ptr())
+        else:
+            call("txe_ntn_score_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, prep.full)), _lib.stream_ptr())
     return idx, key
 
 

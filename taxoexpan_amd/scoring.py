@@ -609,11 +609,61 @@ class overlapped_gradient_allreduce:
         self._pending = []
 
 
+# the widest k evaluate._best_parents gives to the fused rounds (<= ops.TOPK_WIDE_MAX = 64); above it the score block + select route.
+# Measured (tools/topk_wide_timing.py, MAG-Full, 8,192 queries x 356 k candidates, one MI355X; profiles/NOTES.md): the rounds cost
+# 22.0 / 26.1 / 35.5 / 40.1 / 53.0 / 99.8 ms at k = 9 / 16 / 17 / 24 / 32 / 64, score blocks + txe_select_k 47.4-48.4 ms at every k:
+# 24 is the largest measured k at which the rounds are not the slower route.
+TOPK_FUSED_MAX = 24
+
+
+def host_topk_rounds(S, k, larger_is_better=True, idx_base=0):
+    """the wide best-k kernels' specification in numpy, literally as they run (csrc/txe_common.h): rounds of 8 under a ceiling.  The
+    order is total over (key, column) -- better key first, equal keys by ascending column; key = the score, negated when smaller is
+    better, NaN as -inf -- so a row's best k are its best 8, then the best 8 among the entries strictly worse than the 8th chosen, ...
+    Each round scans the row keeping a sorted list of at most 8 eligible entries (an entry enters only if it beats the list's last) and
+    hands its last SLOT to the next round as the ceiling exactly as it stands: an empty slot is (-inf, INT_MAX), under which nothing is
+    eligible.  S [nq, G] -> (idx int64 [nq, k] = column + idx_base, -1 behind the row's last entry; key float64 [nq, k], -inf there).
+    Ceiling columns are local: idx_base is added on output only."""
+    import numpy as np
+    S = np.asarray(S, dtype=np.float64)
+    key = S if larger_is_better else -S
+    key = np.where(np.isnan(key), -np.inf, key)
+    nq, G = key.shape
+    k = int(k)
+    EMPTY = (-np.inf, 0x7fffffff)
+
+    def better(a, b):                                   # topk_better: (key, column) a strictly before b
+        return a[0] > b[0] or (a[0] == b[0] and a[1] < b[1])
+    idx, out = np.full((nq, k), -1, dtype=np.int64), np.full((nq, k), -np.inf)
+    for q in range(nq):
+        ceil = None                                     # first round: every entry is eligible
+        for k0 in range(0, k, 8):
+            kr = min(8, k - k0)
+            slots = [EMPTY] * kr
+            for n in range(G):
+                e = (float(key[q, n]), n)
+                if ceil is not None and not better(ceil, e):
+                    continue
+                if better(e, slots[-1]):
+                    slots[-1] = e
+                    t = kr - 1
+                    while t > 0 and better(slots[t], slots[t - 1]):
+                        slots[t - 1], slots[t] = slots[t], slots[t - 1]
+                        t -= 1
+            for t, (kv, n) in enumerate(slots):
+                idx[q, k0 + t] = -1 if n == EMPTY[1] else n + idx_base
+                out[q, k0 + t] = kv
+            ceil = slots[-1]
+    return idx, out
+
+
 def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_better=True, block=None, group=None, shard_lo=0, sharded=False,
                        return_scores=False):
     """infer.py:96-106 / test_fast.py:121-131 without the score matrix: per query block ONE launch of the score GEMM whose epilogue keeps
     each tile's best k columns per row (txe_score_topk_block) + a merge launch -- no [Q, G] scores, no [Q, G] index temporaries (the
-    torch composite topk_parents below needs two int64 [Q, G] ones: 3.5 GB per 1,024-query block on MAG-Full).  Same selection and
+    torch composite topk_parents below needs two int64 [Q, G] ones: 3.5 GB per 1,024-query block on MAG-Full).  k <= 64: above 8 the
+    selection runs in ceil(k / 8) rounds of 8 under a ceiling (txe_score_topk_wide_block; host_topk_rounds states them), one pass of the
+    score tiles per round, still without a score block.  Same selection and
     order as topk_parents on the materialised scores of the same kernel (bit-identical values): better score first, ties by ascending
     candidate position (Python's stable sort), NaN last.  match: BIM / LBM / MLP / NTN.  hg: this rank's candidate rows (positions
     [shard_lo, shard_lo + len) of the global list).  Candidate-sharded (ONLY when asked: `group` given or sharded=True, _sharded_call
@@ -625,8 +675,8 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
     dev = hg.device
     distributed = _sharded_call(group, sharded)
     Q, G = queries.shape[0], hg.shape[0]
-    k_loc = min(int(k), G, 8)
-    assert int(k) <= 8, "topk_parents_fused: k <= 8 (the kernels keep 8 entries per list)"
+    k_loc = min(int(k), G, ops.TOPK_WIDE_MAX)
+    assert int(k) <= ops.TOPK_WIDE_MAX, "topk_parents_fused: k <= 64 (rounds of 8 under a ceiling; wider lists: score blocks + ops.select_k)"
     if block is None:
         block = 1024 if Q > 4096 else max(Q, 1)
     outs = []
@@ -643,7 +693,7 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
         key = torch.zeros((Q, 0), dtype=torch.float32, device=dev)
     if distributed:
         world = dist.get_world_size(group)
-        kk = min(int(k), 8)
+        kk = min(int(k), ops.TOPK_WIDE_MAX)
         # every rank contributes kk slots per query (a rank with fewer candidates pads with empty slots)
         pad_i = torch.full((Q, kk), 0x7fffffff, dtype=torch.int32, device=dev)
         pad_k = torch.full((Q, kk), -float("inf"), dtype=torch.float32, device=dev)
