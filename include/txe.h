@@ -629,6 +629,23 @@ int txe_sample_anchors(const int* order, int n_order, int start, int Q, const in
                        const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k, unsigned long long seed,
                        int epoch, int repeated, int* packed, int* n_padded, void* stream);
 
+/* ---- txe_sample_anchors with hard negatives: the first negative slots of a query come from a mined table, the rest from the pool.
+ * hard_idx [n_queries, H] int32, row i for node_list[i] (i = order[s], the index the epoch order holds): node ids, best first;
+ * hard_cnt [n_queries]: the valid entries of each row.  For the query at epoch position s, c = min(max(hard_cnt[i], 0), H),
+ * m = min(hard_slots, c) and one rotation r = (hi32(h) c) >> 32, h = mix64(seed ^ mix64(epoch << 44 | s << 20 | 16383 << 6)) (slot
+ * value 16383 is free: k < 2^14): negative slot j < m takes hard_idx[i H + (r + j) % c] without a rejection loop (a row's entries are
+ * distinct), unless that entry is in q's mask row, negative or above pool[n_pool - 1] (pool must be ascending here) -- then, and for
+ * every slot j >= m, the slot is txe_sample_anchors' slot j bit for bit: the same draws, tries and *n_padded accounting.  So
+ * hard_slots = 0 or an all-empty table give txe_sample_anchors' output, and no table can put an invalid or masked id into a batch.
+ * Mined negatives are plain negatives (exclude -1): the query can be in an anchor's egonet only when the anchor is the query, a parent
+ * or a child of it, and all of those are masked.
+ * TXE_ERR_ARG (before any device work): everything txe_sample_anchors refuses, a NULL hard_idx or hard_cnt, H < 1, hard_slots < 0 or
+ * hard_slots > k. */
+int txe_sample_anchors_hard(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                            const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k,
+                            unsigned long long seed, int epoch, int repeated, int* packed, int* n_padded, const int* hard_idx,
+                            const int* hard_cnt, int H, int hard_slots, void* stream);
+
 /* ---- validation-anchor sampling on device, sampling_mode 0: data_loader/dataset.py:304-307,340-355 (every parent, then at most k
  * negatives) for the Q queries at positions start .. start+Q-1 of the epoch order.  Query i's run: node2parents[q] in order (label 1,
  * exclude q), then the surviving negatives in slot order (label 0, exclude -1).  Negative slot j of epoch position s in round t draws

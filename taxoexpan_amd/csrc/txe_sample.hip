@@ -28,6 +28,32 @@ __device__ __forceinline__ int lower_bound(const int* __restrict__ r, int n, int
     return lo;
 }
 
+// The positive of query q, batch row i (one lane per query calls it): dataset.py:336-340's pointer walk, and the query's id / run entry.
+__device__ __forceinline__ void emit_positive(int q, int i, int Q, int B, int base, const int* __restrict__ par_ptr,
+                                              const int* __restrict__ par_idx, int* __restrict__ pos_ptr, int repeated,
+                                              int* __restrict__ packed) {
+    int* anchors = packed;
+    int* exclude = packed + B;
+    int* qids = packed + 2 * B;
+    const int pb = par_ptr[q], np_ = par_ptr[q + 1] - pb;
+    int p = q;                                        // (a query always has a parent: sampler.py checks; never an invalid id regardless)
+    if (np_ > 0) {
+        int c = pos_ptr[q];
+        c = (c >= 0 && c < np_) ? c : 0;
+        p = par_idx[pb + c];
+        pos_ptr[q] = (c + 1) % np_;
+    }
+    anchors[base] = p;
+    exclude[base] = q;
+    if (repeated) {                                   // one run per query: the distinct id and the run's first pair
+        qids[i] = q;
+        packed[3 * B + i] = base;
+        if (i == Q - 1) packed[3 * B + Q] = B;
+    } else {
+        qids[base] = q;
+    }
+}
+
 // One wavefront per query, lane = negative slot (strides of 64 for k >= 64); lane 0 also takes the positive.
 // A query appears once in an epoch order, and the loader's two batches in flight run on its one side stream, so no two waves -- of one
 // launch or of two -- touch the same positive pointer at the same time: the read-modify-write of pos_ptr needs no atomic.
@@ -47,25 +73,7 @@ __global__ __launch_bounds__(256) void sample_anchors_kernel(const int* __restri
     int* anchors = packed;
     int* exclude = packed + B;
     int* qids = packed + 2 * B;
-    if (l == 0) {                                     // the positive: dataset.py:336-340
-        const int pb = par_ptr[q], np_ = par_ptr[q + 1] - pb;
-        int p = q;                                    // (a query always has a parent: sampler.py checks; never an invalid id regardless)
-        if (np_ > 0) {
-            int c = pos_ptr[q];
-            c = (c >= 0 && c < np_) ? c : 0;
-            p = par_idx[pb + c];
-            pos_ptr[q] = (c + 1) % np_;
-        }
-        anchors[base] = p;
-        exclude[base] = q;
-        if (repeated) {                               // one run per query: the distinct id and the run's first pair
-            qids[i] = q;
-            packed[3 * B + i] = base;
-            if (i == Q - 1) packed[3 * B + Q] = B;
-        } else {
-            qids[base] = q;
-        }
-    }
+    if (l == 0) emit_positive(q, i, Q, B, base, par_ptr, par_idx, pos_ptr, repeated, packed);
     const int mb = mask_ptr[q], mn = mask_ptr[q + 1] - mb;
     const int* mrow = mask_idx + mb;
     for (int j0 = 0; j0 < k; j0 += 64) {
@@ -103,6 +111,71 @@ __device__ __forceinline__ int group_draw(unsigned long long seed, int epoch, in
 __device__ __forceinline__ bool unmasked(const int* __restrict__ mrow, int mn, int a) {
     const int at = lower_bound(mrow, mn, a);
     return !(at < mn && mrow[at] == a);
+}
+
+// ---- hard negatives: the first slots of a query come from a mined table (sampler.mine_hard_negatives: the best unmasked pool nodes of
+// node_list[i] under the model, best first), the rest from the pool route above.  Row i = order[s] of hard_idx [n_queries, H] holds
+// c = min(max(hard_cnt[i], 0), H) entries; m = min(hard_slots, c) slots are hard.  One rotation per query and epoch,
+// r = (hi32(h) c) >> 32 with h = mix64(seed ^ mix64(ctr(epoch, s, HARD_ROT_SLOT, 0))), and slot j < m takes row[(r + j) % c]: no
+// rejection loop, the entries of a row are distinct.  Every other slot is txe_sample_anchors' slot bit for bit (the same hash of
+// (seed, epoch, s, j, t), the same tries, the same n_padded accounting).
+// Why a mined negative is a plain negative with exclude = -1: an anchor's egonet is its parents, itself and its children
+// (dataset.py:404-437), so the query can appear in it only if the anchor is the query, one of its parents or one of its children -- all
+// of them in node2masks[q], and mining selects among unmasked candidates only.  The kernel does not rely on the table for that: an entry
+// that is in q's mask row, negative or above the largest pool id (pool is ascending: sorted(all_positions)) sends its slot down the
+// pool route, so a bad table cannot put an invalid or masked id into a batch.
+#define HARD_ROT_SLOT 16383                           // the one value of the 14-bit slot field no negative slot takes (k < 1 << 14)
+
+__global__ __launch_bounds__(256) void sample_anchors_hard_kernel(const int* __restrict__ order, int start, int Q, const int* __restrict__ node_list,
+                                                                  const int* __restrict__ par_ptr, const int* __restrict__ par_idx,
+                                                                  const int* __restrict__ mask_ptr, const int* __restrict__ mask_idx,
+                                                                  const int* __restrict__ pool, int n_pool, int* __restrict__ pos_ptr, int k,
+                                                                  unsigned long long seed, int epoch, int repeated, int* __restrict__ packed,
+                                                                  int* __restrict__ n_padded, const int* __restrict__ hard_idx,
+                                                                  const int* __restrict__ hard_cnt, int H, int hard_slots) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + w;
+    if (i >= Q) return;
+    const int s = start + i;
+    const int oi = order[s];
+    const int q = node_list[oi];
+    const int B = Q * (1 + k);
+    const int base = i * (1 + k);
+    int* anchors = packed;
+    int* exclude = packed + B;
+    int* qids = packed + 2 * B;
+    if (l == 0) emit_positive(q, i, Q, B, base, par_ptr, par_idx, pos_ptr, repeated, packed);
+    const int mb = mask_ptr[q], mn = mask_ptr[q + 1] - mb;
+    const int* mrow = mask_idx + mb;
+    int c = hard_cnt[oi];
+    c = c < 0 ? 0 : (c > H ? H : c);                  // (a count above the row width reads no further than the row)
+    const int m = hard_slots < c ? hard_slots : c;
+    const int* hrow = hard_idx + (size_t)oi * (size_t)H;
+    int r = 0;
+    if (m > 0) {
+        const uint64_t h = mix64(seed ^ mix64(sample_ctr(epoch, s, HARD_ROT_SLOT, 0)));
+        r = (int)(((h >> 32) * (uint64_t)c) >> 32);
+    }
+    const int id_max = pool[n_pool - 1];              // the largest pool id
+    for (int j0 = 0; j0 < k; j0 += 64) {
+        const int j = j0 + l;
+        if (j >= k) break;
+        int a = 0;
+        bool ok = false;
+        if (j < m) {                                  // r < c and j < m <= c: r + j < 2c, no overflow
+            a = hrow[(r + j) % c];
+            ok = a >= 0 && a <= id_max && unmasked(mrow, mn, a);
+        }
+        for (int t = 0; t < SAMPLE_TRIES && !ok; ++t) {
+            a = group_draw(seed, epoch, s, j, t, pool, n_pool);
+            ok = unmasked(mrow, mn, a);
+        }
+        if (!ok) atomicAdd(n_padded, 1);
+        const int o = base + 1 + j;
+        anchors[o] = a;
+        exclude[o] = -1;
+        if (!repeated) qids[o] = q;
+    }
 }
 
 __global__ __launch_bounds__(256) void sample_groups_count_kernel(const int* __restrict__ order, int start, int Q, const int* __restrict__ node_list,
@@ -246,6 +319,24 @@ int txe_sample_anchors(const int* order, int n_order, int start, int Q, const in
     if (Q == 0) return TXE_OK;
     hipLaunchKernelGGL(sample_anchors_kernel, dim3((Q + 3) / 4), dim3(256), 0, (hipStream_t)stream, order, start, Q, node_list, par_ptr,
                        par_idx, mask_ptr, mask_idx, pool, n_pool, pos_ptr, k, seed, epoch, repeated, packed, n_padded);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
+int txe_sample_anchors_hard(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                            const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k,
+                            unsigned long long seed, int epoch, int repeated, int* packed, int* n_padded, const int* hard_idx,
+                            const int* hard_cnt, int H, int hard_slots, void* stream) {
+    if (!order || !node_list || !par_ptr || !par_idx || !mask_ptr || !mask_idx || !pool || !pos_ptr || !packed || !n_padded) return TXE_ERR_ARG;
+    if (!hard_idx || !hard_cnt || H < 1) return TXE_ERR_ARG;
+    if (k < 1 || k >= (1 << 14) || Q < 0 || n_pool < 1 || n_order < 0 || start < 0 || epoch < 0 || epoch >= (1 << 20)) return TXE_ERR_ARG;
+    if (hard_slots < 0 || hard_slots > k) return TXE_ERR_ARG;
+    if ((long long)start + Q > n_order || (long long)start + Q > (1 << 24)) return TXE_ERR_ARG;
+    if (4LL * Q * (1 + k) + 1 > 0x7fffffffLL) return TXE_ERR_ARG;
+    if (Q == 0) return TXE_OK;
+    hipLaunchKernelGGL(sample_anchors_hard_kernel, dim3((Q + 3) / 4), dim3(256), 0, (hipStream_t)stream, order, start, Q, node_list, par_ptr,
+                       par_idx, mask_ptr, mask_idx, pool, n_pool, pos_ptr, k, seed, epoch, repeated, packed, n_padded, hard_idx, hard_cnt, H,
+                       hard_slots);
     TXE_CHECK_LAUNCH();
     return TXE_OK;
 }

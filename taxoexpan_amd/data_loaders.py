@@ -207,15 +207,20 @@ class DeviceBatchLoader:
     batch -- no host work per pair, no upload per batch (the epoch order goes up once per epoch), labels a cached device tensor.  Its
     positives walk the same pointers as the host sampler, starting from the dataset's node2positive_pointer when the loader is made; the
     host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py).
+    hard_negatives / hard_slots (this sampler only; default off): a sampler.HardNegatives table whose rows fill the first hard_slots
+    negative slots of every query (txe_sample_anchors_hard); set_hard_negatives changes it between epochs.
     sampler="device" on a sampling_mode 0 dataset (validation batches of the shipped configs; train / validation): sampler.DeviceGroupSampler
     draws every parent and at most negative_size negatives per query, labels an int64 device tensor.  The batch size B is then known on
     the device only, so three batches are in flight: each next() after the first finishes batch b (its node count, read back one next()
     ago), begins the egonet count of batch b+1 (its B, read back one next() ago) and samples batch b+2 -- no next() waits on work it
     enqueued itself."""
 
-    def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host"):
+    def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host",
+                 hard_negatives=None, hard_slots=0):
         if sampler not in ("host", "device"):
             raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
+        if hard_negatives is not None and not (sampler == "device" and dataset.sampling_mode == 1):
+            raise ValueError("hard negatives need sampler='device' on a sampling_mode 1 dataset")
         self.repeated_queries = bool(repeated_queries)
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         self.shuffle, self.seed, self.drop_last = shuffle, int(seed), drop_last
@@ -232,6 +237,19 @@ class DeviceBatchLoader:
             self._labels = {}
         torch.cuda.current_stream(self.device).synchronize()      # the resident taxonomy / feature table are complete from here on
         self._epoch = 0
+        if hard_negatives is not None:
+            self.set_hard_negatives(hard_negatives, hard_slots)
+
+    def set_hard_negatives(self, table, slots=0):
+        """from the next epoch's first batch on, the first `slots` negatives of every query come from `table` (sampler.HardNegatives,
+        e.g. sampler.mine_hard_negatives; None: uniform draws again) -- DeviceAnchorSampler.set_hard_negatives.  ValueError on a loader
+        whose sampler is 'host' or the sampling_mode 0 group sampler, for slots outside [0, negative_size] or a table of another row
+        count; RuntimeError while an epoch is being iterated (two batches are in flight on the side stream)."""
+        from .sampler import DeviceAnchorSampler
+        if not isinstance(self.sampler, DeviceAnchorSampler):
+            raise ValueError("hard negatives need sampler='device' on a sampling_mode 1 dataset (the host sampler and the sampling_mode 0 "
+                             "group sampler draw from the pool only)")
+        self.sampler.set_hard_negatives(table, slots)
 
     def __len__(self):
         n = len(self.dataset)
@@ -278,12 +296,16 @@ class DeviceBatchLoader:
             Q = min(bs, n - b * bs)
             return Q, self.sampler.begin(order_dev, b * bs, Q, epoch, self.repeated_queries, self._side,
                                          egonet_seed=self.seed + 7919 * self._epoch + b)
-        nxt = begin(0) if len(self) else None
-        for b in range(len(self)):
-            Q, pending = nxt
-            batch = finish_device_batch(pending, self.features)
-            nxt = begin(b + 1) if b + 1 < len(self) else None
-            yield batch["g"], batch["x"], batch["qf"], self._label(Q)
+        self.sampler.in_epoch = True                                 # (set_hard_negatives refuses until the epoch's batches are out)
+        try:
+            nxt = begin(0) if len(self) else None
+            for b in range(len(self)):
+                Q, pending = nxt
+                batch = finish_device_batch(pending, self.features)
+                nxt = begin(b + 1) if b + 1 < len(self) else None
+                yield batch["g"], batch["x"], batch["qf"], self._label(Q)
+        finally:
+            self.sampler.in_epoch = False
 
     def _iter_groups(self, order, epoch):
         """sampling_mode 0: sample b+2, begin the egonet count of b+1, finish b (see the class docstring)"""

@@ -6,7 +6,12 @@ What is reproduced: the positive walk exactly (the same pointer arithmetic over 
 of epoch orders equal the host sampler's), and the distribution of the negatives -- uniform over the distinct content of the reference's
 5x queue (sorted(all_positions)), rejected while masked.  What is not: the `random`-module trace of the queue shuffles (a negative slot
 is a counter-based hash of (seed, epoch, epoch position, slot, attempt), host_draw restates it bit for bit) and the negative-egonet
-cache (dataset.py:390-400), which the device egonet builder never had either."""
+cache (dataset.py:390-400), which the device egonet builder never had either.
+
+Hard negatives (off by default): mine_hard_negatives ranks every pool node for every training query under the model as it stands
+(candidate encode, score blocks, ops.select_k with the query's masks) and keeps the best `size` per query in a HardNegatives table;
+txe_sample_anchors_hard then fills the first `hard_slots` negative slots of a query from its row (one rotation per query and epoch)
+and the rest from the pool as before.  host_draw(hard=..., hard_slots=...) restates that draw, host_hard_table the table."""
 import numpy as np
 import torch
 
@@ -14,6 +19,7 @@ from . import _lib
 from .rng import _mix64
 
 TRIES = 64           # SAMPLE_TRIES of csrc/txe_sample.hip: rejections before a slot keeps its (masked) last draw
+HARD_ROT_SLOT = 16383    # HARD_ROT_SLOT of csrc/txe_sample.hip: the slot value of the rotation's counter (no negative slot takes it: k < 2^14)
 
 
 def _check(dataset):
@@ -63,11 +69,26 @@ def _ctr(epoch, s, j, t):
     return (u(epoch) << np.uint64(44)) | (u(s) << np.uint64(20)) | (u(j) << np.uint64(6)) | u(t)
 
 
-def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=False):
+def _hard_arrays(hard):
+    """(idx int64 [n_queries, H], cnt int64 [n_queries]) on the host from a HardNegatives or an (idx, cnt) pair of arrays"""
+    idx, cnt = hard.numpy() if isinstance(hard, HardNegatives) else hard
+    idx, cnt = np.asarray(idx).astype(np.int64), np.asarray(cnt).astype(np.int64).reshape(-1)
+    if idx.ndim != 2 or idx.shape[1] < 1 or idx.shape[0] != cnt.shape[0]:
+        raise ValueError(f"a hard-negative table is idx [n_queries, H >= 1] and cnt [n_queries], got {idx.shape} and {cnt.shape}")
+    return idx, cnt
+
+
+def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=False, hard=None, hard_slots=0):
     """numpy restatement of txe_sample_anchors for the Q queries at positions start .. start+Q-1 of `order` (indices into node_list).
     ptr: the positive pointers (int32 [n]), advanced in place; default a copy of arrays['ptr'].  Returns dict(anchors, exclude, query
-    [B]; runs [Q] and offsets [Q+1] with repeated_queries; n_padded) -- the arrays the kernel writes, bit for bit."""
+    [B]; runs [Q] and offsets [Q+1] with repeated_queries; n_padded) -- the arrays the kernel writes, bit for bit.
+    hard (a HardNegatives, or its (idx, cnt) as arrays) with hard_slots in [0, k]: the restatement of txe_sample_anchors_hard, in
+    integers like the rest: query i = order[s] has c = min(max(cnt[i], 0), H) entries, m = min(hard_slots, c) hard slots and the rotation
+    r = (hi32(h) c) >> 32, h = mix64(seed ^ mix64(ctr(epoch, s, HARD_ROT_SLOT, 0))); slot j < m is idx[i, (r + j) % c] unless that entry
+    is masked for the query, negative or above the largest pool id -- then, and for j >= m, the slot is the pool draw it is without a table."""
     k = arrays["k"]
+    if hard is not None and not 0 <= int(hard_slots) <= k:
+        raise ValueError(f"hard_slots must be in [0, {k}], got {hard_slots}")
     pool, mask_ptr, mask_idx = arrays["pool"], arrays["mask_ptr"], arrays["mask_idx"]
     ptr = arrays["ptr"].copy() if ptr is None else ptr
     s = np.arange(start, start + Q, dtype=np.int64)
@@ -82,14 +103,27 @@ def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=F
         j, t = np.arange(k)[None, :, None], np.arange(TRIES)[None, None, :]
         h = _mix64(np.uint64(seed) ^ _mix64(_ctr(epoch, s[:, None, None], j, t)))
         draws = pool[(((h >> np.uint64(32)) * np.uint64(len(pool))) >> np.uint64(32)).astype(np.int64)]      # [Q, k, TRIES]
+        if hard is not None:
+            hidx, hcnt = _hard_arrays(hard)
+            rows = np.asarray(order, dtype=np.int64)[s]
+            cnt = np.clip(hcnt[rows], 0, hidx.shape[1])
+            n_hard = np.minimum(int(hard_slots), cnt)
+            hr = _mix64(np.uint64(seed) ^ _mix64(_ctr(epoch, s, HARD_ROT_SLOT, 0)))
+            rot = (((hr >> np.uint64(32)) * cnt.astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
     neg = np.empty((Q, k), dtype=np.int64)
     n_padded = 0
     for i, v in enumerate(q):
         row = mask_idx[mask_ptr[v]:mask_ptr[v + 1]]
         ok = ~np.isin(draws[i], row)
         first = np.where(ok.any(1), ok.argmax(1), TRIES - 1)
-        n_padded += int((~ok.any(1)).sum())
+        padded = ~ok.any(1)
         neg[i] = draws[i, np.arange(k), first]
+        if hard is not None:
+            for j in range(int(n_hard[i])):
+                e = int(hidx[rows[i], (rot[i] + j) % cnt[i]])
+                if 0 <= e <= int(pool[-1]) and e not in row:       # else: the pool route, as without a table
+                    neg[i, j], padded[j] = e, False
+        n_padded += int(padded.sum())
     anchors = np.concatenate([pos[:, None], neg], 1).reshape(-1)
     exclude = np.concatenate([q[:, None], np.full((Q, k), -1, dtype=np.int64)], 1).reshape(-1)
     out = dict(anchors=anchors, exclude=exclude, query=np.repeat(q, 1 + k), n_padded=n_padded)
@@ -98,9 +132,155 @@ def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=F
     return out
 
 
+class HardNegatives:
+    """The mined hard negatives of every training query, on a device: idx int32 [n_queries, H] -- row i belongs to dataset.node_list[i]
+    (the index an epoch order holds), node ids best first, unused entries -1 at the tail only -- and cnt int32 [n_queries], the valid
+    entries of each row.  mine_hard_negatives makes one from the model; from_numpy validates one made elsewhere."""
+
+    def __init__(self, idx, cnt):
+        if idx.dim() != 2 or idx.shape[1] < 1 or cnt.shape != (idx.shape[0],) or idx.dtype != torch.int32 or cnt.dtype != torch.int32:
+            raise ValueError(f"HardNegatives: idx int32 [n_queries, H >= 1] and cnt int32 [n_queries], got {tuple(idx.shape)} {idx.dtype} "
+                             f"and {tuple(cnt.shape)} {cnt.dtype}")
+        self.idx, self.cnt = idx.contiguous(), cnt.contiguous()
+
+    n_queries = property(lambda self: int(self.idx.shape[0]))
+    H = property(lambda self: int(self.idx.shape[1]))
+    device = property(lambda self: self.idx.device)
+
+    def numpy(self):
+        """(idx, cnt) as host arrays (synchronises the device)"""
+        return self.idx.cpu().numpy(), self.cnt.cpu().numpy()
+
+    @classmethod
+    def from_numpy(cls, idx, dataset, device):
+        """a table from a host array idx [len(node_list), H] of node ids (-1 = unused), checked on the host: ValueError for another shape,
+        H < 1, an entry that is neither -1 nor in all_positions, a valid entry after a -1, a duplicate in a row, or an entry in the
+        query's node2masks.  cnt is the number of valid entries per row."""
+        a = np.asarray(idx)
+        n = len(dataset.node_list)
+        if a.ndim != 2 or a.shape[0] != n or a.shape[1] < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"HardNegatives: an integer array [{n}, H >= 1] is needed (one row per entry of node_list), got "
+                             f"{a.dtype} {a.shape}")
+        a = a.astype(np.int64)
+        valid = a >= 0
+        if (a < -1).any() or not np.isin(a[valid], np.asarray(sorted(dataset.all_positions), dtype=np.int64)).all():
+            raise ValueError("HardNegatives: an entry is neither -1 nor a member of all_positions")
+        if (valid[:, 1:] & ~valid[:, :-1]).any():
+            raise ValueError("HardNegatives: a valid entry follows a -1 (unused entries sit at the tail only)")
+        cnt = valid.sum(1)
+        for i, q in enumerate(dataset.node_list):
+            row = a[i, :cnt[i]].tolist()
+            if len(set(row)) != len(row):
+                raise ValueError(f"HardNegatives: row {i} (query {q}) holds a duplicate")
+            if not dataset.node2masks[q].isdisjoint(row):
+                raise ValueError(f"HardNegatives: row {i} holds an entry that node2masks[{q}] masks")
+        return cls(torch.from_numpy(a.astype(np.int32)).to(device), torch.from_numpy(cnt.astype(np.int32)).to(device))
+
+
+def _hard_size(size, n_pool):
+    from . import ops
+    if isinstance(size, bool) or int(size) != size or not 1 <= int(size) <= min(ops.SELECT_K_MAX, n_pool):
+        raise ValueError(f"hard negatives: 1 <= size <= min({ops.SELECT_K_MAX}, pool of {n_pool}), got {size!r}")
+    return int(size)
+
+
+def host_hard_table(S, pool, mask_off, mask_idx, size):
+    """numpy restatement of the table mine_hard_negatives selects from a score array S [n_queries, len(pool)] (larger = harder; negate
+    first when smaller is better): scoring.host_select_k's best `size` unmasked columns per row -- best first, equal scores by ascending
+    column, NaN last -- mapped to node ids through `pool`, -1 where fewer exist.  mask_off / mask_idx: the masked COLUMNS per query as a
+    CSR.  Returns (idx int32 [n_queries, size], cnt int32 [n_queries])."""
+    from .scoring import host_select_k
+    pool = np.asarray(pool, dtype=np.int64)
+    size = _hard_size(size, len(pool))
+    sel = host_select_k(S, size, mask_off, mask_idx).astype(np.int64)
+    idx = np.where(sel >= 0, pool[np.maximum(sel, 0)], -1).astype(np.int32)
+    return idx, (sel >= 0).sum(1).astype(np.int32)
+
+
+def _mining_inputs(model, dataset, device, seed=0, batch_size=-1, dtax=None):
+    """what mining scores: dict(hg = the encoded egonets of pool = sorted(all_positions) (evaluate.candidate_graphs on the dataset's
+    device taxonomy, scoring.encode_candidates in eval mode under no_grad; the model's mode is restored), qf = the raw features of
+    node_list in order, pool, and mask_off / mask_idx = node2masks[q] as candidate rows (evaluate._retrieval_masks))"""
+    from .evaluate import _retrieval_masks, candidate_graphs
+    from .scoring import encode_candidates
+    device = torch.device(device)
+    pool = sorted(dataset.all_positions)
+    index = {a: i for i, a in enumerate(pool)}
+    g = candidate_graphs(dtax if dtax is not None else dataset.device_taxonomy(device), pool, dataset.expand_factor, seed, batch_size)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            hg = encode_candidates(model, g)
+    finally:
+        model.train(was_training)
+    qf = dataset.node_features[torch.as_tensor(list(dataset.node_list), dtype=torch.long)].to(device)
+    mask_off, mask_idx = _retrieval_masks(dataset, dataset.node_list, index)
+    return dict(hg=hg, qf=qf, pool=np.asarray(pool, dtype=np.int64), mask_off=mask_off, mask_idx=mask_idx)
+
+
+def mine_hard_negatives(model, dataset, device, size, qblock=None, seed=0, batch_size=-1, larger_is_better=True, dtax=None, timings=None):
+    """The `size` hardest negatives of every training query under `model` as it stands, as a HardNegatives on `device`: per query of
+    node_list the best-scoring nodes of the sampler's pool (sorted(all_positions)) that node2masks[q] does not name, best first (ties by
+    ascending pool position, NaN last), -1 where fewer exist.  The pool's egonets are encoded once (eval mode, no_grad; the model's mode
+    is restored), then score blocks of at most scoring.RETRIEVE_BLOCK_BYTES (qblock: fewer queries per block) -- the prepared matcher's
+    block kernel for BIM / LBM / MLP / NTN, the literal loop for any other matcher (evaluate._score_blocks) -- negated when smaller is
+    better, each followed by one masked ops.select_k.  A [queries x pool] matrix is never held.
+    ValueError unless 1 <= size <= min(ops.SELECT_K_MAX, len(pool)).  seed / batch_size: the candidate egonets' sampling seed and encode
+    chunk, as evaluate().  dtax: the dataset's device taxonomy when the caller holds one (a loader's .dtax; default: made here).
+    timings: a dict that receives the seconds of encode / score / select (the stages are then separated by device synchronises)."""
+    import time
+    from . import ops
+    from .evaluate import _score_blocks
+    from .scoring import RETRIEVE_BLOCK_BYTES
+    _check(dataset)
+    device = torch.device(device)
+    size = _hard_size(size, len(dataset.all_positions))
+    clock = None
+    if timings is not None:
+        def clock(name, t0):
+            torch.cuda.synchronize(device)
+            timings[name] = timings.get(name, 0.0) + time.perf_counter() - t0
+            return time.perf_counter()
+    t0 = time.perf_counter()
+    m = _mining_inputs(model, dataset, device, seed, batch_size, dtax)
+    if clock:
+        t0 = clock("encode", t0)
+    hg, qf = m["hg"], m["qf"]
+    Q, G = int(qf.shape[0]), int(hg.shape[0])
+    sel = torch.full((Q, size), -1, dtype=torch.int32, device=device)
+    moff = midx = None
+    if m["mask_idx"].size:
+        moff = torch.from_numpy(m["mask_off"].astype(np.int32)).to(device)
+        midx = torch.from_numpy(m["mask_idx"].astype(np.int32)).to(device)
+    block = max(1, RETRIEVE_BLOCK_BYTES // (4 * ((G + 3) // 4 * 4)))
+    if qblock is not None:
+        block = max(1, min(block, int(qblock)))
+    was_training = model.training
+    model.eval()                                                   # (the literal loop calls model.match)
+    try:
+        with torch.no_grad():
+            for q0, S in _score_blocks(model, hg, qf, block):
+                S = S.float()
+                if not larger_is_better:
+                    S = -S
+                if clock:
+                    t0 = clock("score", t0)
+                q1 = q0 + S.shape[0]
+                ops.select_k(S, size, None if moff is None else moff[q0:q1 + 1].contiguous(), midx, out=sel[q0:q1])
+                if clock:
+                    t0 = clock("select", t0)
+    finally:
+        model.train(was_training)
+    pool_dev = torch.from_numpy(m["pool"].astype(np.int32)).to(device)
+    idx = torch.where(sel >= 0, pool_dev[sel.clamp_min(0).long()], sel)
+    return HardNegatives(idx, (sel >= 0).sum(1).to(torch.int32))
+
+
 class DeviceAnchorSampler:
     """sampler_arrays(dataset) resident on `device`, with the positive pointers (from node2positive_pointer when made; device sampling
-    does NOT advance the host dict) and a padded-slot counter.  begin() launches the sampler and the egonet node count on one stream."""
+    does NOT advance the host dict) and a padded-slot counter.  begin() launches the sampler and the egonet node count on one stream.
+    set_hard_negatives(table, slots): launch() / begin() then call txe_sample_anchors_hard; without a table they call txe_sample_anchors."""
 
     def __init__(self, dataset, device, seed=0, dtax=None):
         _check(dataset)
@@ -121,16 +301,44 @@ class DeviceAnchorSampler:
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
             return torch.from_numpy(o.astype(np.int32)).to(self.device)
 
+    hard, hard_slots, in_epoch = None, 0, False
+
+    def set_hard_negatives(self, table, slots=0):
+        """from the next launch on, the first `slots` negative slots of a query come from `table` (a HardNegatives on this device; None:
+        the pool alone again).  ValueError: slots outside [0, k], a table with another row count than node_list, or one on another
+        device.  RuntimeError while a loader iterates an epoch over this sampler (its batches in flight read the table on a side
+        stream).  The device is synchronised once: the table, written on the caller's stream, is complete before a side stream reads
+        it, and no launch in flight still reads the table it replaces."""
+        if self.in_epoch:
+            raise RuntimeError("set_hard_negatives while an epoch is being iterated: it takes effect between epochs only")
+        if isinstance(slots, bool) or int(slots) != slots or not 0 <= int(slots) <= self.k:
+            raise ValueError(f"hard slots must be in [0, negative_size = {self.k}], got {slots!r}")
+        if table is not None:
+            if not isinstance(table, HardNegatives):
+                raise ValueError(f"set_hard_negatives takes a sampler.HardNegatives or None, got {type(table).__name__}")
+            if table.n_queries != self.n_queries:
+                raise ValueError(f"the table holds {table.n_queries} rows, the dataset's node_list {self.n_queries} queries")
+            if table.device != self.device:
+                raise ValueError(f"the table lives on {table.device}, the sampler on {self.device}")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self.hard, self.hard_slots = table, int(slots) if table is not None else 0
+
     def launch(self, order_dev, start, Q, epoch, repeated_queries=True, stream=None):
-        """txe_sample_anchors alone: the packed [4B + 1] int32 index arrays of the batch, written on `stream` (default: current)"""
+        """txe_sample_anchors (with a table set: txe_sample_anchors_hard) alone: the packed [4B + 1] int32 index arrays of the batch,
+        written on `stream` (default: current)"""
         a = self.arrays
         B = Q * (1 + self.k)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)), _lib.on_device(self.device):
             packed = torch.empty(4 * B + 1, dtype=torch.int32, device=self.device)
-            _lib.call("txe_sample_anchors", _lib.ptr(order_dev), int(order_dev.numel()), int(start), int(Q), _lib.ptr(a["node_list"]),
-                      _lib.ptr(a["par_ptr"]), _lib.ptr(a["par_idx"]), _lib.ptr(a["mask_ptr"]), _lib.ptr(a["mask_idx"]), _lib.ptr(a["pool"]),
-                      self.n_pool, _lib.ptr(a["ptr"]), self.k, self.seed, int(epoch), int(bool(repeated_queries)), _lib.ptr(packed),
-                      _lib.ptr(self._padded), _lib.stream_ptr())
+            args = (_lib.ptr(order_dev), int(order_dev.numel()), int(start), int(Q), _lib.ptr(a["node_list"]), _lib.ptr(a["par_ptr"]),
+                    _lib.ptr(a["par_idx"]), _lib.ptr(a["mask_ptr"]), _lib.ptr(a["mask_idx"]), _lib.ptr(a["pool"]), self.n_pool,
+                    _lib.ptr(a["ptr"]), self.k, self.seed, int(epoch), int(bool(repeated_queries)), _lib.ptr(packed), _lib.ptr(self._padded))
+            if self.hard is None:
+                _lib.call("txe_sample_anchors", *args, _lib.stream_ptr())
+            else:
+                _lib.call("txe_sample_anchors_hard", *args, _lib.ptr(self.hard.idx), _lib.ptr(self.hard.cnt), self.hard.H, self.hard_slots,
+                          _lib.stream_ptr())
         return packed
 
     def begin(self, order_dev, start, Q, epoch, repeated_queries=True, stream=None, egonet_seed=0):

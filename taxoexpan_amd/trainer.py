@@ -247,9 +247,37 @@ def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, sa
         torch.save(state, os.path.join(str(save_dir), "model_best.pth"))
 
 
+def _checked_hard_negatives(cfg, train_loader):
+    """fit's hard_negatives option as dict(size, slots, every, start), or None; ValueError for anything fit cannot run"""
+    if cfg is None:
+        return None
+    from .sampler import DeviceAnchorSampler, _hard_size
+    if not isinstance(cfg, dict) or not {"size", "slots"} <= set(cfg) or not set(cfg) <= {"size", "slots", "every", "start"}:
+        raise ValueError(f"hard_negatives is None or dict(size=, slots=, every=1, start=1), got {cfg!r}")
+    if not (isinstance(getattr(train_loader, "sampler", None), DeviceAnchorSampler) and hasattr(train_loader, "set_hard_negatives")):
+        raise ValueError("hard_negatives needs a DeviceBatchLoader(sampler='device') over a sampling_mode 1 dataset (the host sampler and "
+                         "the sampling_mode 0 group sampler draw from the pool only)")
+    out = dict(every=1, start=1)
+    out.update(cfg)
+    for name, v in out.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"hard_negatives[{name!r}] must be an integer, got {v!r}")
+        out[name] = int(v)
+    k = train_loader.sampler.k
+    if not 0 <= out["slots"] <= k:
+        raise ValueError(f"hard_negatives: slots must be in [0, negative_size = {k}], got {out['slots']}")
+    out["size"] = _hard_size(out["size"], train_loader.sampler.n_pool)
+    if out["size"] < out["slots"]:
+        raise ValueError(f"hard_negatives: size {out['size']} is below slots {out['slots']}")
+    if out["every"] < 1 or out["start"] < 1:
+        raise ValueError(f"hard_negatives: every and start are at least 1, got {out['every']} and {out['start']}")
+    return out
+
+
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
-        loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False):
+        loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False,
+        hard_negatives=None):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -273,7 +301,16 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     completed before the diverged one, so that `resume=` starts the diverged epoch again.
     loss_fn / group_size go to train_epoch (the device losses of taxoexpan_amd.loss -- info_nce, bce, square_exp, margin_rank -- keep an
     epoch free of read-backs; see there).  train_epoch_fn / validate_fn replace trainer.train_epoch / evaluate.validate (same call
-    signatures); the loop control here makes no GPU call of its own.  Returns the list of per-epoch logs."""
+    signatures); the loop control here makes no GPU call of its own.  Returns the list of per-epoch logs.
+    hard_negatives: None (uniform negatives, as ever) or dict(size=H, slots=m, every=1, start=1): before every epoch e >= start with
+    (e - start) % every == 0, sampler.mine_hard_negatives(model, train_loader.dataset, size=H, larger_is_better=larger_is_better) ranks
+    the pool for every training query under the model as it stands, and train_loader.set_hard_negatives(table, m) makes the first m
+    negative slots of every query draw from its H best (DeviceBatchLoader(sampler="device"), sampling_mode 1); before `start` the
+    loader draws uniformly, between mining epochs it keeps the last table.  Checked before the first step (ValueError): the loader kind,
+    0 <= slots <= negative_size, 1 <= size, size >= slots, every >= 1, start >= 1, no other key.  The table is not checkpointed: a
+    resumed run mines at its first qualifying epoch.  The log of an epoch that mined gains hard_mined = True and hard_mean_count = the
+    mean of the table's cnt; no other key changes."""
+    hard = _checked_hard_negatives(hard_negatives, train_loader)
     if train_epoch_fn is None:
         train_epoch_fn = train_epoch
     if validate_fn is None:
@@ -308,9 +345,18 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     if freeze_on_nonfinite:
         guard_args["freeze_on_nonfinite"] = True
     for epoch in range(start_epoch, epochs + 1):
+        mined = None
+        if hard is not None and epoch >= hard["start"] and (epoch - hard["start"]) % hard["every"] == 0:
+            from .sampler import mine_hard_negatives
+            table = mine_hard_negatives(model, train_loader.dataset, train_loader.device, hard["size"], larger_is_better=larger_is_better,
+                                        dtax=getattr(train_loader, "dtax", None))
+            train_loader.set_hard_negatives(table, hard["slots"])
+            mined = {"hard_mined": True, "hard_mean_count": float(table.cnt.double().mean().item())}
         result = train_epoch_fn(model, train_loader, optimizer, loss_fn=loss_fn, group_size=group_size, **guard_args)
         log = {"epoch": epoch}
         log.update(result)
+        if mined is not None:
+            log.update(mined)
         logs.append(log)
         if result.get("first_nonfinite", -1) >= 0:
             checkpoint = None
