@@ -213,6 +213,21 @@ int txe_readout_multi_fwd(const int* graph_off, int G, const float* h, long long
 int txe_readout_multi_bwd(const int* graph_off, int G, const int* pos, int D, int mode, const float* d_hg, const int* argmax,
                           float* d_h, long long ld_dh, void* stream);
 
+/* AttentionReadout: global attention pooling with a position-aware gate (beyond the reference: its model_zoo.py stops at
+ * "TODO: try GlobalAttentionPooling").  Y [N][A] = gate_hidden(h) from txe_linear_fwd, P [vocab][A], u [A]:
+ *   s_v = sum_j u_j tanh(Y[v][j] + P[pos_v][j]);  alpha = softmax of s over the egonet (shifted by its maximum);
+ *   hg[g] = sum_v alpha_v h[v].   alpha [N] is written once by the forward and read by the backward; an empty egonet gives a zero row.
+ * The backward writes d_h = alpha_v d_hg[g] (the term through Y is txe_linear_bwd's), d_Y [N][A], d_P [vocab][A], d_u [A]; it is
+ * atomic free: ws (txe_readout_attn_bwd_ws_bytes) holds one [vocab + 1][A] block of column sums per egonet, reduced in a fixed order
+ * by a second launch.  vocab <= 8.  G == 0: TXE_OK, nothing launched, nothing written. */
+int txe_readout_attn_fwd(const int* graph_off, int G, const float* h, long long ld_h, int D, const float* Y, long long ld_y, int A,
+                         const int* pos, const float* P, int vocab, const float* u, float* hg, float* alpha, void* stream);
+size_t txe_readout_attn_bwd_ws_bytes(int G, int A, int vocab);
+int txe_readout_attn_bwd(const int* graph_off, int G, const float* h, long long ld_h, int D, const float* Y, long long ld_y, int A,
+                         const int* pos, const float* P, int vocab, const float* u, const float* hg, const float* alpha,
+                         const float* d_hg, long long ld_dhg, float* d_h, long long ld_dh, float* d_Y, long long ld_dy, float* d_P,
+                         float* d_u, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- matchers: BIM model_zoo.py:313, LBM :328 (apply_exp) ------------------------------------------------------- */
 int txe_bilinear_project(const float* e1, long long ld_e1, int G, int l, const float* W, int r, float* U, long long ld_u,
                          void* sws, size_t sws_bytes, void* stream);   /* sws: NULL, or txe_gemm_plain_split_ws_bytes(G, r, l) of scratch:

@@ -29,8 +29,11 @@ def _gat_like(cls, positional):
 
 PROPAGATION = {"GCN": _gcn_like(zoo.GCN, False), "PGCN": _gcn_like(zoo.PGCN, True),
                "GAT": _gat_like(zoo.GAT, False), "PGAT": _gat_like(zoo.PGAT, True)}
-# readout -> (module class, how many copies of out_dim the graph vector holds)
-READOUT = {"MR": (zoo.MeanReadout, 1), "WMR": (zoo.WeightedMeanReadout, 1), "CR": (zoo.ConcatReadout, 3)}
+# readout -> (factory over the options, how many copies of out_dim the graph vector holds).  "AR" (attention pooling with a
+# position-aware gate; optional `attention_dim`, 100 if missing) is this package's own: the reference has no such readout.
+READOUT = {"MR": (lambda o: zoo.MeanReadout(), 1), "WMR": (lambda o: zoo.WeightedMeanReadout(), 1),
+           "CR": (lambda o: zoo.ConcatReadout(), 3),
+           "AR": (lambda o: zoo.AttentionReadout(o["out_dim"], attention_dim=o.get("attention_dim", 100)), 1)}
 MATCH = {"MLP": lambda l, r, o: zoo.MLP(l, r, o["hidden_dim"]), "LBM": lambda l, r, o: zoo.LBM(l, r),
          "BIM": lambda l, r, o: zoo.BIM(l, r)}
 
@@ -43,8 +46,8 @@ class TaxoExpan(torch.nn.Module):
         if propagation_method in PROPAGATION:
             self.graph_propagate = PROPAGATION[propagation_method](options)
         if readout_method in READOUT:
-            cls, copies = READOUT[readout_method]
-            self.readout = cls()
+            make, copies = READOUT[readout_method]
+            self.readout = make(options)
             dims = (options["out_dim"] * copies, options["in_dim"])        # (graph side, query side) of the matcher
             if matching_method in MATCH:
                 self.match = MATCH[matching_method](dims[0], dims[1], options)

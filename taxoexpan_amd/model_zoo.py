@@ -9,6 +9,7 @@ libtxe (include/txe.h) instead of DGL + torch.
     GAT/PGAT   model_zoo.py:169-220      GAT/PGAT   -> one fused GATStackFunction over all layers
     MeanReadout/WeightedMeanReadout      model_zoo.py:227-242 -> txe_readout_*
     ConcatReadout/SumReadout/MaxReadout  model_zoo.py:244-276 -> txe_readout_multi_*
+    (none: "TODO: try GlobalAttentionPooling", :225)          AttentionReadout -> txe_linear_* + txe_readout_attn_*
     MLP        model_zoo.py:281-298      MLP        -> txe_linear_*  
     NTN        model_zoo.py:331-346      NTN        -> k x txe_bilinear_pair_* + txe_linear_*  (+ score_all / txe_ntn_* for the eval loop;
                                                        not reachable from model/model.py)
@@ -18,6 +19,7 @@ Side effects the callers rely on are kept: PGAT/PGCN pop g.ndata['pos'] (model_z
 writes g.ndata['a'] (:241).
 """
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -512,6 +514,46 @@ class MaxReadout(nn.Module):
         """model_zoo.py:274-276"""
         h = _node_features(g)
         return ops.ReadoutMultiFunction.apply(g.csr(h.device), h, None, 2)
+
+
+class AttentionReadout(nn.Module):
+    """Global attention pooling (DGL's GlobalAttentionPooling) with a position-aware gate -- NOT in the reference: its readout section
+    opens with "TODO: try GlobalAttentionPooling", and four of its configs name a `PGAT_PATR_*` architecture with `attention_dim: 100`
+    whose class was never published.  This is not a reconstruction of that class.
+        s_v = gate_out(tanh(gate_hidden(h_v) + gate_position[pos_v]));  alpha = softmax of s over the egonet;  hg = sum_v alpha_v h_v
+    The weights depend on h, so the output layer cannot be folded behind this readout: it takes the route of Concat / Sum / MaxReadout
+    (node features materialised, a plain [G, in_dim] tensor out).  g.ndata['a'] receives alpha [N], where WeightedMeanReadout leaves its
+    weights."""
+
+    def __init__(self, in_dim, attention_dim=100, position_vocab_size=3):
+        super(AttentionReadout, self).__init__()
+        self.gate_hidden = nn.Linear(in_dim, attention_dim)
+        self.gate_position = nn.Embedding(position_vocab_size, attention_dim)
+        self.gate_out = nn.Linear(attention_dim, 1, bias=False)         # (a bias would cancel in the softmax)
+
+    def forward(self, g, pos):
+        h = _node_features(g)
+        Y = ops.LinearFunction.apply(h, None, self.gate_hidden.weight, self.gate_hidden.bias, 0)
+        hg, alpha = ops.ReadoutAttnFunction.apply(g.csr(h.device), h, Y, pos, self.gate_position.weight, self.gate_out.weight)
+        g.ndata['a'] = alpha
+        return hg
+
+
+def host_attention_readout(params, graph_off, h, pos, dtype=np.float64):
+    """numpy restatement of AttentionReadout: params = {'gate_hidden.weight' [A, D], 'gate_hidden.bias' [A], 'gate_position.weight'
+    [vocab, A], 'gate_out.weight' [1, A]} -> (hg [G, D], alpha [N]) in `dtype`"""
+    W, b, P, u = (np.asarray(params[k], dtype=dtype) for k in ("gate_hidden.weight", "gate_hidden.bias", "gate_position.weight",
+                                                               "gate_out.weight"))
+    h, pos, graph_off = np.asarray(h, dtype=dtype), np.asarray(pos).astype(np.int64), np.asarray(graph_off).astype(np.int64)
+    s = np.tanh(h @ W.T + b + P[pos]) @ u.reshape(-1)
+    alpha, hg = np.zeros(h.shape[0], dtype=dtype), np.zeros((len(graph_off) - 1, h.shape[1]), dtype=dtype)
+    for g in range(len(graph_off) - 1):
+        beg, end = graph_off[g], graph_off[g + 1]
+        if end > beg:
+            e = np.exp(s[beg:end] - s[beg:end].max())
+            alpha[beg:end] = e / e.sum()
+            hg[g] = alpha[beg:end] @ h[beg:end]
+    return hg, alpha
 
 
 class _LazyPositionWeight:

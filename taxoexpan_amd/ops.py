@@ -1206,6 +1206,51 @@ class ReadoutMultiFunction(torch.autograd.Function):
         return None, d_h, None, None
 
 
+class ReadoutAttnFunction(torch.autograd.Function):
+    """AttentionReadout (model_zoo.AttentionReadout): hg[g] = sum_v alpha_v h[v], alpha = softmax over the egonet of
+    s_v = <u, tanh(Y[v] + P[pos_v])>, with Y = gate_hidden(h) handed in by the caller (a LinearFunction, whose own backward carries d_Y on
+    to h and the gate's weights).  Returns (hg [G, D], alpha [N]); alpha is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, csr, h, Y, pos, P, u):
+        _need_cuda(h, Y, P, u)
+        h, ld_h = _rows(h)
+        Y, ld_y = _rows(Y)
+        G, N, D, A = csr.n_graphs, h.shape[0], h.shape[1], Y.shape[1]
+        Pf, uf = _f32(P), _f32(u.reshape(-1))
+        if Y.shape[0] != N or tuple(Pf.shape[1:]) != (A,) or uf.numel() != A:
+            raise ValueError("ReadoutAttnFunction: h [N, D], Y [N, A], P [vocab, A] and u [A] do not fit together")
+        pos = _i32(pos, h.device)
+        if G == 0 or N == 0:                                # nothing to launch (an empty tensor has no address to hand over)
+            hg, alpha = h.new_zeros((G, D)), _empty((N,), h)
+        else:
+            hg, alpha = _empty((G, D), h), _empty((N,), h)
+            with _lib.on_device(h.device):
+                call("txe_readout_attn_fwd", ptr(csr.graph_off), G, ptr(h), ld_h, D, ptr(Y), ld_y, A, ptr(pos), ptr(Pf), Pf.shape[0],
+                     ptr(uf), ptr(hg), ptr(alpha), _lib.stream_ptr())
+        ctx.csr, ctx.pos, ctx.misc = csr, pos, (h, ld_h, Y, ld_y, Pf, uf, hg, alpha)
+        ctx.u_shape = u.shape
+        ctx.mark_non_differentiable(alpha)
+        return hg, alpha
+
+    @staticmethod
+    def backward(ctx, d_hg, _d_alpha):
+        csr, pos = ctx.csr, ctx.pos
+        h, ld_h, Y, ld_y, Pf, uf, hg, alpha = ctx.misc
+        G, (N, D), A, vocab = csr.n_graphs, h.shape, Y.shape[1], Pf.shape[0]
+        d_hg, ld_dhg = _rows(d_hg)
+        d_h, d_Y = _empty((N, D), h), _empty((N, A), h)
+        if G == 0 or N == 0:                                # nothing is launched: the parameters' gradients are zero
+            return None, d_h, d_Y, None, torch.zeros_like(Pf), torch.zeros_like(uf).reshape(ctx.u_shape)
+        d_P, d_u = torch.empty_like(Pf), torch.empty_like(uf)
+        with _lib.on_device(h.device):
+            wsb = pure("txe_readout_attn_bwd_ws_bytes", G, A, vocab)
+            ws = _ws(wsb, h)
+            call("txe_readout_attn_bwd", ptr(csr.graph_off), G, ptr(h), ld_h, D, ptr(Y), ld_y, A, ptr(pos), ptr(Pf), vocab, ptr(uf),
+                 ptr(hg), ptr(alpha), ptr(d_hg), ld_dhg, ptr(d_h), D, ptr(d_Y), A, ptr(d_P), ptr(d_u), ptr(ws), wsb, _lib.stream_ptr())
+        return None, d_h, d_Y, None, d_P, d_u.reshape(ctx.u_shape)
+
+
 class LinearFunction(torch.autograd.Function):
     """y = act([x1 | x2] W^T + b): nn.Linear over a virtual concat (the MLP matcher, model_zoo.py:285-298); act 0/1 relu/2 tanh"""
 
