@@ -174,4 +174,46 @@ struct ProfScope {
     }
 };
 
+// ---- one driver per reducing mode of the all-candidate loop (host side) ------------------------------------------------------------
+// Best-k and log-partition have one shape whatever the matcher family: the family's score pass, given as a callable that enqueues it
+// and returns its status, between the launches every family shares.  tiles = the pass's column tiles (the lists' / pairs' middle
+// dimension).  The entry points validate, build their operands and name their ProfScopes; nothing here is launched before they have.
+int topk_floor_init(int* floor_ws, int nq, hipStream_t s);       // txe_rank.hip: every row's floor = -inf; records no ProfScope
+struct TopkLists {             // a best-k entry point's scratch and outputs (txe.h: txe_score_topk_block)
+    float* part_key; int* part_idx; int* floor_ws; int* out_idx; float* out_key; int idx_base;
+};
+// k <= TOPK_MAX: floors, one pass, the merge
+template <class Pass>
+static inline int topk_one_pass(int nq, long long tiles, int k, const TopkLists& t, hipStream_t s, Pass pass) {
+    int rc = topk_floor_init(t.floor_ws, nq, s);
+    if (rc) return rc;
+    rc = pass();
+    if (rc) return rc;
+    return txe_topk_merge(t.part_key, t.part_idx, nq, tiles * k, k, t.idx_base, t.out_idx, t.out_key, s);
+}
+// k <= TOPK_WIDE_MAX: the rounds of 8 under a ceiling (above); launch_round(kr, ceil_key, ceil_idx) is one pass keeping kr entries per
+// tile row under the ceilings (NULL in the first round); ceil_ws: [nq] float keys, then [nq] int columns
+template <class Pass>
+static inline int topk_rounds(int nq, long long tiles, int k, const TopkLists& t, void* ceil_ws, hipStream_t s, Pass launch_round) {
+    float* ck = reinterpret_cast<float*>(ceil_ws);
+    int* ci = reinterpret_cast<int*>(ck + nq);
+    for (int k0 = 0; k0 < k; k0 += TOPK_MAX) {
+        const int kr = (k - k0 < TOPK_MAX) ? k - k0 : TOPK_MAX;
+        int rc = topk_floor_init(t.floor_ws, nq, s);
+        if (rc) return rc;
+        rc = launch_round(kr, k0 ? ck : nullptr, k0 ? ci : nullptr);
+        if (rc) return rc;
+        rc = topk_merge_round(t.part_key, t.part_idx, nq, tiles * kr, kr, t.idx_base, t.out_idx + k0, t.out_key ? t.out_key + k0 : nullptr, k,
+                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
+        if (rc) return rc;
+    }
+    return TXE_OK;
+}
+// log-partition: one pass leaving the tiles' (max, sum) pairs, the merge
+template <class Pass>
+static inline int lse_one_pass(int nq, long long tiles, float* part_max, float* part_sum, float* lse, hipStream_t s, Pass pass) {
+    const int rc = pass();
+    return rc ? rc : txe_lse_merge(part_max, part_sum, nq, tiles, lse, s);
+}
+
 }  // namespace txe

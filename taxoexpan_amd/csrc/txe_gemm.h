@@ -69,6 +69,16 @@ static inline void vmat_set_mask(VMat& m, const unsigned* mask, float drop_p) {
 //   n >= cols_main : c2[m*ldc2 + n - cols_main]
 // value = acc (* (mask bit(m, n+mask_col0) ? drop_scale : 0)) (* leaky'(act_src[m][n]) for n<cols_main) (exp() if apply_exp).
 // Split-K: block z writes at c + z*split_stride (no extras expected).
+// Epi::cnt_mode by name (the field stays an int; the modes are described at the field)
+enum EpiMode : int {
+    EPI_STORE = 0,                              // store the tile
+    EPI_COUNT_GT = 1, EPI_COUNT_LT = 2,         // count mode: larger / smaller is better
+    EPI_PICK = 3,                               // pick mode
+    EPI_TOPK_MAX = 4, EPI_TOPK_MIN = 5,         // top-k mode: larger / smaller is better
+    EPI_LSE_MAX = 6, EPI_LSE_MIN = 7            // lse mode: larger / smaller is better
+};
+// (for the launchers, which pick the lse mode's own instantiations by it; the kernels compare the field with the names in place)
+static inline bool epi_is_lse(int mode) { return mode == EPI_LSE_MAX || mode == EPI_LSE_MIN; }
 struct Epi {
     float* c;
     long long ldc;
@@ -87,13 +97,13 @@ struct Epi {
     int apply_exp;
     long long split_stride;
     // count mode (fused ranking of the scoring loop): nothing is stored; for row m and each p in [cnt_off[m], cnt_off[m+1]):
-    //   cnt_out[p] += #{ n < N : value(m, n) > cnt_thr[p] }  (cnt_mode 1)  /  < cnt_thr[p]  (cnt_mode 2)    -- int32 atomics, exact
-    // pick mode (cnt_mode 3; the thresholds of that ranking): column n belongs to the row m with cnt_off[m] <= n < cnt_off[m+1] (the
+    //   cnt_out[p] += #{ n < N : value(m, n) > cnt_thr[p] }  (EPI_COUNT_GT)  /  < cnt_thr[p]  (EPI_COUNT_LT)    -- int32 atomics, exact
+    // pick mode (EPI_PICK; the thresholds of that ranking): column n belongs to the row m with cnt_off[m] <= n < cnt_off[m+1] (the
     //   columns are the gathered true parents of the rows' queries, query by query); only c[n] = value(m, n) of those pairs is stored
     //   and tiles that hold none of them return at once -- a staircase of ~(rows/128 + columns/BN) tiles instead of the whole product
-    // top-k mode (cnt_mode 4: larger is better, 5: smaller is better; the scoring loop's "best k parents", infer.py:100-106): nothing of
+    // top-k mode (EPI_TOPK_MAX: larger is better, EPI_TOPK_MIN: smaller is better; the scoring loop's "best k parents", infer.py:100-106): nothing of
     //   the product is stored; every tile leaves, per row, its topk_k best columns in the order Python's stable sorted() gives them
-    //   (better value first, equal values by ascending column; NaN ranks last) as keys (value, negated in mode 5) + column numbers at
+    //   (better value first, equal values by ascending column; NaN ranks last) as keys (value, negated in EPI_TOPK_MIN) + column numbers at
     //   topk_key / topk_idx [M][column tiles][topk_k]; a merge kernel (txe_topk_merge) picks each row's best k among the tiles' lists
     int cnt_mode;
     int topk_k;
@@ -101,7 +111,7 @@ struct Epi {
     union { int* topk_idx; float* lse_s; };
     int* topk_floor;           // [M] ordered-int keys (topk_ord): a lower bound of each row's final k-th best key, raised by every tile
     int force_bn128;           // 1: 128-wide column tiles whatever the shape (the top-k and lse scratch is laid out by them)
-    // lse mode (cnt_mode 6: larger is better, z = value; 7: smaller is better, z = -value; the scoring loop's log-partition, the exact
+    // lse mode (EPI_LSE_MAX: larger is better, z = value; EPI_LSE_MIN: smaller is better, z = -value; the scoring loop's log-partition, the exact
     //   form of loss.py:52-57 over test_fast.py:121-123): nothing of the product is stored; every tile leaves, per row, the pair
     //   (max z, sum exp(z - max)) over its columns < N at lse_m / lse_s [M][column tiles] (txe_common.h: lse_max / lse_term name the
     //   special values); a merge kernel (txe_lse_merge) combines a row's pairs in tile order
@@ -133,7 +143,7 @@ static inline Epi epi_plain(float* c, long long ldc, int cols) {
     e.act_src = c; e.ld_act = 0; e.act_slope = 1.f; e.act_on = 0;
     e.mask = reinterpret_cast<const unsigned*>(c); e.mask_ld = 0; e.mask_col0 = 0; e.mask_on = 0; e.drop_scale = 1.f;
     e.apply_exp = 0; e.split_stride = 0;
-    e.cnt_mode = 0; e.cnt_off = nullptr; e.cnt_thr = nullptr; e.cnt_out = nullptr;
+    e.cnt_mode = EPI_STORE; e.cnt_off = nullptr; e.cnt_thr = nullptr; e.cnt_out = nullptr;
     e.topk_k = 0; e.topk_key = nullptr; e.topk_idx = nullptr; e.topk_floor = nullptr; e.force_bn128 = 0;
     e.alg_flops = 0.0; e.route = 0; e.k_valid = 0;
     e.plain_k_order = 0;
@@ -469,7 +479,7 @@ __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(const Epi E, const
 // for the count mode) -- plain / exp / mask / activation stores, the pick, count and best-k modes.  Shared by gemm_kernel and the
 // bf16-pipe product of txe_gemm_split.hip (the scoring loop's four entry points must produce bit-identical scores: ONE epilogue).
 // cnt_pb / cnt_np / cnt_th: the count mode's per-row positive range and first thresholds, fetched by the caller before its k-loop.
-// LSE: the lse mode (cnt_mode 6 / 7) and nothing else -- its own instantiation of every kernel that ends here, so that the code of the
+// LSE: the lse mode (EPI_LSE_MAX / EPI_LSE_MIN) and nothing else -- its own instantiation of every kernel that ends here, so that the code of the
 // other modes (the training GEMMs among them) is what it was without it.
 template <int BN, int SMEM, bool LSE = false>
 __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, const int m0, const int n0, const int M, const int N, const int tn,
@@ -477,7 +487,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
     constexpr int CLD = BN + 4;
     constexpr int C4 = BN / 4;                       // 16-byte chunks per tile row
     float* Cs = smem;
-    if (E.cnt_mode == 3) {                           // pick mode: store the rows' own columns only
+    if (E.cnt_mode == EPI_PICK) {                    // pick mode: store the rows' own columns only
         for (int idx = threadIdx.x; idx < GEMM_BM * C4; idx += GEMM_THREADS) {
             const int row = idx / C4, c4 = idx % C4;
             const int m = m0 + row, mc = min(m, M - 1);
@@ -492,14 +502,14 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
         }
         return;
     }
-    if (E.cnt_mode == 4 || E.cnt_mode == 5) {
+    if (E.cnt_mode == EPI_TOPK_MAX || E.cnt_mode == EPI_TOPK_MIN) {
         // best-k columns of every row of this tile: two threads per row, each scans its half row (ascending columns) into a best-k list,
         // the pair merges, the even thread writes the row's topk_k entries of this column tile
         static_assert(GEMM_THREADS == 2 * GEMM_BM, "two threads per tile row");
         constexpr int HW = BN / 2;
         const int row = threadIdx.x >> 1, half = threadIdx.x & 1;
         const int m = m0 + row, nb = n0 + half * HW;
-        const bool larger = E.cnt_mode == 4;
+        const bool larger = E.cnt_mode == EPI_TOPK_MAX;
         float bk[TOPK_MAX];
         int bi[TOPK_MAX];
         topk_init(bk, bi);
@@ -573,7 +583,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
         constexpr int HW = BN / 2;
         const int row = threadIdx.x >> 1, half = threadIdx.x & 1;
         const int m = m0 + row, nb = n0 + half * HW;
-        const bool larger = E.cnt_mode == 6;
+        const bool larger = E.cnt_mode == EPI_LSE_MAX;
         const float* src = Cs + row * CLD + half * HW;
         float mx = -INFINITY;
         bool bad = false;
@@ -612,7 +622,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
         }
         return;
     }
-    if (E.cnt_mode != 0) {
+    if (E.cnt_mode != EPI_STORE) {
         // fused ranking: every thread owns 4 consecutive columns of a row; the C4 lanes of a row reduce their counts by butterfly.
         // The rows' positive ranges and (up to PS) thresholds are staged once per tile in the LDS left over behind the C tile.
         constexpr int FREE = SMEM - GEMM_BM * CLD;
@@ -642,7 +652,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
                 v[4 * j] = t4.x; v[4 * j + 1] = t4.y; v[4 * j + 2] = t4.z; v[4 * j + 3] = t4.w;
             }
             // columns past N never count: push them to the losing side of every comparison
-            const float lose = (E.cnt_mode == 1) ? -INFINITY : INFINITY;
+            const float lose = (E.cnt_mode == EPI_COUNT_GT) ? -INFINITY : INFINITY;
 #pragma unroll
             for (int i = 0; i < HW; ++i) {
                 const float x = E.apply_exp ? __expf(v[i]) : v[i];
@@ -654,7 +664,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
             for (int k = 0; k < np; ++k) {                       // the two threads of a row share the trip count
                 const float th = (k < PS) ? s_thr[row * PS + k] : E.cnt_thr[pb + k];
                 int c = 0;
-                if (E.cnt_mode == 1) {
+                if (E.cnt_mode == EPI_COUNT_GT) {
 #pragma unroll
                     for (int i = 0; i < HW; ++i) c += (v[i] > th) ? 1 : 0;
                 } else {
@@ -789,13 +799,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(VMat A, VMat B, c
 
     // count mode: this tile's rows' positive ranges and first thresholds are fetched NOW (two dependent loads), so that their
     // latency hides under the whole k-loop instead of sitting in the epilogue
-    if (E.cnt_mode == 3) {                           // pick mode: a tile without a (row, own column) pair has nothing to do (block-uniform)
+    if (E.cnt_mode == EPI_PICK) {                    // pick mode: a tile without a (row, own column) pair has nothing to do (block-uniform)
         const int lo = E.cnt_off[m0], hi = E.cnt_off[min(m0 + GEMM_BM, M)];
         if (n0 >= hi || n0 + BN <= lo) return;
     }
     int cnt_pb = 0, cnt_np = 0;
     float cnt_th[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if ((E.cnt_mode == 1 || E.cnt_mode == 2) && threadIdx.x < GEMM_BM && m0 + (int)threadIdx.x < M) {
+    if ((E.cnt_mode == EPI_COUNT_GT || E.cnt_mode == EPI_COUNT_LT) && threadIdx.x < GEMM_BM && m0 + (int)threadIdx.x < M) {
         cnt_pb = E.cnt_off[m0 + threadIdx.x];
         cnt_np = E.cnt_off[m0 + threadIdx.x + 1] - cnt_pb;
 #pragma unroll
@@ -1224,7 +1234,7 @@ static inline void gemm_launch_v(int bn, dim3 grid, hipStream_t stream, const VM
     }
     name = names[bn == 128 ? 0 : (bn == 64 ? 1 : 2)];
     if constexpr (AK && BKC) {                       // (the lse mode: NT products on 128-wide tiles -- gemm_launch_layout refuses any other)
-        if (E.cnt_mode == 6 || E.cnt_mode == 7) {
+        if (epi_is_lse(E.cnt_mode)) {
             static char lse_name[48];
             if (!lse_name[0]) snprintf(lse_name, sizeof(lse_name), "gemm_kernel<true, true, %d, %d, %d>", VA, VB, GEMM_BN_LSE);
             ProfScope prof(lse_name, stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
@@ -1260,7 +1270,7 @@ static inline int gemm_launch_layout(const VMat& A, const VMat& B, const Epi& E_
                                      hipStream_t stream, void* tail_ws = nullptr, size_t tail_ws_bytes = 0) {
     if (M <= 0 || N <= 0) return TXE_OK;
     // the lse mode exists for NT products on 128-wide tiles only (gemm_launch_v); no other instance has its epilogue
-    if ((E_in.cnt_mode == 6 || E_in.cnt_mode == 7) && !(AK && BKC && E_in.force_bn128 && splits <= 1)) return TXE_ERR_ARG;
+    if (epi_is_lse(E_in.cnt_mode) && !(AK && BKC && E_in.force_bn128 && splits <= 1)) return TXE_ERR_ARG;
     Epi E = E_in;
     {   // the epilogue loads its extras unconditionally: give the unused ones a readable dummy address
         const void* valid = E.c ? (const void*)E.c : (const void*)E.c2;
@@ -1270,14 +1280,14 @@ static inline int gemm_launch_layout(const VMat& A, const VMat& B, const Epi& E_
     int va = vmat_vec(A), vb = vmat_vec(B);
     if (va == 1 || vb == 1) va = vb = 1;
     if (splits < 1) splits = 1;
-    const bool allow160 = !BKC && va == 4 && vb == 4 && !E.mask_on && !E.act_on && E.cnt_mode == 0 &&
+    const bool allow160 = !BKC && va == 4 && vb == 4 && !E.mask_on && !E.act_on && E.cnt_mode == EPI_STORE &&
                           (E.c2 == nullptr || E.cols_main >= N);
     const bool tail_split = tail_ws != nullptr && !E.plain_k_order;
     int bn = E.force_bn128 ? 128 : choose_bn(M, N, splits, tail_split, K, allow160, (E.route & GEMM_ROUTE_FORCE_BN160) != 0);
     int tile0 = 0;
     // whole rounds of 128 x 128 tiles of a plain product with a short reduction: persistent workgroups (gemm_persist_kernel)
     if (splits == 1 && tail_ws != nullptr && va == 4 && vb == 4 && N > 64 && !(E.route & GEMM_ROUTE_NO_PERSIST) && !E.mask_on && !E.act_on &&
-        E.cnt_mode == 0 && (E.c2 == nullptr || E.cols_main >= N) && (K % GEMM_BK) == 0 && K >= 5 * GEMM_BK && K <= TXE_PERSIST_MAXK &&
+        E.cnt_mode == EPI_STORE && (E.c2 == nullptr || E.cols_main >= N) && (K % GEMM_BK) == 0 && K >= 5 * GEMM_BK && K <= TXE_PERSIST_MAXK &&
         A.p2 == nullptr && B.p2 == nullptr && A.cols_main == A.cols && B.cols_main == B.cols && A.rows_main >= A.rows && B.rows_main >= B.rows &&
         (AK ? A.cols : A.rows) >= K && (BKC ? B.cols : B.rows) >= K) {
         const int slots = 2 * device_cu_count();

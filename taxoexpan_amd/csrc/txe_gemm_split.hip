@@ -192,11 +192,11 @@ __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGem
     float cnt_th[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if constexpr (EPI >= 2) {
         const int m0 = tm * 128, n0 = tn * SPL_BN;
-        if (E.cnt_mode == 3) {
+        if (E.cnt_mode == EPI_PICK) {
             const int lo = E.cnt_off[m0], hi = E.cnt_off[min(m0 + 128, p.M)];
             if (n0 >= hi || n0 + SPL_BN <= lo) return;
         }
-        if ((E.cnt_mode == 1 || E.cnt_mode == 2) && threadIdx.x < 128 && m0 + (int)threadIdx.x < p.M) {
+        if ((E.cnt_mode == EPI_COUNT_GT || E.cnt_mode == EPI_COUNT_LT) && threadIdx.x < 128 && m0 + (int)threadIdx.x < p.M) {
             cnt_pb = E.cnt_off[m0 + threadIdx.x];
             cnt_np = E.cnt_off[m0 + threadIdx.x + 1] - cnt_pb;
 #pragma unroll
@@ -717,7 +717,7 @@ int gemm_nt_split_epi_launch(const void* Ap, const void* Bp, const Epi& E, int M
         E2.act_src = (const float*)valid;
         E2.mask = (const unsigned*)valid;
     }
-    if (E.cnt_mode == 6 || E.cnt_mode == 7) {           // the lse mode: its own instantiation (gemm_tile_epilogue's LSE)
+    if (epi_is_lse(E.cnt_mode)) {                       // the lse mode: its own instantiation (gemm_tile_epilogue's LSE)
         ProfScope prof("gemm_nt_split_kernel<2, 3, 2, 3>", stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
         hipLaunchKernelGGL((gemm_nt_split_kernel<2, 3, 2, 3>), dim3(p.nbm * p.nbn), dim3(256), 0, stream, p, E2);
         TXE_CHECK_LAUNCH();

@@ -640,8 +640,6 @@ int txe_bilinear_folded_bwd(const float* Z, long long ld_z, int G, int Kp, const
     return TXE_OK;
 }
 
-int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key, void* stream);
-
 // Plain dense product on the library's fp32 MFMA GEMM (tests / micro-benchmarks; the model paths above use the same kernels
 // through their fused entry points).  layout 0: C = A[M][K] * B[N][K]^T;  1: C = A[M][K] * B[K][N];  2: C = A[K][M]^T * B[K][N].
 // splits > 1 writes `splits` partial products at C + z*M*N (the caller reduces them).
@@ -821,7 +819,7 @@ int txe_score_positives(const float* Q, long long ld_q, int nq, const float* Up,
     VMat B = vmat_plain(Up, ld_u, n_pos, r);
     Epi E = epi_plain(thr, 0, n_pos);
     E.apply_exp = apply_exp;
-    E.cnt_mode = 3;
+    E.cnt_mode = EPI_PICK;
     E.cnt_off = pos_off;
     E.plain_k_order = 1;
     E.alg_flops = 2.0 * n_pos * (double)r;           // the pairs that are wanted
@@ -846,7 +844,7 @@ int txe_score_count_block(const float* Q, long long ld_q, int nq, const float* U
     VMat B = vmat_plain(U, ld_u, G, r);
     Epi E = epi_plain(reinterpret_cast<float*>(counts), 0, G);     // c is never written in count mode
     E.apply_exp = apply_exp;
-    E.cnt_mode = larger_is_better ? 1 : 2;
+    E.cnt_mode = larger_is_better ? EPI_COUNT_GT : EPI_COUNT_LT;
     E.cnt_off = pos_off; E.cnt_thr = thr; E.cnt_out = counts;
     {
         const int sr = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, (hipStream_t)stream);
@@ -863,14 +861,6 @@ int txe_score_count_block(const float* Q, long long ld_q, int nq, const float* U
 // Ties in Python's stable order (ascending candidate row), NaN last.  1 <= k <= 8; G >= 1.
 // floor_ws [nq] ints: scratch (the rows' rising selection floors, initialised here).
 int txe_score_topk_tiles(int G) { return (G + 127) / 128; }
-}  // extern "C"
-namespace txe {
-__global__ void topk_floor_init_kernel(int* __restrict__ f, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) f[i] = topk_ord(-INFINITY);
-}
-}  // namespace txe
-extern "C" {
 
 int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
                          int larger_is_better, int k, int idx_base, float* part_key, int* part_idx, int* floor_ws, int* out_idx,
@@ -880,21 +870,18 @@ int txe_score_topk_block(const float* Q, long long ld_q, int nq, const float* U,
         return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
-    hipLaunchKernelGGL(topk_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, (hipStream_t)stream, floor_ws, nq);
-    TXE_CHECK_LAUNCH();
+    hipStream_t s = (hipStream_t)stream;
     VMat A = vmat_plain(Q, ld_q, nq, r);
     VMat B = vmat_plain(U, ld_u, G, r);
     Epi E = epi_plain(part_key, 0, G);                              // c is never written in top-k mode
     E.apply_exp = apply_exp;
-    E.cnt_mode = larger_is_better ? 4 : 5;
+    E.cnt_mode = larger_is_better ? EPI_TOPK_MAX : EPI_TOPK_MIN;
     E.topk_k = k; E.topk_key = part_key; E.topk_idx = part_idx; E.topk_floor = floor_ws;
     E.force_bn128 = 1;                                              // (the scratch layout counts 128-wide column tiles)
-    int rc = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, (hipStream_t)stream);
-    if (rc < 0) return rc;
-    if (rc == 0) rc = gemm_nt(A, B, E, nq, G, r, 1, (hipStream_t)stream);
-    else rc = TXE_OK;
-    if (rc) return rc;
-    return txe_topk_merge(part_key, part_idx, nq, (long long)txe_score_topk_tiles(G) * k, k, idx_base, out_idx, out_key, stream);
+    return topk_one_pass(nq, txe_score_topk_tiles(G), k, {part_key, part_idx, floor_ws, out_idx, out_key, idx_base}, s, [&] {
+        const int sr = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, s);
+        return sr == 0 ? gemm_nt(A, B, E, nq, G, r, 1, s) : (sr < 0 ? sr : TXE_OK);
+    });
 }
 
 // txe_score_topk_block for 1 <= k <= 64 (a curator's list of 10 or 20, a re-ranker's 50: infer.py:100-106 with a longer slice): rounds
@@ -912,13 +899,11 @@ int txe_score_topk_wide_block(const float* Q, long long ld_q, int nq, const floa
     if (nq == 0) return TXE_OK;
     if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
     hipStream_t s = (hipStream_t)stream;
-    float* ck = reinterpret_cast<float*>(ceil_ws);
-    int* ci = reinterpret_cast<int*>(ck + nq);
     VMat A = vmat_plain(Q, ld_q, nq, r);
     VMat B = vmat_plain(U, ld_u, G, r);
     Epi E = epi_plain(part_key, 0, G);                              // c is never written in top-k mode
     E.apply_exp = apply_exp;
-    E.cnt_mode = larger_is_better ? 4 : 5;
+    E.cnt_mode = larger_is_better ? EPI_TOPK_MAX : EPI_TOPK_MIN;
     E.topk_key = part_key; E.topk_idx = part_idx; E.topk_floor = floor_ws;
     E.force_bn128 = 1;                                              // (the scratch layout counts 128-wide column tiles)
     const void* up = u_packed;
@@ -932,20 +917,11 @@ int txe_score_topk_wide_block(const float* Q, long long ld_q, int nq, const floa
             up = w;
         }
     }
-    const long long tiles = txe_score_topk_tiles(G);
-    for (int k0 = 0; k0 < k; k0 += TOPK_MAX) {
-        const int kr = (k - k0 < TOPK_MAX) ? k - k0 : TOPK_MAX;
-        hipLaunchKernelGGL(topk_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
-        TXE_CHECK_LAUNCH();
-        E.topk_k = kr;
-        E.topk_ceil_key = k0 ? ck : nullptr; E.topk_ceil_idx = k0 ? ci : nullptr;
-        int rc = sws ? gemm_nt_split_epi_launch(sws, up, E, nq, G, r, s) : gemm_nt(A, B, E, nq, G, r, 1, s);
-        if (rc) return rc;
-        rc = topk_merge_round(part_key, part_idx, nq, tiles * kr, kr, idx_base, out_idx + k0, out_key ? out_key + k0 : nullptr, k,
-                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
-        if (rc) return rc;
-    }
-    return TXE_OK;
+    return topk_rounds(nq, txe_score_topk_tiles(G), k, {part_key, part_idx, floor_ws, out_idx, out_key, idx_base}, ceil_ws, s,
+                       [&](int kr, const float* ceil_key, const int* ceil_idx) {
+                           E.topk_k = kr; E.topk_ceil_key = ceil_key; E.topk_ceil_idx = ceil_idx;
+                           return sws ? gemm_nt_split_epi_launch(sws, up, E, nq, G, r, s) : gemm_nt(A, B, E, nq, G, r, 1, s);
+                       });
 }
 
 // Fused scoring + log-partition of one block of the loop (model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99: the exact
@@ -953,27 +929,24 @@ int txe_score_topk_wide_block(const float* Q, long long ld_q, int nq, const floa
 // z = the score (larger is better) or its negative.  The score tile never leaves the workgroup; every 128 x 128 tile leaves each row's
 // (max z, sum exp(z - max)) at part_max / part_sum [nq][txe_score_topk_tiles(G)] (scratch), txe_lse_merge combines them in tile order.
 // The same MFMA kernel and k order as txe_score_block: the scores behind the sum are bit-identical to the materialised ones.  G >= 1.
-int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
-
 int txe_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
                         int larger_is_better, float* part_max, float* part_sum, float* lse, void* sws, size_t sws_bytes,
                         const void* u_packed, void* stream) {
     if (nq < 0 || G < 1 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || !Q || !U || !part_max || !part_sum || !lse) return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
+    hipStream_t s = (hipStream_t)stream;
     VMat A = vmat_plain(Q, ld_q, nq, r);
     VMat B = vmat_plain(U, ld_u, G, r);
     Epi E = epi_plain(part_max, 0, G);                              // c is never written in lse mode
     E.apply_exp = apply_exp;
-    E.cnt_mode = larger_is_better ? 6 : 7;
+    E.cnt_mode = larger_is_better ? EPI_LSE_MAX : EPI_LSE_MIN;
     E.lse_m = part_max; E.lse_s = part_sum;
     E.force_bn128 = 1;                                              // (the scratch layout counts 128-wide column tiles)
-    int rc = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, (hipStream_t)stream);
-    if (rc < 0) return rc;
-    if (rc == 0) rc = gemm_nt(A, B, E, nq, G, r, 1, (hipStream_t)stream);
-    else rc = TXE_OK;
-    if (rc) return rc;
-    return txe_lse_merge(part_max, part_sum, nq, (long long)txe_score_topk_tiles(G), lse, stream);
+    return lse_one_pass(nq, txe_score_topk_tiles(G), part_max, part_sum, lse, s, [&] {
+        const int sr = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, s);
+        return sr == 0 ? gemm_nt(A, B, E, nq, G, r, 1, s) : (sr < 0 ? sr : TXE_OK);
+    });
 }
 
 }  // extern "C"

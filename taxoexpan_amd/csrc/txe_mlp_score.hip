@@ -396,11 +396,6 @@ __global__ __launch_bounds__(256) void mlp_positives_kernel(const MlpArgs a, con
     a.S[j] = (a.fa[g] | a.fb[q]) ? mlp_literal(ar, nbr, a.mw, a.Hp) : mlp_pair(ar, nbr, a.mw, a.Hp, a.c[q]);
 }
 
-__global__ void mlp_floor_init_kernel(int* __restrict__ f, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) f[i] = topk_ord(-INFINITY);
-}
-
 static MlpArgs mlp_args(const float* Ap, const int* fa, int G, const float* nB, const float* c, const int* fb, int nq, int H, const float* mw) {
     MlpArgs a{};
     a.Ap = Ap; a.fa = fa; a.G = G; a.nB = nB; a.c = c; a.fb = fb; a.nq = nq; a.mw = mw; a.Hp = mlp_padded(H);
@@ -420,9 +415,6 @@ static int mlp_launch(const MlpArgs& a, hipStream_t s, const char* name) {
 using namespace txe;
 
 extern "C" {
-
-int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key, void* stream);
-int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
 
 int txe_mlp_padded_h(int H) { return H < 1 ? 0 : mlp_padded(H); }
 
@@ -486,13 +478,10 @@ int txe_mlp_score_topk_block(const float* Ap, const int* flag_a, int G, const fl
     if (!TXE_MLP_ARGS_OK || G < 1 || k < 1 || k > TOPK_MAX || !part_key || !part_idx || !floor_ws || !out_idx) return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(mlp_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
-    TXE_CHECK_LAUNCH();
     MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
     a.larger = larger_is_better ? 1 : 0; a.k = k; a.part_key = part_key; a.part_idx = part_idx; a.floor_ws = floor_ws;
-    const int rc = mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]");
-    if (rc) return rc;
-    return txe_topk_merge(part_key, part_idx, nq, (long long)((G + MLP_BG - 1) / MLP_BG) * k, k, idx_base, out_idx, out_key, stream);
+    return topk_one_pass(nq, (G + MLP_BG - 1) / MLP_BG, k, {part_key, part_idx, floor_ws, out_idx, out_key, idx_base}, s,
+                         [&] { return mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]"); });
 }
 
 // model_zoo.py:285-298 under infer.py:100-106 with a longer list -- txe_mlp_score_topk_block for 1 <= k <= 64, txe_score_topk_wide_block's
@@ -503,23 +492,13 @@ int txe_mlp_score_topk_wide_block(const float* Ap, const int* flag_a, int G, con
     if (!TXE_MLP_ARGS_OK || G < 1 || k < 1 || k > TOPK_WIDE_MAX || !part_key || !part_idx || !floor_ws || !out_idx || !ceil_ws) return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     hipStream_t s = (hipStream_t)stream;
-    float* ck = reinterpret_cast<float*>(ceil_ws);
-    int* ci = reinterpret_cast<int*>(ck + nq);
     MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
     a.larger = larger_is_better ? 1 : 0; a.part_key = part_key; a.part_idx = part_idx; a.floor_ws = floor_ws;
-    const long long tiles = (G + MLP_BG - 1) / MLP_BG;
-    for (int k0 = 0; k0 < k; k0 += TOPK_MAX) {
-        const int kr = (k - k0 < TOPK_MAX) ? k - k0 : TOPK_MAX;
-        hipLaunchKernelGGL(mlp_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
-        TXE_CHECK_LAUNCH();
-        a.k = kr; a.ceil_key = k0 ? ck : nullptr; a.ceil_idx = k0 ? ci : nullptr;
-        int rc = k0 ? mlp_launch<MLP_TOPK_CEIL>(a, s, "mlp_pair_kernel[topk]") : mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]");
-        if (rc) return rc;
-        rc = topk_merge_round(part_key, part_idx, nq, tiles * kr, kr, idx_base, out_idx + k0, out_key ? out_key + k0 : nullptr, k,
-                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
-        if (rc) return rc;
-    }
-    return TXE_OK;
+    return topk_rounds(nq, (G + MLP_BG - 1) / MLP_BG, k, {part_key, part_idx, floor_ws, out_idx, out_key, idx_base}, ceil_ws, s,
+                       [&](int kr, const float* ceil_key, const int* ceil_idx) {
+                           a.k = kr; a.ceil_key = ceil_key; a.ceil_idx = ceil_idx;
+                           return ceil_key ? mlp_launch<MLP_TOPK_CEIL>(a, s, "mlp_pair_kernel[topk]") : mlp_launch<MLP_TOPK>(a, s, "mlp_pair_kernel[topk]");
+                       });
 }
 
 // model_zoo.py:285-298 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
@@ -531,9 +510,7 @@ int txe_mlp_score_lse_block(const float* Ap, const int* flag_a, int G, const flo
     hipStream_t s = (hipStream_t)stream;
     MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
     a.larger = larger_is_better ? 1 : 0; a.part_max = part_max; a.part_sum = part_sum;
-    const int rc = mlp_launch<MLP_LSE>(a, s, "mlp_pair_kernel[lse]");
-    if (rc) return rc;
-    return txe_lse_merge(part_max, part_sum, nq, (long long)((G + MLP_BG - 1) / MLP_BG), lse, stream);
+    return lse_one_pass(nq, (G + MLP_BG - 1) / MLP_BG, part_max, part_sum, lse, s, [&] { return mlp_launch<MLP_LSE>(a, s, "mlp_pair_kernel[lse]"); });
 }
 
 }  // extern "C"

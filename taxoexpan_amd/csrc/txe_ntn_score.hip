@@ -8,7 +8,7 @@
 // M, candidates along N, the tile geometry, operand loaders and fragment maps of gemm_kernel) and runs gemm_kernel's k-loop once per
 // slice over U_j; after slice j every accumulator goes through  s = fma(u_j, tanh((acc + a_j[n]) + c_j[m]), s)  and is cleared.  After
 // the last slice s IS the tile the GEMM's epilogue receives: gemm_tile_epilogue stores it, picks the positives' pairs out of it
-// (cnt_mode 3), counts (1 / 2), keeps its best k (4 / 5) or reduces its rows to (max, sum exp) pairs (6 / 7).  No [Q x G x k] pre-activation is ever written, and nothing is split
+// (EPI_PICK), counts (EPI_COUNT_*), keeps its best k (EPI_TOPK_*) or reduces its rows to (max, sum exp) pairs (EPI_LSE_*).  No [Q x G x k] pre-activation is ever written, and nothing is split
 // along the reduction: a score is a function of its two rows' values only (an MFMA accumulator is a k-ordered fmaf chain over its own
 // row and column), so the four modes see bit-identical scores wherever a pair lands -- in another tile, another launch, or among the
 // gathered rows of the positives.
@@ -50,7 +50,7 @@ struct NtnArgs {
 // buffered, one barrier per k-tile).  The k * nk k-tiles of the k slices form one software-pipelined stream: the first k-tile of slice
 // j + 1 is fetched under the last MFMA block of slice j.  A k-tile that lies wholly inside K takes the 16-byte row loader, a ragged
 // last one the element loader (both zero what lies past M / N / K).  V: the operands' common vector width (4, or 1 on odd pitches).
-// LSE: the tile ends in the epilogue's lse mode (Epi: cnt_mode 6 / 7) -- an instantiation of its own
+// LSE: the tile ends in the epilogue's lse mode (Epi: EPI_LSE_MAX / EPI_LSE_MIN) -- an instantiation of its own
 template <int V, bool LSE = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void ntn_score_kernel(const VMat A, VMat B, const NtnArgs P, const Epi E, const int M, const int N,
                                                                     const int K) {
@@ -71,13 +71,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void ntn_score_kernel(const VMat A
     const int tm = row_fast ? lb % nbm : lb / nbn, tn = row_fast ? lb / nbm : lb % nbn;
     const int m0 = tm * GEMM_BM, n0 = tn * BN;
 
-    if (E.cnt_mode == 3) {                           // pick mode: a tile without a (row, own column) pair has nothing to do (block-uniform)
+    if (E.cnt_mode == EPI_PICK) {                    // pick mode: a tile without a (row, own column) pair has nothing to do (block-uniform)
         const int lo = E.cnt_off[m0], hi = E.cnt_off[min(m0 + GEMM_BM, M)];
         if (n0 >= hi || n0 + BN <= lo) return;
     }
     int cnt_pb = 0, cnt_np = 0;
     float cnt_th[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if ((E.cnt_mode == 1 || E.cnt_mode == 2) && threadIdx.x < GEMM_BM && m0 + (int)threadIdx.x < M) {
+    if ((E.cnt_mode == EPI_COUNT_GT || E.cnt_mode == EPI_COUNT_LT) && threadIdx.x < GEMM_BM && m0 + (int)threadIdx.x < M) {
         cnt_pb = E.cnt_off[m0 + threadIdx.x];
         cnt_np = E.cnt_off[m0 + threadIdx.x + 1] - cnt_pb;
 #pragma unroll
@@ -261,7 +261,7 @@ static int ntn_launch(const NtnCall& n, int N, Epi E, hipStream_t s, const char*
     // 16-byte loaders when every row of both operands starts on a 16-byte boundary -- every slice's too
     const bool v4 = vmat_vec(A) == 4 && vmat_vec(B) == 4 && (n.k == 1 || n.slice_u % 4 == 0);
     ProfScope prof(name, s, 2.0 * n.nq * (double)N * n.r * n.k, 0);
-    if (E.cnt_mode == 6 || E.cnt_mode == 7) {
+    if (epi_is_lse(E.cnt_mode)) {
         if (v4) hipLaunchKernelGGL((ntn_score_kernel<4, true>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
         else hipLaunchKernelGGL((ntn_score_kernel<1, true>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
     } else if (v4) hipLaunchKernelGGL((ntn_score_kernel<4>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
@@ -270,20 +270,11 @@ static int ntn_launch(const NtnCall& n, int N, Epi E, hipStream_t s, const char*
     return TXE_OK;
 }
 
-__global__ void ntn_floor_init_kernel(int* __restrict__ f, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) f[i] = topk_ord(-INFINITY);
-}
-
 }  // namespace txe
 
 using namespace txe;
 
 extern "C" {
-
-int txe_topk_merge(const float* keys, const int* idx, int nq, long long cnt, int k, int idx_base, int* out_idx, float* out_key, void* stream);
-int txe_score_topk_tiles(int G);
-int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
 
 int txe_ntn_project(const float* hg, long long ld_hg, int G, int l, const float* V1, long long ld_v, const float* b, int k, float* a,
                     long long ld_a, void* stream) {
@@ -318,7 +309,7 @@ int txe_ntn_score_positives(const float* Q, long long ld_q, int nq, const float*
     if (!ntn_call_ok(n) || !pos_off || !thr) return TXE_ERR_ARG;
     if (nq == 0 || G == 0) return TXE_OK;
     Epi E = epi_plain(thr, 0, G);
-    E.cnt_mode = 3;
+    E.cnt_mode = EPI_PICK;
     E.cnt_off = pos_off;
     return ntn_launch(n, G, E, (hipStream_t)stream, "ntn_score_kernel[positives]");
 }
@@ -330,7 +321,7 @@ int txe_ntn_score_count_block(const float* Q, long long ld_q, int nq, const floa
     if (!ntn_call_ok(n) || !pos_off || !thr || !counts) return TXE_ERR_ARG;
     if (nq == 0 || G == 0) return TXE_OK;
     Epi E = epi_plain(reinterpret_cast<float*>(counts), 0, G);     // c is never written in count mode
-    E.cnt_mode = larger_is_better ? 1 : 2;
+    E.cnt_mode = larger_is_better ? EPI_COUNT_GT : EPI_COUNT_LT;
     E.cnt_off = pos_off; E.cnt_thr = thr; E.cnt_out = counts;
     return ntn_launch(n, G, E, (hipStream_t)stream, "ntn_score_kernel[count]");
 }
@@ -343,14 +334,11 @@ int txe_ntn_score_topk_block(const float* Q, long long ld_q, int nq, const float
     if (!ntn_call_ok(n) || G < 1 || topk < 1 || topk > TOPK_MAX || !part_key || !part_idx || !floor_ws || !out_idx) return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ntn_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
-    TXE_CHECK_LAUNCH();
     Epi E = epi_plain(part_key, 0, G);                              // c is never written in top-k mode
-    E.cnt_mode = larger_is_better ? 4 : 5;
+    E.cnt_mode = larger_is_better ? EPI_TOPK_MAX : EPI_TOPK_MIN;
     E.topk_k = topk; E.topk_key = part_key; E.topk_idx = part_idx; E.topk_floor = floor_ws;
-    const int rc = ntn_launch(n, G, E, s, "ntn_score_kernel[topk]");
-    if (rc) return rc;
-    return txe_topk_merge(part_key, part_idx, nq, (long long)txe_score_topk_tiles(G) * topk, topk, idx_base, out_idx, out_key, stream);
+    return topk_one_pass(nq, txe_score_topk_tiles(G), topk, {part_key, part_idx, floor_ws, out_idx, out_key, idx_base}, s,
+                         [&] { return ntn_launch(n, G, E, s, "ntn_score_kernel[topk]"); });
 }
 
 // model_zoo.py:331-346 under infer.py:100-106 with a longer list -- txe_ntn_score_topk_block for 1 <= topk <= 64, txe_score_topk_wide_block's
@@ -364,25 +352,14 @@ int txe_ntn_score_topk_wide_block(const float* Q, long long ld_q, int nq, const 
         return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     hipStream_t s = (hipStream_t)stream;
-    float* ck = reinterpret_cast<float*>(ceil_ws);
-    int* ci = reinterpret_cast<int*>(ck + nq);
     Epi E = epi_plain(part_key, 0, G);                              // c is never written in top-k mode
-    E.cnt_mode = larger_is_better ? 4 : 5;
+    E.cnt_mode = larger_is_better ? EPI_TOPK_MAX : EPI_TOPK_MIN;
     E.topk_key = part_key; E.topk_idx = part_idx; E.topk_floor = floor_ws;
-    const long long tiles = txe_score_topk_tiles(G);
-    for (int k0 = 0; k0 < topk; k0 += TOPK_MAX) {
-        const int kr = (topk - k0 < TOPK_MAX) ? topk - k0 : TOPK_MAX;
-        hipLaunchKernelGGL(ntn_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
-        TXE_CHECK_LAUNCH();
-        E.topk_k = kr;
-        E.topk_ceil_key = k0 ? ck : nullptr; E.topk_ceil_idx = k0 ? ci : nullptr;
-        int rc = ntn_launch(n, G, E, s, "ntn_score_kernel[topk]");
-        if (rc) return rc;
-        rc = topk_merge_round(part_key, part_idx, nq, tiles * kr, kr, idx_base, out_idx + k0, out_key ? out_key + k0 : nullptr, topk,
-                              k0 ? ck : nullptr, k0 ? ci : nullptr, ck, ci, s);
-        if (rc) return rc;
-    }
-    return TXE_OK;
+    return topk_rounds(nq, txe_score_topk_tiles(G), topk, {part_key, part_idx, floor_ws, out_idx, out_key, idx_base}, ceil_ws, s,
+                       [&](int kr, const float* ceil_key, const int* ceil_idx) {
+                           E.topk_k = kr; E.topk_ceil_key = ceil_key; E.topk_ceil_idx = ceil_idx;
+                           return ntn_launch(n, G, E, s, "ntn_score_kernel[topk]");
+                       });
 }
 
 // model_zoo.py:331-346 under model/loss.py:52-57 over test_fast.py:121-123 / infer.py:97-99 -- the log-partition of every query over all
@@ -394,11 +371,10 @@ int txe_ntn_score_lse_block(const float* Q, long long ld_q, int nq, const float*
     if (!ntn_call_ok(n) || G < 1 || !part_max || !part_sum || !lse) return TXE_ERR_ARG;
     if (nq == 0) return TXE_OK;
     Epi E = epi_plain(part_max, 0, G);                              // c is never written in lse mode
-    E.cnt_mode = larger_is_better ? 6 : 7;
+    E.cnt_mode = larger_is_better ? EPI_LSE_MAX : EPI_LSE_MIN;
     E.lse_m = part_max; E.lse_s = part_sum;
-    const int rc = ntn_launch(n, G, E, (hipStream_t)stream, "ntn_score_kernel[lse]");
-    if (rc) return rc;
-    return txe_lse_merge(part_max, part_sum, nq, (long long)txe_score_topk_tiles(G), lse, stream);
+    hipStream_t s = (hipStream_t)stream;
+    return lse_one_pass(nq, txe_score_topk_tiles(G), part_max, part_sum, lse, s, [&] { return ntn_launch(n, G, E, s, "ntn_score_kernel[lse]"); });
 }
 
 #undef TXE_NTN_CALL

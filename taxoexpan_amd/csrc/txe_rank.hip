@@ -238,6 +238,18 @@ int topk_merge_round(const float* keys, const int* idx, int nq, long long cnt, i
     return TXE_OK;
 }
 
+// the rows' rising selection floors before a pass of the score tiles in top-k mode: nothing chosen yet
+__global__ void topk_floor_init_kernel(int* __restrict__ f, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) f[i] = topk_ord(-INFINITY);
+}
+
+int topk_floor_init(int* floor_ws, int nq, hipStream_t s) {
+    hipLaunchKernelGGL(topk_floor_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, floor_ws, nq);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
 // lse[q] = log sum exp z of row q from its `cnt` (max, sum) pairs (txe_common.h: m = max z, s = sum exp(z - m) of a part of the row; NaN /
 // +Inf / -Inf in m name the special cases, (-Inf, 0) is an empty part) -- the per-tile pairs of the score kernels' lse epilogue, or the
 // per-rank pairs of a candidate-sharded loop.  One wave per row, in float64: M = the largest m (NaN kept), then the lanes' strided

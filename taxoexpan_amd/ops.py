@@ -3,7 +3,9 @@
 torch is plumbing here: it owns device memory (caching allocator), the current HIP stream and autograd's tape;
 every number is produced by the hand-written HIP kernels.  There is no CPU path -- host tensors raise.
 """
+import collections
 import ctypes
+import functools
 import typing
 import weakref
 
@@ -1872,21 +1874,164 @@ def _score_sws(nq, G, r, ref, u_packed=False):
     return _ws(n, ref), n
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# the modes of the all-candidate loop -- store, count, best-k, log-partition -- once for every matcher family
+# ----------------------------------------------------------------------------------------------------------------
+class _Family:
+    """what the mode functions below (and scoring.prepare_matcher's loop over blocks) take from a matcher family:
+    prefix: of its C entry points -- prefix + "_block" / "_count_block" / "_topk_block" / "_topk_wide_block" / "_lse_block";
+    queries(Q, prep, q_padded=False): one block's prepared query side, its row count in .n;
+    head(qp, prep) / tail(qp, prep, store=False): the C arguments in front of / behind a mode's own (store: for prefix_block);
+    ref(qp, prep): the tensor whose device the outputs and the scratch follow;
+    project(hg, match): the candidate side; loop_queries(Q, prep): all queries prepared once, their row blocks go to queries();
+    positives(qb, prep, off, rows, out): the thresholds of the ranking, whose route differs per family.
+    BIM / LBM is the subclass below; MLP and NTN (_MLP, _NTN further down) are instances made of their sections' functions."""
+
+    def __init__(self, prefix, **functions):
+        self.prefix = prefix
+        self.__dict__.update(functions)
+
+    def tail(self, qp, prep, store=False):
+        return ()
+
+
+# one query block of a BIM / LBM call: Q laid as _query_layout asks (pitch ldq, contraction width K), its row count, the candidates' planes
+# that go with K (up: _planes) and the scratch of the bf16 route beside them (sws, swb: _score_sws)
+_BilinearQueries = collections.namedtuple("_BilinearQueries", "Q ldq K n up sws swb")
+
+
+class _BilinearFamily(_Family):
+    """BIM (apply_exp false) / LBM (true) over a BilinearPrepared"""
+    prefix = "txe_score"
+
+    def __init__(self, apply_exp):
+        self.apply_exp = apply_exp
+
+    def project(self, hg, match):
+        return bilinear_prepare(hg, match.W.weight)
+
+    def loop_queries(self, Q, prep):
+        return pad_queries_like(Q, prep)
+
+    def positives(self, qb, prep, off, rows, out):
+        return positive_scores_staircase(qb, prep.gather(rows), self.apply_exp, off, out)
+
+    def queries(self, Q, prep, q_padded=False):
+        _need_cuda(Q, prep.full)
+        Q, ldq, K = _lay_queries(Q, prep, q_padded)
+        up = _planes(prep, K)
+        return _BilinearQueries(Q, ldq, K, Q.shape[0], up, *_score_sws(Q.shape[0], prep.G, K, Q, up is not None))
+
+    def head(self, qp, prep):
+        return (ptr(qp.Q), qp.ldq, qp.n, ptr(prep.full), prep.full.stride(0), prep.G, qp.K, int(self.apply_exp))
+
+    def tail(self, qp, prep, store=False):
+        tws = _tail_ws(qp.Q) if store else None         # (the stored block's whole rounds run on persistent workgroups: their scratch)
+        return ((ptr(tws), tws.numel()) if store else ()) + (ptr(qp.sws), qp.swb, ptr(qp.up))
+
+    def ref(self, qp, prep):
+        return qp.Q
+
+
+def _store_block(fam, Q, prep, out=None):
+    """S [nq, G] of one query block; default: rows on a 16-byte pitch (vector stores / rank sweeps)"""
+    qp = fam.queries(Q, prep)
+    nq, G, ref = qp.n, prep.G, fam.ref(qp, prep)
+    S = out if out is not None else _empty((nq, (G + 3) // 4 * 4), ref)[:, :G]
+    assert S.dtype == torch.float32 and (S.numel() == 0 or S.stride(1) == 1)
+    if nq > 0 and G > 0:
+        with _lib.on_device(ref.device):
+            call(fam.prefix + "_block", *fam.head(qp, prep), ptr(S), S.stride(0) if nq > 1 else max(S.stride(0), G),
+                 *fam.tail(qp, prep, store=True), _lib.stream_ptr())
+    return S
+
+
+def _count_block(fam, Q, prep, pos_off, thr, larger_is_better, counts, q_padded=False):
+    """counts int32 [n_pos] += the candidates strictly better than each positive's threshold; counts None: zeros made here"""
+    qp = fam.queries(Q, prep, q_padded)
+    ref = fam.ref(qp, prep)
+    pos_off = _i32(pos_off, ref.device)
+    thr = _f32(thr)
+    if counts is None:
+        counts = torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=ref.device)
+    if thr.numel() == 0 or qp.n == 0 or prep.G == 0:    # (a query block without a single positive: nothing to count)
+        return counts
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
+    with _lib.on_device(ref.device):
+        call(fam.prefix + "_count_block", *fam.head(qp, prep), ptr(pos_off), ptr(thr), int(larger_is_better), ptr(counts),
+             *fam.tail(qp, prep), _lib.stream_ptr())
+    return counts
+
+
+def _topk_scratch(sc, nq, need, ref):
+    """the best-k entry points' per-tile lists (key fp32 / idx int32 [need]) and floors (int32 [nq]) in the dict a loop over blocks
+    passes along (None: for this call only), grown when a block needs more or the device changed"""
+    sc = sc if sc is not None else {}
+    if sc.get("n", 0) < need or sc.get("nq", 0) < nq or sc["key"].device != ref.device:
+        sc["key"], sc["idx"], sc["n"] = _empty((need,), ref), torch.empty(need, dtype=torch.int32, device=ref.device), need
+        sc["floor"], sc["nq"] = torch.empty(nq, dtype=torch.int32, device=ref.device), nq
+    return sc
+
+
+TOPK_WIDE_MAX = 64          # txe_topk_wide_max(): the widest fused best-k (rounds of 8 under a ceiling; csrc/txe_common.h)
+
+
+def _topk_ceil(sc, nq, ref):
+    """the wide best-k entry points' ceilings (8 * nq bytes: [nq] fp32 keys, then [nq] int32 columns) beside _topk_scratch's buffers"""
+    if sc.get("ceil_nq", 0) < nq or sc["ceil"].device != ref.device:
+        sc["ceil"], sc["ceil_nq"] = torch.empty(2 * nq, dtype=torch.int32, device=ref.device), nq
+    return sc["ceil"]
+
+
+def _topk_block(fam, Q, prep, k, larger_is_better, idx_base, scratch, q_padded=False):
+    """(idx int32 [nq, k], key fp32 [nq, k]) of one query block: up to 8 the one pass of prefix_topk_block, above it prefix_topk_wide_block's
+    rounds"""
+    qp = fam.queries(Q, prep, q_padded)
+    nq, G, ref = qp.n, prep.G, fam.ref(qp, prep)
+    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, fam.prefix[4:] + "_topk_block: 1 <= k <= min(64, candidates)"
+    idx = torch.empty((nq, k), dtype=torch.int32, device=ref.device)
+    key = _empty((nq, k), ref)
+    if nq == 0:
+        return idx, key
+    with _lib.on_device(ref.device):
+        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), ref)
+        args = (*fam.head(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx),
+                ptr(key), *fam.tail(qp, prep))
+        if k <= 8:
+            call(fam.prefix + "_topk_block", *args, _lib.stream_ptr())
+        else:
+            call(fam.prefix + "_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, ref)), _lib.stream_ptr())
+    return idx, key
+
+
+def _lse_scratch(sc, need, ref):
+    """the log-partition entry points' per-tile (max, sum) pairs (two fp32 [need]) in the dict a loop over blocks passes along (None: for
+    this call only), grown when a block needs more or the device changed"""
+    sc = sc if sc is not None else {}
+    if sc.get("lse_n", 0) < need or sc["lse_max"].device != ref.device:
+        sc["lse_max"], sc["lse_sum"], sc["lse_n"] = _empty((need,), ref), _empty((need,), ref), need
+    return sc
+
+
+def _lse_block(fam, Q, prep, larger_is_better, scratch, q_padded=False):
+    """lse fp32 [nq] of one query block: one pass of prefix_lse_block"""
+    qp = fam.queries(Q, prep, q_padded)
+    nq, G, ref = qp.n, prep.G, fam.ref(qp, prep)
+    assert G >= 1, fam.prefix[4:] + "_lse_block: at least one candidate"
+    lse = _empty((nq,), ref)
+    if nq == 0:
+        return lse
+    with _lib.on_device(ref.device):
+        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), ref)
+        call(fam.prefix + "_lse_block", *fam.head(qp, prep), int(larger_is_better), ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse),
+             *fam.tail(qp, prep), _lib.stream_ptr())
+    return lse
+
+
 def score_block(Q, U, apply_exp, out=None):
     """S[q][g] = match(hg[g], Q[q]) for a block of queries against every candidate (test_fast.py:116-123).  U: a [G, r] tensor (that of
     bilinear_project brings its padding and planes along) or a BilinearPrepared, here and in the score_* functions below."""
-    prep = _as_prepared(U)
-    _need_cuda(Q, prep.full)
-    Q, ldq, K = _lay_queries(Q, prep)
-    nq, G = Q.shape[0], prep.G
-    S = out if out is not None else _empty((nq, (G + 3) // 4 * 4), Q)[:, :G]     # 16-byte row pitch: vector stores / rank sweeps
-    with _lib.on_device(Q.device):
-        tws = _tail_ws(Q)
-        up = _planes(prep, K)
-        sws, swb = _score_sws(nq, G, K, Q, up is not None)
-        call("txe_score_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), ptr(S), S.stride(0), ptr(tws),
-             tws.numel(), ptr(sws), swb, ptr(up), _lib.stream_ptr())
-    return S
+    return _store_block(_BilinearFamily(apply_exp), Q, _as_prepared(U), out)
 
 
 def positive_scores(Q, U, apply_exp, pos_off, pos_idx):
@@ -1944,43 +2089,7 @@ def score_count_block(Q, U, apply_exp, pos_off, thr, larger_is_better=True, coun
     """fused scoring + ranking of one query block against a candidate (shard) matrix U: int32 counts [n_pos] of candidates that beat
     each positive's score thr[j] (txe_score_count_block; no [nq x G] score block is materialised).
     q_padded: Q is a row block of pad_queries_like(all queries, U) -- its columns up to U's padded width are zeros already."""
-    prep = _as_prepared(U)
-    _need_cuda(Q, prep.full)
-    Q, ldq, K = _lay_queries(Q, prep, q_padded)
-    nq, G = Q.shape[0], prep.G
-    pos_off = _i32(pos_off, Q.device)
-    thr = _f32(thr)
-    if counts is None:
-        counts = torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=Q.device)
-    if thr.numel() == 0:                                # a query block without a single positive: nothing to count
-        return counts
-    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
-    with _lib.on_device(Q.device):
-        up = _planes(prep, K)
-        sws, swb = _score_sws(nq, G, K, Q, up is not None)
-        call("txe_score_count_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), ptr(pos_off), ptr(thr),
-             int(larger_is_better), ptr(counts), ptr(sws), swb, ptr(up), _lib.stream_ptr())
-    return counts
-
-
-def _topk_scratch(sc, nq, need, ref):
-    """the best-k entry points' per-tile lists (key fp32 / idx int32 [need]) and floors (int32 [nq]) in the dict a loop over blocks
-    passes along (None: for this call only), grown when a block needs more or the device changed"""
-    sc = sc if sc is not None else {}
-    if sc.get("n", 0) < need or sc.get("nq", 0) < nq or sc["key"].device != ref.device:
-        sc["key"], sc["idx"], sc["n"] = _empty((need,), ref), torch.empty(need, dtype=torch.int32, device=ref.device), need
-        sc["floor"], sc["nq"] = torch.empty(nq, dtype=torch.int32, device=ref.device), nq
-    return sc
-
-
-TOPK_WIDE_MAX = 64          # txe_topk_wide_max(): the widest fused best-k (rounds of 8 under a ceiling; csrc/txe_common.h)
-
-
-def _topk_ceil(sc, nq, ref):
-    """the wide best-k entry points' ceilings (8 * nq bytes: [nq] fp32 keys, then [nq] int32 columns) beside _topk_scratch's buffers"""
-    if sc.get("ceil_nq", 0) < nq or sc["ceil"].device != ref.device:
-        sc["ceil"], sc["ceil_nq"] = torch.empty(2 * nq, dtype=torch.int32, device=ref.device), nq
-    return sc["ceil"]
+    return _count_block(_BilinearFamily(apply_exp), Q, _as_prepared(U), pos_off, thr, larger_is_better, counts, q_padded)
 
 
 def score_topk_block(Q, U, apply_exp, k, larger_is_better=True, idx_base=0, q_padded=False, scratch=None):
@@ -1990,27 +2099,7 @@ def score_topk_block(Q, U, apply_exp, k, larger_is_better=True, idx_base=0, q_pa
     the one pass of txe_score_topk_block, above it txe_score_topk_wide_block's ceil(k / 8) rounds of 8 under a ceiling (same order, same
     scores, one pass of the score tiles per round).
     q_padded: as in score_count_block.  scratch: dict reused across the blocks of a loop (the per-tile lists)."""
-    prep = _as_prepared(U)
-    _need_cuda(Q, prep.full)
-    G = prep.G
-    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, "score_topk_block: 1 <= k <= min(64, candidates)"
-    Q, ldq, K = _lay_queries(Q, prep, q_padded)
-    nq = Q.shape[0]
-    idx = torch.empty((nq, k), dtype=torch.int32, device=Q.device)
-    key = _empty((nq, k), Q)
-    if nq == 0:
-        return idx, key
-    with _lib.on_device(Q.device):
-        up = _planes(prep, K)
-        sws, swb = _score_sws(nq, G, K, Q, up is not None)
-        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), Q)
-        args = (ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), int(larger_is_better), int(k), int(idx_base),
-                ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx), ptr(key), ptr(sws), swb, ptr(up))
-        if k <= 8:
-            call("txe_score_topk_block", *args, _lib.stream_ptr())
-        else:
-            call("txe_score_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, Q)), _lib.stream_ptr())
-    return idx, key
+    return _topk_block(_BilinearFamily(apply_exp), Q, _as_prepared(U), k, larger_is_better, idx_base, scratch, q_padded)
 
 
 def topk_merge(keys, idx, k):
@@ -2032,36 +2121,12 @@ def topk_merge(keys, idx, k):
     return out_i, out_k
 
 
-def _lse_scratch(sc, need, ref):
-    """the log-partition entry points' per-tile (max, sum) pairs (two fp32 [need]) in the dict a loop over blocks passes along (None: for
-    this call only), grown when a block needs more or the device changed"""
-    sc = sc if sc is not None else {}
-    if sc.get("lse_n", 0) < need or sc["lse_max"].device != ref.device:
-        sc["lse_max"], sc["lse_sum"], sc["lse_n"] = _empty((need,), ref), _empty((need,), ref), need
-    return sc
-
-
 def score_lse_block(Q, U, apply_exp, larger_is_better=True, q_padded=False, scratch=None):
     """fused scoring + log-partition of one query block against a candidate matrix U (txe_score_lse_block): fp32 [nq],
     lse[q] = log sum_g exp(z[q][g]) with z the score (larger is better) or its negative -- the exact denominator of loss.py:52-57 over
     every candidate.  No [nq x G] block is materialised.  G >= 1.  A NaN score gives NaN, a z = +Inf gives +Inf, all z = -Inf gives
     -Inf.  q_padded: as in score_count_block.  scratch: dict reused across the blocks of a loop (the per-tile pairs)."""
-    prep = _as_prepared(U)
-    _need_cuda(Q, prep.full)
-    G = prep.G
-    assert G >= 1, "score_lse_block: at least one candidate"
-    Q, ldq, K = _lay_queries(Q, prep, q_padded)
-    nq = Q.shape[0]
-    lse = _empty((nq,), Q)
-    if nq == 0:
-        return lse
-    with _lib.on_device(Q.device):
-        up = _planes(prep, K)
-        sws, swb = _score_sws(nq, G, K, Q, up is not None)
-        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), Q)
-        call("txe_score_lse_block", ptr(Q), ldq, nq, ptr(prep.full), prep.full.stride(0), G, K, int(apply_exp), int(larger_is_better),
-             ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse), ptr(sws), swb, ptr(up), _lib.stream_ptr())
-    return lse
+    return _lse_block(_BilinearFamily(apply_exp), Q, _as_prepared(U), larger_is_better, scratch, q_padded)
 
 
 def lse_merge(part_max, part_sum):
@@ -2254,14 +2319,7 @@ def _mlp_args(qp, prep):
 def mlp_score_block(Q, prep, out=None):
     """S[q][g] = match(hg[g], Q[q]) of an MLP matcher for a block of queries (raw [nq, r] or MLPQueries) against every candidate
     (txe_mlp_score_block).  out: [nq, G] view with unit column stride; default: rows on a 16-byte pitch like score_block."""
-    qp = mlp_prepare_queries(Q, prep)
-    G = prep.G
-    S = out if out is not None else _empty((qp.n, (G + 3) // 4 * 4), prep.Ap)[:, :G]
-    assert S.dtype == torch.float32 and (S.numel() == 0 or S.stride(1) == 1)
-    if qp.n > 0 and G > 0:
-        with _lib.on_device(prep.Ap.device):
-            call("txe_mlp_score_block", *_mlp_args(qp, prep), ptr(S), S.stride(0), _lib.stream_ptr())
-    return S
+    return _store_block(_MLP, Q, prep, out)
 
 
 def mlp_positive_scores(Q, prep, pos_off, pos_idx, out=None):
@@ -2283,58 +2341,24 @@ def mlp_positive_scores(Q, prep, pos_off, pos_idx, out=None):
 def mlp_score_count_block(Q, prep, pos_off, thr, larger_is_better=True, counts=None):
     """fused scoring + ranking of one query block (txe_mlp_score_count_block): int32 counts [n_pos] of candidates strictly better than
     each positive's threshold; no [nq x G] block is materialised.  counts (zeroed by the caller) accumulate: shards add."""
-    qp = mlp_prepare_queries(Q, prep)
-    dev = prep.Ap.device
-    pos_off = _i32(pos_off, dev)
-    thr = _f32(thr)
-    if counts is None:
-        counts = torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=dev)
-    if thr.numel() == 0 or qp.n == 0 or prep.G == 0:
-        return counts
-    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
-    with _lib.on_device(dev):
-        call("txe_mlp_score_count_block", *_mlp_args(qp, prep), ptr(pos_off), ptr(thr), int(larger_is_better), ptr(counts),
-             _lib.stream_ptr())
-    return counts
+    return _count_block(_MLP, Q, prep, pos_off, thr, larger_is_better, counts)
 
 
 def mlp_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=None):
     """fused scoring + best-k selection of one query block (txe_mlp_score_topk_block): (idx int32 [nq, k] = candidate rows + idx_base,
     key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(64, G), above 8 by txe_mlp_score_topk_wide_block's
     rounds.  scratch: dict reused across blocks."""
-    qp = mlp_prepare_queries(Q, prep)
-    dev = prep.Ap.device
-    G, nq = prep.G, qp.n
-    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, "mlp_score_topk_block: 1 <= k <= min(64, candidates)"
-    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-    key = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    if nq == 0:
-        return idx, key
-    with _lib.on_device(dev):
-        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), prep.Ap)
-        args = (*_mlp_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx),
-                ptr(key))
-        if k <= 8:
-            call("txe_mlp_score_topk_block", *args, _lib.stream_ptr())
-        else:
-            call("txe_mlp_score_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, prep.Ap)), _lib.stream_ptr())
-    return idx, key
+    return _topk_block(_MLP, Q, prep, k, larger_is_better, idx_base, scratch)
 
 
 def mlp_score_lse_block(Q, prep, larger_is_better=True, scratch=None):
     """fused scoring + log-partition of one query block (txe_mlp_score_lse_block): fp32 [nq] in score_lse_block's definition and
     conventions.  G >= 1.  scratch: dict reused across blocks."""
-    qp = mlp_prepare_queries(Q, prep)
-    G, nq = prep.G, qp.n
-    assert G >= 1, "mlp_score_lse_block: at least one candidate"
-    lse = _empty((nq,), prep.Ap)
-    if nq == 0:
-        return lse
-    with _lib.on_device(prep.Ap.device):
-        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), prep.Ap)
-        call("txe_mlp_score_lse_block", *_mlp_args(qp, prep), int(larger_is_better), ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse),
-             _lib.stream_ptr())
-    return lse
+    return _lse_block(_MLP, Q, prep, larger_is_better, scratch)
+
+
+_MLP = _Family("txe_mlp_score", project=mlp_project, loop_queries=mlp_prepare_queries, positives=mlp_positive_scores, head=_mlp_args,
+               queries=lambda Q, prep, q_padded=False: mlp_prepare_queries(Q, prep), ref=lambda qp, prep: prep.Ap)
 
 
 # ================================================================================================================
@@ -2439,14 +2463,7 @@ def _ntn_args(qp, prep):
 def ntn_score_block(Q, prep, out=None):
     """S[q][g] = match(hg[g], Q[q]) of an NTN matcher for a block of queries (raw [nq, r] or NTNQueries) against every candidate
     (txe_ntn_score_block).  out: [nq, G] view with unit column stride; default: rows on a 16-byte pitch like score_block."""
-    qp = ntn_prepare_queries(Q, prep)
-    G = prep.G
-    S = out if out is not None else _empty((qp.n, (G + 3) // 4 * 4), prep.full)[:, :G]
-    assert S.dtype == torch.float32 and (S.numel() == 0 or S.stride(1) == 1)
-    if qp.n > 0 and G > 0:
-        with _lib.on_device(prep.full.device):
-            call("txe_ntn_score_block", *_ntn_args(qp, prep), ptr(S), S.stride(0) if qp.n > 1 else max(S.stride(0), G), _lib.stream_ptr())
-    return S
+    return _store_block(_NTN, Q, prep, out)
 
 
 def ntn_positive_scores(Q, prep, pos_off, pos_idx, out=None, rows_valid=False):
@@ -2478,54 +2495,23 @@ def ntn_positive_scores(Q, prep, pos_off, pos_idx, out=None, rows_valid=False):
 def ntn_score_count_block(Q, prep, pos_off, thr, larger_is_better=True, counts=None):
     """fused scoring + ranking of one query block (txe_ntn_score_count_block): int32 counts [n_pos] of candidates strictly better than
     each positive's threshold; no [nq x G] block is materialised.  counts (zeroed by the caller) accumulate: shards add."""
-    qp = ntn_prepare_queries(Q, prep)
-    dev = prep.full.device
-    pos_off = _i32(pos_off, dev)
-    thr = _f32(thr)
-    if counts is None:
-        counts = torch.zeros(max(int(thr.numel()), 1), dtype=torch.int32, device=dev)
-    if thr.numel() == 0 or qp.n == 0 or prep.G == 0:
-        return counts
-    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= thr.numel()
-    with _lib.on_device(dev):
-        call("txe_ntn_score_count_block", *_ntn_args(qp, prep), ptr(pos_off), ptr(thr), int(larger_is_better), ptr(counts), _lib.stream_ptr())
-    return counts
+    return _count_block(_NTN, Q, prep, pos_off, thr, larger_is_better, counts)
 
 
 def ntn_score_topk_block(Q, prep, k, larger_is_better=True, idx_base=0, scratch=None):
     """fused scoring + best-k selection of one query block (txe_ntn_score_topk_block): (idx int32 [nq, k] = candidate rows + idx_base,
     key fp32 [nq, k]) in score_topk_block's order and conventions.  1 <= k <= min(64, G), above 8 by txe_ntn_score_topk_wide_block's
     rounds.  scratch: dict reused across blocks."""
-    qp = ntn_prepare_queries(Q, prep)
-    dev = prep.full.device
-    G, nq = prep.G, qp.n
-    assert 1 <= k <= TOPK_WIDE_MAX and k <= G, "ntn_score_topk_block: 1 <= k <= min(64, candidates)"
-    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
-    key = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    if nq == 0:
-        return idx, key
-    with _lib.on_device(dev):
-        sc = _topk_scratch(scratch, nq, nq * pure("txe_score_topk_tiles", G) * min(k, 8), prep.full)
-        args = (*_ntn_args(qp, prep), int(larger_is_better), int(k), int(idx_base), ptr(sc["key"]), ptr(sc["idx"]), ptr(sc["floor"]), ptr(idx),
-                ptr(key))
-        if k <= 8:
-            call("txe_ntn_score_topk_block", *args, _lib.stream_ptr())
-        else:
-            call("txe_ntn_score_topk_wide_block", *args, ptr(_topk_ceil(sc, nq, prep.full)), _lib.stream_ptr())
-    return idx, key
+    return _topk_block(_NTN, Q, prep, k, larger_is_better, idx_base, scratch)
 
 
 def ntn_score_lse_block(Q, prep, larger_is_better=True, scratch=None):
     """fused scoring + log-partition of one query block (txe_ntn_score_lse_block): fp32 [nq] in score_lse_block's definition and
     conventions.  G >= 1.  scratch: dict reused across blocks."""
-    qp = ntn_prepare_queries(Q, prep)
-    G, nq = prep.G, qp.n
-    assert G >= 1, "ntn_score_lse_block: at least one candidate"
-    lse = _empty((nq,), prep.full)
-    if nq == 0:
-        return lse
-    with _lib.on_device(prep.full.device):
-        sc = _lse_scratch(scratch, nq * pure("txe_score_topk_tiles", G), prep.full)
-        call("txe_ntn_score_lse_block", *_ntn_args(qp, prep), int(larger_is_better), ptr(sc["lse_max"]), ptr(sc["lse_sum"]), ptr(lse),
-             _lib.stream_ptr())
-    return lse
+    return _lse_block(_NTN, Q, prep, larger_is_better, scratch)
+
+
+# (positives: the loop hands over the positives' local rows, those of another shard clamped to 0, and masks their scores itself, as for BIM / LBM)
+_NTN = _Family("txe_ntn_score", project=ntn_project, loop_queries=ntn_prepare_queries, head=_ntn_args,
+               positives=functools.partial(ntn_positive_scores, rows_valid=True),
+               queries=lambda Q, prep, q_padded=False: ntn_prepare_queries(Q, prep), ref=lambda qp, prep: prep.full)

@@ -15,83 +15,32 @@ import torch.distributed as dist
 from . import ops
 
 
-class _PreparedBilinear:
-    """a BIM / LBM matcher over a candidate set: U = hg W once (ops.bilinear_prepare), every query block one GEMM with its epilogue"""
+class _PreparedMatcher:
+    """a matcher over a candidate set: the family's candidate side once (ops._BilinearFamily: U = hg W; ops._MLP: A = hg W1a^T + b1;
+    ops._NTN: the k slices U_j = hg W_j and a = V1 hg^T + b), then every query block through ONE function per mode whatever the family
+    (ops._store_block / _count_block / _topk_block / _lse_block) -- the same scratch and count conventions for all.  The blocks of
+    positives / count / topk / lse are row blocks of .queries(all queries); score takes raw query rows."""
 
-    def __init__(self, match, hg):
-        self.prep, self.exp = ops.bilinear_prepare(hg, match.W.weight), match.apply_exp
-
-    def queries(self, Q):
-        return ops.pad_queries_like(Q, self.prep)
-
-    def score(self, qb, out=None):
-        return ops.score_block(qb, self.prep, self.exp, out=out)
-
-    def positives(self, qb, off, rows, out):
-        return ops.positive_scores_staircase(qb, self.prep.gather(rows), self.exp, off, out)
-
-    def count(self, qb, off, thr, larger_is_better, counts):
-        return ops.score_count_block(qb, self.prep, self.exp, off, thr, larger_is_better, counts=counts, q_padded=True)
-
-    def topk(self, qb, k, larger_is_better, idx_base, scratch):
-        return ops.score_topk_block(qb, self.prep, self.exp, k, larger_is_better, idx_base=idx_base, q_padded=True, scratch=scratch)
-
-    def lse(self, qb, larger_is_better, scratch):
-        return ops.score_lse_block(qb, self.prep, self.exp, larger_is_better, q_padded=True, scratch=scratch)
-
-
-class _PreparedMLP:
-    """the MLP matcher over a candidate set: A = hg W1a^T + b1 once (ops.mlp_project), every query block through the VALU pair kernel
-    (txe_mlp_*) -- the same four modes, the same scratch and count conventions"""
-
-    def __init__(self, match, hg):
-        self.prep = ops.mlp_project(hg, match)
+    def __init__(self, fam, match, hg):
+        self.fam, self.prep = fam, fam.project(hg, match)
 
     def queries(self, Q):
-        return ops.mlp_prepare_queries(Q, self.prep)
+        return self.fam.loop_queries(Q, self.prep)
 
     def score(self, qb, out=None):
-        return ops.mlp_score_block(qb, self.prep, out=out)
+        return ops._store_block(self.fam, qb, self.prep, out)
 
     def positives(self, qb, off, rows, out):
-        return ops.mlp_positive_scores(qb, self.prep, off, rows, out=out)
+        return self.fam.positives(qb, self.prep, off, rows, out)
 
     def count(self, qb, off, thr, larger_is_better, counts):
-        return ops.mlp_score_count_block(qb, self.prep, off, thr, larger_is_better, counts=counts)
+        return ops._count_block(self.fam, qb, self.prep, off, thr, larger_is_better, counts, q_padded=True)
 
     def topk(self, qb, k, larger_is_better, idx_base, scratch):
-        return ops.mlp_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
+        return ops._topk_block(self.fam, qb, self.prep, k, larger_is_better, idx_base, scratch, q_padded=True)
 
     def lse(self, qb, larger_is_better, scratch):
-        return ops.mlp_score_lse_block(qb, self.prep, larger_is_better, scratch=scratch)
-
-
-class _PreparedNTN:
-    """the NTN matcher over a candidate set: the k slices U_j = hg W_j and a = V1 hg^T + b once (ops.ntn_project), every query block
-    through the score GEMM's tile run once per slice with tanh and the sum over slices in registers (txe_ntn_*) -- the same four modes,
-    the same scratch and count conventions"""
-
-    def __init__(self, match, hg):
-        self.prep = ops.ntn_project(hg, match)
-
-    def queries(self, Q):
-        return ops.ntn_prepare_queries(Q, self.prep)
-
-    def score(self, qb, out=None):
-        return ops.ntn_score_block(qb, self.prep, out=out)
-
-    def positives(self, qb, off, rows, out):
-        # (rows: the positives' local rows, those of another shard clamped to 0 -- the caller masks their scores, as for BIM / LBM)
-        return ops.ntn_positive_scores(qb, self.prep, off, rows, out=out, rows_valid=True)
-
-    def count(self, qb, off, thr, larger_is_better, counts):
-        return ops.ntn_score_count_block(qb, self.prep, off, thr, larger_is_better, counts=counts)
-
-    def topk(self, qb, k, larger_is_better, idx_base, scratch):
-        return ops.ntn_score_topk_block(qb, self.prep, k, larger_is_better, idx_base=idx_base, scratch=scratch)
-
-    def lse(self, qb, larger_is_better, scratch):
-        return ops.ntn_score_lse_block(qb, self.prep, larger_is_better, scratch=scratch)
+        return ops._lse_block(self.fam, qb, self.prep, larger_is_better, scratch, q_padded=True)
 
 
 def _ntn_fused_ok(match):
@@ -116,12 +65,19 @@ def prepare_matcher(match, hg):
         if not _ntn_fused_ok(match):
             raise TypeError("no fused all-candidate route for an NTN matcher with a non_linear other than tanh or more than "
                             f"{ops.NTN_MAX_K} slices")
-        return _PreparedNTN(match, hg)
+        return _PreparedMatcher(ops._NTN, match, hg)
     if isinstance(match, MLP):
-        return _PreparedMLP(match, hg)
+        return _PreparedMatcher(ops._MLP, match, hg)
     if hasattr(match, "W") and hasattr(match, "apply_exp"):
-        return _PreparedBilinear(match, hg)
+        return _PreparedMatcher(ops._BilinearFamily(match.apply_exp), match, hg)
     raise TypeError(f"no fused all-candidate route for a {type(match).__name__} matcher (BIM / LBM / MLP / NTN have one)")
+
+
+def _default_block(Q):
+    """queries per launch when the caller names none: a query set of up to 4,096 goes in ONE block (score_all says why; the fused loops:
+    five launches in all instead of five per 1,024 queries), larger sets in blocks of 1,024 (a [1024 x G] tile pass per block; the
+    thresholds' small score matrix grows with block x positives)"""
+    return 1024 if Q > 4096 else max(int(Q), 1)
 
 
 def _ntn_params(m):
@@ -158,7 +114,7 @@ def score_all(match, hg, queries, block=None, out=None):
     Q = queries.shape[0]
     G = hg.shape[0]
     if block is None:
-        block = 1024 if Q > 4096 else max(int(Q), 1)
+        block = _default_block(Q)
     S = out if out is not None else torch.empty((Q, (G + 3) // 4 * 4), dtype=torch.float32, device=hg.device)[:, :G]
     for q0 in range(0, Q, block):
         pm.score(queries[q0:q0 + block], out=S[q0:q0 + block])
@@ -196,7 +152,7 @@ def log_partition_fused(match, hg, queries, larger_is_better=True, block=None):
     dev = hg.device
     Q, G = queries.shape[0], hg.shape[0]
     if block is None:
-        block = 1024 if Q > 4096 else max(int(Q), 1)
+        block = _default_block(Q)
     if Q == 0 or G == 0:
         return torch.full((Q,), -float("inf"), dtype=torch.float32, device=dev)
     if fused_matcher_ok(match):
@@ -352,9 +308,7 @@ def rank_all_fused(match, hg, queries, pos_off, pos_idx, block=None, larger_is_b
     dev = hg.device
     distributed = _sharded_call(group, sharded)
     if block is None:
-        # query blocks of 1,024 (a [1024 x G] tile pass per block; the thresholds' small score matrix grows with block x positives);
-        # a query set of a few thousand goes in ONE block: five launches in all instead of five per 1,024 queries
-        block = 1024 if queries.shape[0] > 4096 else max(int(queries.shape[0]), 1)
+        block = _default_block(queries.shape[0])
     if local_fns is None and hg.shape[0] > 0:
         ranks, thr = _rank_all_fused_device(match, hg, queries, pos_off, pos_idx, block, larger_is_better, group, shard_lo, distributed)
         return (ranks, thr) if return_thresholds else ranks
@@ -678,7 +632,7 @@ def topk_parents_fused(match, hg, queries, candidate_ids=None, k=5, larger_is_be
     k_loc = min(int(k), G, ops.TOPK_WIDE_MAX)
     assert int(k) <= ops.TOPK_WIDE_MAX, "topk_parents_fused: k <= 64 (rounds of 8 under a ceiling; wider lists: score blocks + ops.select_k)"
     if block is None:
-        block = 1024 if Q > 4096 else max(Q, 1)
+        block = _default_block(Q)
     outs = []
     if k_loc > 0 and Q > 0:
         pm = prepare_matcher(match, hg)

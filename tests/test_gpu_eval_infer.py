@@ -453,3 +453,57 @@ def test_fused_routes_agree_between_the_prepared_matcher_and_the_projected_tenso
                     top_b = ops.score_topk_block(Qb[q0:q1], U, ex, 5, larger, idx_base=7, q_padded=True)
                     top_c = ops.score_topk_block(Q[q0:q1], U, ex, 5, larger, idx_base=7)
                     assert all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(top_a, top_b, top_c))
+
+
+@pytest.mark.parametrize("kind", ["MLP", "NTN"])
+def test_fused_routes_agree_between_the_prepared_matcher_and_the_named_entry_points(kind):
+    """MLP and NTN: score / positives / count / best-k (k = 5: one pass; k = 17: two rounds, the second ragged; idx_base 7) /
+    log-partition give the same bits whether they are reached through scoring.prepare_matcher(match, hg) or through the named
+    ops.mlp_* / ops.ntn_* functions on a candidate side of their own -- for the whole query set in one block (130 rows: two row tiles,
+    the second ragged) and for blocks of 128 that share one scratch dict per side; 257 candidates are three column tiles, the last one
+    column wide.  Both sides run the same kernels on the same values: exact, no tolerance."""
+    from taxoexpan_amd import model_zoo as mz, ops, scoring
+    dev, nq, G, l, r = _dev(), 130, 257, 12, 12
+    gen = torch.Generator().manual_seed(nq + G)
+    hg = (torch.randn(G, l, generator=gen) * 0.5).to(dev)
+    Q = (torch.randn(nq, r, generator=gen) * 0.5).to(dev)
+    torch.manual_seed(11)
+    match = (mz.MLP(l, r, 20) if kind == "MLP" else mz.NTN(l, r, k=3)).to(dev)
+    rs = np.random.RandomState(2)
+    npos = rs.randint(2, 5, size=nq)                                       # about three positives per query
+    pos_idx = torch.from_numpy(np.concatenate([rs.choice(G, size=k, replace=False) for k in npos]).astype(np.int64)).to(dev)
+    pos_off = np.concatenate([[0], np.cumsum(npos)]).astype(np.int64)
+    project, score, positives, count, topk, lse = {
+        "MLP": (ops.mlp_project, ops.mlp_score_block, ops.mlp_positive_scores, ops.mlp_score_count_block, ops.mlp_score_topk_block,
+                ops.mlp_score_lse_block),
+        "NTN": (ops.ntn_project, ops.ntn_score_block, ops.ntn_positive_scores, ops.ntn_score_count_block, ops.ntn_score_topk_block,
+                ops.ntn_score_lse_block)}[kind]
+    with torch.no_grad():
+        pm = scoring.prepare_matcher(match, hg)
+        prep = project(hg, match)
+        Qa = pm.queries(Q)
+        for block in (nq, 128):                                            # 130 = 128 + 2
+            sc_a, sc_b = (None, None) if block == nq else ({}, {})
+            for q0 in range(0, nq, block):
+                q1 = min(q0 + block, nq)
+                lo, hi = int(pos_off[q0]), int(pos_off[q1])
+                off = torch.from_numpy((pos_off[q0:q1 + 1] - lo).astype(np.int32)).to(dev)
+                rows = pos_idx[lo:hi]
+                where = (kind, block, q0)
+                assert torch.equal(pm.score(Q[q0:q1]), score(Q[q0:q1], prep)), where
+                thr_a = pm.positives(Qa[q0:q1], off, rows, torch.empty(hi - lo, device=dev))
+                thr_b = positives(Q[q0:q1], prep, off, rows)
+                assert thr_a.shape == (hi - lo,) and torch.equal(thr_a, thr_b), where
+                for larger in (True, False):
+                    cnt_a = pm.count(Qa[q0:q1], off, thr_a, larger, torch.zeros(hi - lo, dtype=torch.int32, device=dev))
+                    cnt_b = count(Q[q0:q1], prep, off, thr_b, larger)
+                    assert torch.equal(cnt_a, cnt_b[:hi - lo]), where + (larger,)
+                    for k in (5, 17):
+                        top_a = pm.topk(Qa[q0:q1], k, larger, 7, sc_a)
+                        top_b = topk(Q[q0:q1], prep, k, larger, idx_base=7, scratch=sc_b)
+                        assert top_a[0].shape == (q1 - q0, k) and int(top_a[0].min()) >= 7, where + (larger, k)
+                        assert all(torch.equal(a, b) for a, b in zip(top_a, top_b)), where + (larger, k)
+                    lse_a, lse_b = pm.lse(Qa[q0:q1], larger, sc_a), lse(Q[q0:q1], prep, larger, scratch=sc_b)
+                    assert lse_a.shape == (q1 - q0,) and torch.equal(lse_a, lse_b), where + (larger,)
+            if sc_a is not None:                                           # the loop's one dict served best-k and log-partition
+                assert set(sc_a) == set(sc_b) == {"key", "idx", "floor", "n", "nq", "ceil", "ceil_nq", "lse_max", "lse_sum", "lse_n"}
