@@ -770,6 +770,30 @@ int txe_adam_step_guarded(int n_tensors, float* const* params, const float* cons
                           double beta2, double eps, double weight_decay, long long step, const double* gnorm2,
                           const long long* first_bad, double max_grad_norm, void* stream);
 
+/* txe_adam_step_guarded with an exponential moving average of the parameters formed in the same launches (an addition: the reference has
+ * no weight averaging).  ema is a seventh HOST array of n_tensors DEVICE pointers (dense fp32, numel[t] elements, no overlap with any
+ * other buffer).  After the update of an element the same thread forms, in fp32,
+ *   e = fma(one_minus_d, p_new - e, e),   one_minus_d = (float)(1.0 - ema_decay),   p_new = the parameter value this step stores
+ * -- lerp(e, p_new, 1 - ema_decay) in the form exp_avg uses.  ema_decay is the effective decay of THIS step (a warm-up schedule is the
+ * host's: optim.ema_decay_at); it must satisfy 0 <= ema_decay < 1, else TXE_ERR_ARG with nothing launched -- this check comes before every
+ * other one.  A NULL ema[t] of a non-empty tensor is TXE_ERR_ARG.  The update itself does not depend on e: params, exp_avg, exp_avg_sq and
+ * max_exp_avg_sq get the bits txe_adam_step_guarded gives them.  An active clip changes g, hence p_new, hence e; a frozen step
+ * (*first_bad >= 0) returns before any load and leaves e untouched as well.  e is read and written with the accesses of the other
+ * buffers: 16 bytes per thread where all seven pointers of a tensor are 16-byte aligned, element by element otherwise.
+ * ema == NULL: txe_adam_step_guarded itself -- the same launches, the same bits; ema_decay is ignored.
+ * gnorm2 / first_bad / max_grad_norm keep the meaning and the ORDERING CONTRACT of txe_adam_step_guarded. */
+int txe_adam_step_ema(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                      float* const* max_exp_avg_sq, float* const* ema, const long long* numel, double lr, double beta1, double beta2,
+                      double eps, double weight_decay, long long step, double ema_decay, const double* gnorm2,
+                      const long long* first_bad, double max_grad_norm, void* stream);
+
+/* a[t][i] <-> b[t][i] for n_tensors pairs of dense tensors of numel[t] 32-bit elements (HOST arrays of DEVICE pointers), up to 24 pairs
+ * per launch.  The exchange moves 32-bit words, never floats: NaN payloads, -0.0 and denormals arrive bit for bit; two calls restore both
+ * sides.  Empty pairs are skipped.  TXE_ERR_ARG (nothing launched): n_tensors < 0, a NULL table with n_tensors > 0, a negative numel, a
+ * NULL pointer of a non-empty pair.  OVERLAP IS NOT SUPPORTED: the two tensors of a pair, and the tensors of different pairs, must not
+ * share memory (every element is read and written by one thread, with no ordering between threads). */
+int txe_tensor_swap(int n_tensors, float* const* a, float* const* b, const long long* numel, void* stream);
+
 /* The per-step device log of the training loop (what trainer.py:63-65 reads back with `loss.item()` every step; csrc/txe_steplog.hip):
  * one call per step, enqueued between `loss.backward()` and `optimizer.step()`; nothing returns to the host.
  *   loss_log[step]   = loss[0]                                     (fp32 device scalar)

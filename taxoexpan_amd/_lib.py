@@ -153,6 +153,8 @@ SIGNATURES = {
     "txe_margin_rank_loss": (I, [P, P, I, I, F, P, P, P, SZ, P]),
     "txe_adam_step": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P]),
     "txe_adam_step_guarded": (I, [I, P, P, P, P, P, P, D, D, D, D, D, L, P, P, D, P]),
+    "txe_adam_step_ema": (I, [I, P, P, P, P, P, P, P, D, D, D, D, D, L, D, P, P, D, P]),
+    "txe_tensor_swap": (I, [I, P, P, P, P]),
     "txe_step_log_ws_bytes": (SZ, [I]),
     "txe_step_log": (I, [P, I, P, P, L, L, P, P, P, P, P, SZ, P]),
     "txe_dropout_uniform_host": (F, [U64, U64]),

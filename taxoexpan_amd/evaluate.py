@@ -235,7 +235,9 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     what info_nce_loss (loss.py:52-57) estimates from sampled negatives.  Formed in float64 from the fp32 lse and the fp32 scores of
     the positives the ranks were counted against.  Non-finite values propagate: a NaN or +-Inf score of a positive or in a query's row
     makes that query's term, and so the mean, NaN or +-Inf.  Not with retrieve=k (ValueError before any launch): a partition over a
-    retrieved subset is not the likelihood.  With nll=False the dict, the ranks and the offsets are what they were without it."""
+    retrieved subset is not the likelihood.  With nll=False the dict, the ranks and the offsets are what they were without it.
+    Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): evaluate(model, ...)` evaluates the averaged
+    model -- the parameters are the averages inside the context; or load a checkpoint's with trainer.load_averaged."""
     device = torch.device(device)
     if retrieve is not None:
         if nll:
@@ -321,7 +323,9 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     (bit-equal to scoring.score_all's entries), log_probs = z - lse[q]: the log of p(parent | query) = exp(z) / sum over ALL candidates
     of exp(z') (scoring.log_partition_fused; z = the score for the info_nce losses, its negative otherwise), formed in float64; `save`
     then writes two more tab-separated columns, `Scores` and `Log-probabilities` (%.6g, comma separated like the parents).  Not with
-    retrieve=k (ValueError before any launch): a partition over a retrieved subset is not the likelihood."""
+    retrieve=k (ValueError before any launch): a partition over a retrieved subset is not the likelihood.
+    Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): infer(model, ...)` infers with the averaged
+    model; or load a checkpoint's with trainer.load_averaged."""
     from .dataset import load_new_taxons
     device = torch.device(device)
     if retrieve is not None:

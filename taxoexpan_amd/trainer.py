@@ -8,7 +8,9 @@ _resume_checkpoint (base/base_trainer.py:59-176) -- in the style of evaluate.val
                   at the first non-finite step, with no launch, pass over the gradients or read-back added
     train_epoch   trainer.py:41-77 without `label.sum()` (:53), `loss.item()` (:64-65) or any other read-back inside the loop
     fit           base_trainer.py:59-107 + trainer.py:79-94: epochs of train_epoch + evaluate.validate, the LR schedule, monitoring,
-                  early stopping, checkpoints with the reference's keys, resume -- and one addition: a diverged epoch ends the run
+                  early stopping, checkpoints with the reference's keys, resume -- and one addition: a diverged epoch ends the run;
+                  averaged=True validates, monitors and checkpoints the averaged weights of optim.Adam(ema_decay=...)
+    load_averaged a checkpoint's averaged weights ("ema_state_dict") into a model
     host_step_log the numpy restatement of txe_step_log (its written definition; the CPU tests use it)
 """
 import inspect
@@ -163,7 +165,10 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         returned grad_norms stay the norms BEFORE clipping -- what clip_grad_norm_ returns.
       freeze_on_nonfinite: from the first step s whose loss or gradients are not finite on, the optimizer launches return without a load
         or a store; after the read-back optimizer.discount_frozen_steps(n_batches - s) takes the skipped steps off the step counts.
-        Model and optimizer are then exactly as after step s - 1 (the forward and backward passes of the later steps still ran)."""
+        Model and optimizer are then exactly as after step s - 1 (the forward and backward passes of the later steps still ran).
+    An optimizer that averages its parameters (optim.Adam(ema_decay=...)) does so inside the same optimizer launch; nothing here changes.
+    A frozen run freezes the averages too: the launch that skips the update skips the average, and the discounted step counts let a
+    warm-up schedule of the decay resume where the device stopped."""
     if loss_fn is None:
         from .loss import info_nce_loss as loss_fn
     info_nce = _is_info_nce(loss_fn)
@@ -233,14 +238,31 @@ class TrainingDiverged(RuntimeError):
         self.epoch, self.step, self.logs, self.checkpoint = epoch, step, list(logs), checkpoint
 
 
-def _checkpoint_state(model, optimizer, epoch, monitor_best, config):
-    return {"arch": type(model).__name__, "epoch": epoch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
-            "monitor_best": monitor_best, "config": config}
+def _checkpoint_state(model, optimizer, epoch, monitor_best, config, averaged=False):
+    """averaged: one more key, "ema_state_dict" = the model's state_dict() with the averages swapped in, as copies (the swap goes back
+    before anything else is read: "state_dict" and "optimizer" are the raw weights and the full state, as ever)"""
+    state = {}
+    if averaged:
+        with optimizer.averaged_parameters():
+            state["ema_state_dict"] = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    state.update({"arch": type(model).__name__, "epoch": epoch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
+                  "monitor_best": monitor_best, "config": config})
+    return state
 
 
-def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, save_best):
+def load_averaged(model, path):
+    """load the averaged weights that fit(averaged=True) wrote into the checkpoint `path` (its "ema_state_dict") into `model`, strictly;
+    a checkpoint without them (written with averaged=False, or by the reference) raises ValueError.  Returns the checkpoint."""
+    ckpt = torch.load(str(path), map_location="cpu", weights_only=False)
+    if "ema_state_dict" not in ckpt:
+        raise ValueError(f"{path} has no 'ema_state_dict': the checkpoint was written without averaged weights (fit(averaged=True))")
+    model.load_state_dict(ckpt["ema_state_dict"], strict=True)
+    return ckpt
+
+
+def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, save_best, averaged=False):
     """base_trainer.py:126-149"""
-    state = _checkpoint_state(model, optimizer, epoch, monitor_best, config)
+    state = _checkpoint_state(model, optimizer, epoch, monitor_best, config, averaged)
     os.makedirs(str(save_dir), exist_ok=True)
     torch.save(state, os.path.join(str(save_dir), f"checkpoint-epoch{epoch}.pth"))
     if save_best:
@@ -277,7 +299,7 @@ def _checked_hard_negatives(cfg, train_loader):
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
         loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False,
-        hard_negatives=None):
+        hard_negatives=None, averaged=False):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -309,7 +331,18 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     loader draws uniformly, between mining epochs it keeps the last table.  Checked before the first step (ValueError): the loader kind,
     0 <= slots <= negative_size, 1 <= size, size >= slots, every >= 1, start >= 1, no other key.  The table is not checkpointed: a
     resumed run mines at its first qualifying epoch.  The log of an epoch that mined gains hard_mined = True and hard_mean_count = the
-    mean of the table's cnt; no other key changes."""
+    mean of the table's cnt; no other key changes.
+    averaged (an addition; off: no new key, no new launch, the logs as they are): the optimizer must be an optim.Adam with an ema_decay
+    in at least one group (ValueError before the first step otherwise).  validate_fn then runs inside
+    optimizer.averaged_parameters(), so the val_* metrics -- and with them the monitor, the plateau scheduler and early stopping --
+    follow the AVERAGED model, and every checkpoint (checkpoint-epochN.pth, model_best.pth, last_finite.pth) gains "ema_state_dict", the
+    model's state_dict() taken inside that context, as copies (load_averaged reads it).  "state_dict" and "optimizer" stay the raw
+    weights and the full optimizer state, the average included, so `resume=` continues exactly.  Hard-negative mining keeps ranking
+    with the raw model, the one being trained: its negatives are meant to be hard for the weights that the next step updates."""
+    if averaged and not (hasattr(optimizer, "averaged_parameters") and any(g.get("ema_decay") is not None for g in optimizer.param_groups)):
+        raise ValueError("fit(averaged=True) needs an optimizer with averaged_parameters() and an ema_decay in at least one parameter "
+                         f"group (taxoexpan_amd.optim.Adam(ema_decay=...)); got {type(optimizer).__name__}")
+    averaged = bool(averaged)
     hard = _checked_hard_negatives(hard_negatives, train_loader)
     if train_epoch_fn is None:
         train_epoch_fn = train_epoch
@@ -363,10 +396,14 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
             if freeze_on_nonfinite and save_dir is not None:
                 os.makedirs(str(save_dir), exist_ok=True)
                 checkpoint = os.path.join(str(save_dir), "last_finite.pth")
-                torch.save(_checkpoint_state(model, optimizer, epoch - 1, mnt_best, config), checkpoint)
+                torch.save(_checkpoint_state(model, optimizer, epoch - 1, mnt_best, config, averaged), checkpoint)
             raise TrainingDiverged(epoch, int(result["first_nonfinite"]), logs, checkpoint)
         if valid_loader is not None:                                   # trainer.py:80-82, base_trainer.py:71-72
-            val = validate_fn(model, valid_loader, metrics=metrics, larger_is_better=larger_is_better)
+            if averaged:
+                with optimizer.averaged_parameters():
+                    val = validate_fn(model, valid_loader, metrics=metrics, larger_is_better=larger_is_better)
+            else:
+                val = validate_fn(model, valid_loader, metrics=metrics, larger_is_better=larger_is_better)
             log.update({"val_" + name: v for name, v in zip(metrics, val["val_metrics"])})
         if lr_scheduler is not None:                                   # trainer.py:84-92
             if plateau:
@@ -389,5 +426,5 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
                 if not_improved_count > early_stop:
                     break
         if save_dir is not None and epoch % save_period == 0:         # base_trainer.py:106-107
-            _save_checkpoint(save_dir, model, optimizer, epoch, mnt_best, config, best)
+            _save_checkpoint(save_dir, model, optimizer, epoch, mnt_best, config, best, averaged)
     return logs

@@ -17,7 +17,14 @@ the device loss (loss.bce_loss / square_exp_loss / margin_rank_loss: still nothi
 as tools/loss_timing.py writes it -- for margin_rank the literal route with its label read-back and host pair construction -- and keeps
 its two `loss.item()`.  --guard goes with info_nce only.
 
-    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50] [--guard] [--loss info_nce]"""
+--ema DECAY (info_nce only, beside --guard or without it) adds two more alternating legs on the same model and optimizer state:
+  (e) train_epoch with the optimizer's ema_decay = DECAY: the average formed inside the Adam launch (txe_adam_step_ema);
+  (l) the yardstick: ema_decay off, and torch._foreach_lerp_ over cloned parameters after every optimizer step -- what
+      torch.optim.swa_utils.AveragedModel does with an EMA rule: one more pass over all parameters, one more launch per step;
+then profiles the three legs twice each, alternating -- adam_kernel<true> of (a) and (l) beside adam_ema_kernel<true> of (e), the
+library's launches per step -- and times the lerp launch of (l) on its own with device events.
+
+    python tools/train_epoch_timing.py [--epochs 3] [--profile-steps 50] [--guard] [--ema DECAY] [--loss info_nce]"""
 import argparse
 import ctypes
 import os
@@ -152,15 +159,78 @@ def guard_report(model, loader, opt, steps, g_s):
           f"counts untouched", flush=True)
 
 
+class LerpAfterStep:
+    """leg (l): the optimizer with its averaging off, and after every step avg = lerp(avg, p, 1 - decay) over clones of the parameters
+    (torch._foreach_lerp_, the update of swa_utils.get_ema_multi_avg_fn); train_epoch sees param_groups, zero_grad and step"""
+
+    def __init__(self, opt, decay):
+        self.opt, self.weight = opt, 1.0 - decay
+        self.params = [p for g in opt.param_groups for p in g["params"]]
+        self.avg = [p.detach().clone() for p in self.params]
+
+    @property
+    def param_groups(self):
+        return self.opt.param_groups
+
+    def zero_grad(self):
+        self.opt.zero_grad()
+
+    @torch.no_grad()
+    def lerp(self):
+        torch._foreach_lerp_(self.avg, [p.detach() for p in self.params], self.weight)
+
+    def step(self):
+        self.opt.step()
+        self.lerp()
+
+
+def set_ema(opt, decay):
+    """averaging on (a decay) or off (None) for every group: optim.Adam reads the key at every step, and keeps state["ema"] while off"""
+    for g in opt.param_groups:
+        g["ema_decay"] = decay
+
+
+def ema_report(model, loader, opt, lerp_opt, decay, steps, e_s, l_s):
+    print(f"(e) {min(e_s):.3f}-{max(e_s):.3f} ms/step (median {float(np.median(e_s)):.3f}), (l) {min(l_s):.3f}-{max(l_s):.3f} ms/step "
+          f"(median {float(np.median(l_s)):.3f})")
+    for r in range(2):
+        for leg, name in (("a", "adam_kernel<true>"), ("e", "adam_ema_kernel<true>"), ("l", "adam_kernel<true>")):
+            set_ema(opt, decay if leg == "e" else None)
+            prof = profiled_kernels(model, loader, lerp_opt if leg == "l" else opt, steps)
+            mean, med, n, work = prof[name]
+            launches = sum(v[2] for v in prof.values()) / steps
+            print(f"round {r} leg ({leg}): {name}: mean {mean:.2f} us, median {med:.2f} us over {n} launches, {work / 1e6:.2f} MB = "
+                  f"{work / (1e-6 * med) / 1e12:.2f} TB/s at the median; {launches:.1f} library launches per step"
+                  + (" (+ 1 torch launch: the lerp)" if leg == "l" else ""), flush=True)
+    set_ema(opt, None)
+    for _ in range(20):
+        lerp_opt.lerp()
+    us = []
+    for _ in range(200):                                     # the lerp launch alone, back to back with nothing: device events around each
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        lerp_opt.lerp()
+        t1.record()
+        t1.synchronize()
+        us.append(1e3 * t0.elapsed_time(t1))
+    n = sum(p.numel() for p in lerp_opt.params)
+    print(f"torch._foreach_lerp_ over {len(lerp_opt.params)} tensors, {n} elements ({12.0 * n / 1e6:.2f} MB read + written), events around "
+          f"each call: mean {float(np.mean(us)):.2f} us, median {float(np.median(us)):.2f} us over {len(us)} calls", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=50)
     ap.add_argument("--guard", action="store_true", help="add leg (g): clip (never active) and freeze on; see the module docstring")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="add legs (e) and (l): the average inside the Adam launch, and a foreach lerp after every step; see the module docstring")
     ap.add_argument("--loss", choices=["info_nce", "bce", "square_exp", "margin_rank"], default="info_nce")
     args = ap.parse_args()
     if args.guard and args.loss != "info_nce":
         ap.error("--guard goes with --loss info_nce only")
+    if args.ema is not None and (args.loss != "info_nce" or not 0.0 < args.ema < 1.0):
+        ap.error("--ema takes a decay in (0, 1) and goes with --loss info_nce only")
     kw = {} if args.loss == "info_nce" else {"loss_fn": DEVICE_LOSS[args.loss]}       # (info_nce: the calls are what they were)
     if kw:
         print(f"loss: {args.loss} -- (a) the device loss, (b) its torch expression", flush=True)
@@ -180,9 +250,24 @@ def main():
     reference_style_epoch(model, _First(loader, 30), opt, dev, args.loss)
     if args.guard:
         train_epoch(model, _First(loader, 30), opt, **GUARD)
-    a_s, b_s, g_s = [], [], []
+    lerp_opt = None
+    if args.ema is not None:
+        set_ema(opt, args.ema)
+        train_epoch(model, _First(loader, 30), opt)
+        set_ema(opt, None)
+        lerp_opt = LerpAfterStep(opt, args.ema)
+        train_epoch(model, _First(loader, 30), lerp_opt)
+    a_s, b_s, g_s, e_s, l_s = [], [], [], [], []
     for e in range(args.epochs):
         ta, ra = timed(lambda: train_epoch(model, loader, opt, **kw))
+        if args.ema is not None:
+            set_ema(opt, args.ema)
+            te, re_ = timed(lambda: train_epoch(model, loader, opt))
+            set_ema(opt, None)
+            tl, rl = timed(lambda: train_epoch(model, loader, lerp_opt))
+            assert re_["first_nonfinite"] == -1 and rl["first_nonfinite"] == -1, "the model diverged: the timing is void"
+            e_s.append(1e3 * te / re_["n_batches"])
+            l_s.append(1e3 * tl / rl["n_batches"])
         if args.guard:
             tg, rg = timed(lambda: train_epoch(model, loader, opt, **GUARD))
             assert rg["first_nonfinite"] == -1, "the model diverged: the timing is void"
@@ -193,6 +278,8 @@ def main():
         b_s.append(1e3 * tb / nb)
         print(f"epoch {e}: (a) train_epoch {1e3 * ta:.1f} ms = {a_s[-1]:.3f} ms/step (loss {ra['loss']:.3f}, |g| {ra['grad_norms'][-1]:.3f}) | "
               + (f"(g) guarded {1e3 * tg:.1f} ms = {g_s[-1]:.3f} ms/step | " if args.guard else "")
+              + (f"(e) EMA in the launch {1e3 * te:.1f} ms = {e_s[-1]:.3f} ms/step | (l) foreach lerp after the step {1e3 * tl:.1f} ms = "
+                 f"{l_s[-1]:.3f} ms/step | " if args.ema is not None else "")
               + f"(b) reference-style loop {1e3 * tb:.1f} ms = {b_s[-1]:.3f} ms/step (loss {lb:.3f})", flush=True)
     prof = profiled_kernels(model, loader, opt, args.profile_steps, **kw)
     loss_kernels = {"bce": ("bce_loss_kernel",), "square_exp": ("square_exp_loss_kernel",),
@@ -204,6 +291,8 @@ def main():
                   f"= {work / (1e-6 * med) / 1e12:.2f} TB/s at the median")
     if args.guard:
         guard_report(model, loader, opt, args.profile_steps, g_s)
+    if args.ema is not None:
+        ema_report(model, loader, opt, lerp_opt, args.ema, args.profile_steps, e_s, l_s)
     print(f"summary: (a) {min(a_s):.3f}-{max(a_s):.3f} ms/step (median {float(np.median(a_s)):.3f}), (b) {min(b_s):.3f}-{max(b_s):.3f} ms/step "
           f"(median {float(np.median(b_s)):.3f}); (a) <= (b) in every epoch: {all(a <= b for a, b in zip(a_s, b_s))}")
 
