@@ -713,6 +713,29 @@ int txe_copy_stream(const void* src, void* dst, long long n_bytes, void* stream)
 int txe_info_nce(const float* x, long long ld_x, int B, int Cc, const long long* target, float* loss, float* d_x, long long ld_dx,
                  void* stream);
 
+/* In-batch negatives (csrc/txe_inbatch.hip): every query row i of S [Q][G] -- the matcher's output for (query i, egonet g) of one
+ * training batch -- is a cross entropy over the batch's columns without those whose anchor lies in the query's mask row:
+ *   valid(i, g) = (g == pos_col[i]) or anchor[g] not in mask_idx[mask_ptr[qnode[i]] .. mask_ptr[qnode[i] + 1])
+ *   loss[0]     = sum_i (log sum_{g valid} exp S[i][g] - S[i][pos_col[i]])                 (sum-reduced, like txe_info_nce)
+ *   d_out[i][g] = softmax over the valid g of row i - [g == pos_col[i]], exactly 0 where not valid; times S[i][g] under chain_exp
+ *                 (S = exp(b): the gradient to b);   n_valid[i] = the valid columns of row i (>= 1: the positive)
+ * mask_ptr / mask_idx: a CSR over nodes, every row ascending (sampler.sampler_arrays); both NULL: nothing is masked.  A masked column's
+ * score is never used (NaN and Inf included); a NaN in a valid column makes the loss NaN.  0 <= pos_col[i] < G and
+ * 0 <= qnode[i] < (nodes of the CSR) are the caller's contract.  d_out may be S itself.  One workgroup per row, then one launch that
+ * adds the row losses in a fixed order in float64: no floating-point atomics, two calls on the same inputs give the same bytes
+ * (valid_total is an integer atomic).  TXE_ERR_ARG before any launch: Q < 0, G < 1, Q * G >= 2^31, ld_s / ld_d < G, a NULL among S,
+ * pos_col, anchor, qnode, loss, d_out, exactly one mask pointer NULL, ws NULL or ws_bytes < txe_inbatch_nce_ws_bytes(Q).
+ * Q == 0: TXE_OK, loss[0] = 0, nothing else written.  After the call ws begins with the Q row losses (fp32, row order). */
+size_t txe_inbatch_nce_ws_bytes(int Q);
+int txe_inbatch_nce(const float* S, long long ld_s, int Q, int G, const int* pos_col, const int* anchor, const int* qnode,
+                    const int* mask_ptr, const int* mask_idx,      /* both NULL: nothing is masked */
+                    int chain_exp,                                  /* 1: d_out = dS * S -- the gradient to b under LBM's exp */
+                    float* loss, float* d_out, long long ld_d,      /* d_out may alias S (in place) */
+                    int* n_valid /* [Q] or NULL */, long long* valid_total /* += sum n_valid, or NULL */,
+                    void* ws, size_t ws_bytes, void* stream);
+/* B[i][g] = exp(B[i][g]) in place over [Q][G] with pitch ld_b: LBM's scores from the bilinear form, in front of txe_inbatch_nce */
+int txe_inbatch_exp(float* B, long long ld_b, int Q, int G, void* stream);
+
 /* ---- the reference's other training losses on a labelled score vector (csrc/txe_pairloss.hip): x [B] fp32, labels [B] int32
  * (label_bytes 4) or int64 (8), read as they are.  An entry is a POSITIVE iff its label is 1.  Each call leaves the sum-reduced loss in
  * loss[0] and its gradient in d_x [B]; no host synchronisation, no floating-point atomics: two calls on the same input give the same

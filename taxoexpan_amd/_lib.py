@@ -147,6 +147,9 @@ SIGNATURES = {
     "txe_select_k_ws_bytes": (SZ, [I, I]),
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),
     "txe_info_nce": (I, [P, L, I, I, P, P, P, L, P]),
+    "txe_inbatch_nce_ws_bytes": (SZ, [I]),
+    "txe_inbatch_nce": (I, [P, L, I, I, P, P, P, P, P, I, P, P, L, P, P, P, SZ, P]),
+    "txe_inbatch_exp": (I, [P, L, I, I, P]),
     "txe_bce_loss": (I, [P, P, I, I, P, P, P]),
     "txe_square_exp_loss": (I, [P, P, I, I, F, P, P, P]),
     "txe_margin_rank_loss_ws_bytes": (SZ, [I]),

@@ -209,6 +209,8 @@ class DeviceBatchLoader:
     host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py).
     hard_negatives / hard_slots (this sampler only; default off): a sampler.HardNegatives table whose rows fill the first hard_slots
     negative slots of every query (txe_sample_anchors_hard); set_hard_negatives changes it between epochs.
+    in_batch=True (this sampler, repeated_queries=True; ValueError otherwise): every batch's graph carries `g.in_batch`, a
+    sampler.InBatchGroups -- views of the sampler's index array and mask CSR for loss.in_batch_info_nce; the 4-tuple keeps its shape.
     sampler="device" on a sampling_mode 0 dataset (validation batches of the shipped configs; train / validation): sampler.DeviceGroupSampler
     draws every parent and at most negative_size negatives per query, labels an int64 device tensor.  The batch size B is then known on
     the device only, so three batches are in flight: each next() after the first finishes batch b (its node count, read back one next()
@@ -216,9 +218,13 @@ class DeviceBatchLoader:
     enqueued itself."""
 
     def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host",
-                 hard_negatives=None, hard_slots=0):
+                 hard_negatives=None, hard_slots=0, in_batch=False):
         if sampler not in ("host", "device"):
             raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
+        if in_batch and not (sampler == "device" and dataset.sampling_mode == 1 and repeated_queries):
+            raise ValueError("in_batch=True needs sampler='device', a sampling_mode 1 dataset and repeated_queries=True (the in-batch "
+                             "groups are views of the device sampler's index array)")
+        self.in_batch = bool(in_batch)
         if hard_negatives is not None and not (sampler == "device" and dataset.sampling_mode == 1):
             raise ValueError("hard negatives need sampler='device' on a sampling_mode 1 dataset")
         self.repeated_queries = bool(repeated_queries)
@@ -234,7 +240,7 @@ class DeviceBatchLoader:
         elif sampler == "device":
             from .sampler import DeviceAnchorSampler
             self.sampler = DeviceAnchorSampler(dataset, self.device, seed=self.seed, dtax=self.dtax)
-            self._labels = {}
+            self._labels, self._pos_cols = {}, {}
         torch.cuda.current_stream(self.device).synchronize()      # the resident taxonomy / feature table are complete from here on
         self._epoch = 0
         if hard_negatives is not None:
@@ -289,6 +295,18 @@ class DeviceBatchLoader:
             lab = self._labels[Q] = lab.reshape(-1)
         return lab
 
+    def _in_batch_groups(self, packed, Q):
+        """sampler.InBatchGroups over the finished batch's packed index array: views, marked as used on the consumer's stream like the
+        batch's other tensors; pos_col = i (1 + k), made once per batch size"""
+        from .sampler import InBatchGroups
+        pos_col = self._pos_cols.get(Q)
+        if pos_col is None:
+            pos_col = self._pos_cols[Q] = torch.arange(Q, dtype=torch.int32, device=self.device) * (1 + self.sampler.k)
+        a = self.sampler.arrays
+        groups = InBatchGroups.from_packed(packed, Q, self.sampler.k, pos_col, a["mask_ptr"], a["mask_idx"])
+        groups.record_stream(torch.cuda.current_stream(self.device))
+        return groups
+
     def _iter_device(self, order, epoch):
         n, bs = len(order), self.batch_size
         order_dev = self.sampler.upload_order(order, self._side)     # once per epoch, on the side stream the launches use
@@ -303,6 +321,8 @@ class DeviceBatchLoader:
                 Q, pending = nxt
                 batch = finish_device_batch(pending, self.features)
                 nxt = begin(b + 1) if b + 1 < len(self) else None
+                if self.in_batch:
+                    batch["g"].in_batch = self._in_batch_groups(pending["packed"], Q)
                 yield batch["g"], batch["x"], batch["qf"], self._label(Q)
         finally:
             self.sampler.in_epoch = False

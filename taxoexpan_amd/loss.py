@@ -9,6 +9,8 @@ gradient (no autograd graph of small torch kernels behind it, no read-back):
                       steps on the stream, nothing read back
     host_bce_loss / host_square_exp_loss / host_margin_rank_loss   the numpy float64 restatements (the written definitions; the tests
                       compare against them)
+    in_batch_info_nce an addition: every query of a batch against ALL of the batch's egonets, masked by the taxonomy (csrc/txe_inbatch.hip,
+                      ops.InBatchNCEFunction; host_in_batch_nce: its float64 restatement)
 
 The last three device losses take (output [B] or [B, 1], target [B] int32 / int64) as trainer.py:57-58 passes them.  An entry is a
 positive iff its label is 1.  Only `nll_loss` (no config uses it) stays with torch."""
@@ -75,6 +77,74 @@ def info_nce_loss(output, target=None):
     if not output.is_cuda:
         raise RuntimeError("taxoexpan_amd.loss.info_nce_loss runs on the MI355X only (no CPU path)")
     return _InfoNCE.apply(output, target).as_subclass(LossTensor)
+
+
+# ---- in-batch negatives -------------------------------------------------------------------------------------------------------------
+
+def is_bilinear_matcher(match):
+    """is `match` a BIM / LBM matcher?  scoring.prepare_matcher's rule: a bilinear weight `W` and the `apply_exp` switch (by attribute,
+    not by class: the reference's own model with its import swapped passes too).  in_batch_info_nce and train_epoch(in_batch=True) ask it."""
+    return hasattr(match, "W") and hasattr(match, "apply_exp")
+
+
+def in_batch_info_nce(match, hg, queries, groups, valid_total=None):
+    """The in-batch loss of one training batch: every query against EVERY graph vector of the batch, not only its own
+    1 + negative_size -- the other queries' egonets are negatives whose encoder work is already paid -- without the columns the taxonomy
+    forbids (sampler.InBatchGroups: an anchor in node2masks[query] is the query's other parent, a sibling's positive or a descendant).
+    match: a BIM / LBM matcher (TypeError otherwise); the cross entropy is taken over its output, b or exp(b), as info_nce_loss takes
+    model(g, h, qf).  hg [G, l]: the graph vectors, e.g. encode_graph's (a DeferredGraphVector is materialised: the folded output layer
+    never forms the hg this product needs).  queries [Q, r]: one row per query (a batch's `qf.rows`; an ops.RepeatedRows gives them).
+    valid_total: None, or an int64 [1] device counter that gains the batch's valid pairs (train_epoch's mean_negatives).
+    Returns the sum-reduced loss as a LossTensor; gradients reach hg and match.W, not the queries."""
+    from . import ops
+    from .model_zoo import _graph_vector
+    if not is_bilinear_matcher(match):
+        raise TypeError(f"in_batch_info_nce takes a BIM / LBM matcher, got {type(match).__name__}")
+    if isinstance(queries, ops.RepeatedRows):
+        queries = queries.rows
+    hg = _graph_vector(hg)
+    if not (torch.is_tensor(hg) and torch.is_tensor(queries) and hg.dim() == 2 and queries.dim() == 2):
+        raise ValueError("in_batch_info_nce takes graph vectors [G, l] and query rows [Q, r]")
+    if not hg.is_cuda:
+        raise RuntimeError("taxoexpan_amd.loss.in_batch_info_nce runs on the MI355X only (no CPU path; loss.host_in_batch_nce is the restatement)")
+    return ops.InBatchNCEFunction.apply(hg, match.W.weight, queries, bool(match.apply_exp), groups, valid_total).as_subclass(LossTensor)
+
+
+def host_in_batch_valid(pos_col, anchor, qnode, mask_ptr=None, mask_idx=None):
+    """valid [Q, G] bool of the in-batch rule: (g == pos_col[i]) or anchor[g] not in the mask row of qnode[i]"""
+    pos_col, anchor, qnode = (np.asarray(a).astype(np.int64).reshape(-1) for a in (pos_col, anchor, qnode))
+    if (mask_ptr is None) != (mask_idx is None):
+        raise ValueError("mask_ptr and mask_idx come together")
+    if pos_col.shape != qnode.shape:
+        raise ValueError(f"one pos_col per query: {pos_col.shape} against {qnode.shape}")
+    valid = np.ones((qnode.shape[0], anchor.shape[0]), dtype=bool)
+    if mask_ptr is not None:
+        mask_ptr, mask_idx = np.asarray(mask_ptr).astype(np.int64), np.asarray(mask_idx)
+        for i, q in enumerate(qnode):
+            valid[i] = ~np.isin(anchor, mask_idx[mask_ptr[q]:mask_ptr[q + 1]])
+    valid[np.arange(qnode.shape[0]), pos_col] = True
+    return valid
+
+
+def host_in_batch_nce(S, pos_col, anchor, qnode, mask_ptr=None, mask_idx=None):
+    """numpy float64 restatement of txe_inbatch_nce -- the written definition: (loss, dS [Q, G], n_valid [Q]).  A masked column's value
+    is never used; dS is exactly 0 there."""
+    S = np.asarray(S, dtype=np.float64)
+    valid = host_in_batch_valid(pos_col, anchor, qnode, mask_ptr, mask_idx)
+    if S.ndim != 2 or S.shape != valid.shape:
+        raise ValueError(f"S must be [Q, G] = {valid.shape}, got {S.shape}")
+    pos_col = np.asarray(pos_col).astype(np.int64).reshape(-1)
+    rows = np.arange(S.shape[0])
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = np.where(valid, S, -np.inf)
+        m = x.max(axis=1, keepdims=True) if S.shape[0] else np.zeros((0, 1))
+        e = np.where(valid, np.exp(x - m), 0.0)
+        s = e.sum(axis=1, keepdims=True)
+        loss = float(np.sum(m[:, 0] + np.log(s[:, 0]) - S[rows, pos_col]))
+        dS = e / s
+        dS[rows, pos_col] -= 1.0
+        dS = np.where(valid, dS, 0.0)
+    return loss, dS, valid.sum(axis=1).astype(np.int64)
 
 
 # ---- bce, square-exp and margin-rank ------------------------------------------------------------------------------------------------

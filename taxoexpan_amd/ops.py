@@ -1543,6 +1543,77 @@ class BilinearStackedRunsFunction(torch.autograd.Function):
         return d_e1, None, dW.reshape(wshape), None
 
 
+def _plain_gemm(layout, A, lda, B, ldb, C, ldc, M, N, K):
+    """txe_gemm_plain on the route the model paths take (route 0, no k-splits), with the stream's tail-splitting scratch"""
+    tws = _tail_ws(C)
+    call("txe_gemm_plain", layout, ptr(A), lda, ptr(B), ldb, ptr(C), ldc, M, N, K, 1, 0, ptr(tws), tws.numel(), _lib.stream_ptr())
+
+
+class InBatchNCEFunction(torch.autograd.Function):
+    """The in-batch loss of a training batch: every one of the Q queries against every one of the batch's G graph vectors,
+    masked by the taxonomy (txe_inbatch_nce).  hg [G, l] (materialised), W [1, l, r], queries [Q, r] (one row per query), groups: a
+    sampler.InBatchGroups of the same Q and G.  Forward: V = q W^T, B = V hg^T (txe_gemm_plain, layout 0), exp in place for LBM
+    (txe_inbatch_exp), then the loss launch, which leaves the gradient to B in place of the scores.  Backward: d_hg = dB^T V, dV = dB hg,
+    dW = dV^T q (layouts 2, 1, 2).  No gradient to the queries.  valid_total: None, or an int64 [1] device counter that gains the
+    batch's valid (query, column) pairs.  Returns the sum-reduced fp32 loss (a 0-dim tensor)."""
+
+    @staticmethod
+    def forward(ctx, hg, W, queries, apply_exp, groups, valid_total=None):
+        _need_cuda(hg, W, queries)
+        if queries.requires_grad:
+            raise ValueError("InBatchNCEFunction: the queries are taxonomy features and get no gradient (detach them)")
+        hg, ldh = _rows(hg)
+        q, ldq = _rows(queries)
+        Wf = _f32(W).reshape(W.shape[-2], W.shape[-1])
+        (G, l), (Q, r) = hg.shape, q.shape
+        if Wf.shape != (l, r):
+            raise ValueError(f"InBatchNCEFunction: W {tuple(W.shape)} does not match hg [{G}, {l}] and queries [{Q}, {r}]")
+        if (groups.Q, groups.G) != (Q, G):
+            raise ValueError(f"InBatchNCEFunction: the groups describe {groups.Q} queries x {groups.G} columns, the batch has {Q} x {G}")
+        if groups.anchor.device != hg.device:
+            raise ValueError("InBatchNCEFunction: the groups live on another device")
+        if G < 1 or Q * G >= 2 ** 31:
+            raise ValueError(f"InBatchNCEFunction: needs G >= 1 and Q * G < 2^31, got Q = {Q}, G = {G}")
+        if valid_total is not None and not (valid_total.dtype == torch.int64 and valid_total.numel() == 1 and valid_total.device == hg.device):
+            raise ValueError("InBatchNCEFunction: valid_total is one int64 element on the batch's device")
+        loss = _empty((), hg)
+        ctx.misc = None
+        with _lib.on_device(hg.device):
+            if Q == 0:                                        # an empty sum: nothing to launch, no gradient
+                return loss.zero_()
+            V, B = _empty((Q, l), hg), _empty((Q, G), hg)
+            _plain_gemm(0, q, ldq, Wf, r, V, l, Q, l, r)
+            _plain_gemm(0, V, l, hg, ldh, B, G, Q, G, l)
+            if apply_exp:
+                call("txe_inbatch_exp", ptr(B), G, Q, G, _lib.stream_ptr())
+            wsb = pure("txe_inbatch_nce_ws_bytes", Q)
+            ws = _ws(wsb, hg)
+            call("txe_inbatch_nce", ptr(B), G, Q, G, ptr(groups.pos_col), ptr(groups.anchor), ptr(groups.qnode), ptr(groups.mask_ptr),
+                 ptr(groups.mask_idx), int(bool(apply_exp)), ptr(loss), ptr(B), G, None, ptr(valid_total), ptr(ws), wsb, _lib.stream_ptr())
+        ctx.misc = (hg, ldh, q, ldq, V, B, W.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if ctx.misc is None:
+            return None, None, None, None, None, None
+        from .loss import _scaled
+        hg, ldh, q, ldq, V, dB, wshape = ctx.misc
+        (G, l), (Q, r) = hg.shape, q.shape
+        dB = _scaled(dB, grad_loss)
+        d_hg = dW = None
+        with _lib.on_device(hg.device):
+            if ctx.needs_input_grad[0]:
+                d_hg = _empty((G, l), hg)
+                _plain_gemm(2, dB, G, V, l, d_hg, l, G, l, Q)
+            if ctx.needs_input_grad[1]:
+                dV, dW = _empty((Q, l), hg), _empty((l, r), hg)
+                _plain_gemm(1, dB, G, hg, ldh, dV, l, Q, l, G)
+                _plain_gemm(2, dV, l, q, ldq, dW, r, l, r, Q)
+                dW = dW.reshape(wshape)
+        return d_hg, dW, None, None, None, None
+
+
 def gcn_folded_graph_vector_ok(csr, cfg, params):
     """may a GCN stack hand out Z instead of hg (cfg.final = 'collapse_z')?  The output layer's bias then rides as one more weight row
     behind a column of Z that counts as 1: its input width must leave a padding column ((Kin) % 32 != 0)."""

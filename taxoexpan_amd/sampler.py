@@ -364,6 +364,83 @@ class DeviceAnchorSampler:
         return self.arrays["ptr"].cpu().numpy()
 
 
+class InBatchGroups:
+    """What the in-batch loss (loss.in_batch_info_nce) needs to know about a batch of Q queries and G egonet columns, as
+    int32 device tensors: anchor [G] = the taxonomy node of every column, qnode [Q] = every query's node, pos_col [Q] = the column of
+    every query's own positive, and node2masks as a CSR (mask_ptr [n + 1], mask_idx, rows ascending; both None: nothing is masked).
+    Column g counts for query i iff g == pos_col[i] or anchor[g] is not in the mask row of qnode[i].  A DeviceBatchLoader(in_batch=True)
+    attaches one to every batch as `g.in_batch` (views of the sampler's packed index array and of its resident mask CSR: nothing is
+    copied); from_numpy builds one from host arrays, validated."""
+
+    def __init__(self, anchor, qnode, pos_col, mask_ptr=None, mask_idx=None):
+        if (mask_ptr is None) != (mask_idx is None):
+            raise ValueError("mask_ptr and mask_idx come together")
+        for name, t in (("anchor", anchor), ("qnode", qnode), ("pos_col", pos_col), ("mask_ptr", mask_ptr), ("mask_idx", mask_idx)):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and
+                                      t.device == anchor.device):
+                raise ValueError(f"InBatchGroups: {name} must be a contiguous int32 vector on the anchors' device")
+        if qnode.numel() != pos_col.numel():
+            raise ValueError(f"InBatchGroups: one pos_col per query, got {pos_col.numel()} for {qnode.numel()} queries")
+        self.anchor, self.qnode, self.pos_col, self.mask_ptr, self.mask_idx = anchor, qnode, pos_col, mask_ptr, mask_idx
+        self.Q, self.G = int(qnode.numel()), int(anchor.numel())
+
+    device = property(lambda self: self.anchor.device)
+
+    @classmethod
+    def from_numpy(cls, anchor, qnode, pos_col, mask_ptr=None, mask_idx=None, device="cpu"):
+        """from host integer arrays.  ValueError: arrays that are not one-dimensional, another number of pos_col than of queries, a
+        pos_col outside [0, G), a negative anchor, exactly one of the mask arrays, a mask_ptr that does not start at 0, decreases or
+        ends elsewhere than at len(mask_idx), a query node outside the CSR's rows, a mask row that is not ascending."""
+        arr = lambda a: None if a is None else np.asarray(a)
+        anchor, qnode, pos_col, mask_ptr, mask_idx = (arr(a) for a in (anchor, qnode, pos_col, mask_ptr, mask_idx))
+        for name, a in (("anchor", anchor), ("qnode", qnode), ("pos_col", pos_col), ("mask_ptr", mask_ptr), ("mask_idx", mask_idx)):
+            if a is not None and (a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0)):
+                raise ValueError(f"InBatchGroups.from_numpy: {name} must be a one-dimensional integer array")
+        if (mask_ptr is None) != (mask_idx is None):
+            raise ValueError("InBatchGroups.from_numpy: mask_ptr and mask_idx come together")
+        Q, G = qnode.shape[0], anchor.shape[0]
+        if pos_col.shape[0] != Q:
+            raise ValueError(f"InBatchGroups.from_numpy: {pos_col.shape[0]} pos_col for {Q} queries")
+        if Q and (pos_col.min() < 0 or pos_col.max() >= G):
+            raise ValueError(f"InBatchGroups.from_numpy: a pos_col lies outside [0, G = {G})")
+        if G and anchor.min() < 0:
+            raise ValueError("InBatchGroups.from_numpy: a negative anchor")
+        if Q and qnode.min() < 0:
+            raise ValueError("InBatchGroups.from_numpy: a negative query node")
+        if mask_ptr is not None:
+            if mask_ptr.shape[0] < 1 or mask_ptr[0] != 0 or (np.diff(mask_ptr) < 0).any() or mask_ptr[-1] != mask_idx.shape[0]:
+                raise ValueError("InBatchGroups.from_numpy: mask_ptr must start at 0, never decrease and end at len(mask_idx)")
+            if Q and qnode.max() >= mask_ptr.shape[0] - 1:
+                raise ValueError(f"InBatchGroups.from_numpy: a query node lies outside the mask CSR's {mask_ptr.shape[0] - 1} rows")
+            if mask_idx.shape[0] > 1:
+                row_start = np.zeros(mask_idx.shape[0], dtype=bool)
+                row_start[mask_ptr[:-1][mask_ptr[:-1] < mask_idx.shape[0]]] = True
+                if ((np.diff(mask_idx.astype(np.int64)) <= 0) & ~row_start[1:]).any():
+                    raise ValueError("InBatchGroups.from_numpy: every mask row must be strictly ascending (sorted(node2masks[q]))")
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(device)
+        if mask_idx is not None and mask_idx.shape[0] == 0:
+            mask_idx = np.zeros(1, dtype=np.int32)         # (a CSR without entries: one unused element, so that its pointer is not NULL)
+        return cls(up(anchor), up(qnode), up(pos_col), up(mask_ptr), up(mask_idx))
+
+    @classmethod
+    def from_packed(cls, packed, Q, k, pos_col, mask_ptr, mask_idx):
+        """the views of a DeviceAnchorSampler batch (repeated_queries layout: anchors at packed[:B], the queries' nodes at
+        packed[2B:2B + Q], B = Q (1 + k)); pos_col = i (1 + k), made once per batch size by the loader"""
+        B = Q * (1 + k)
+        return cls(packed[:B], packed[2 * B:2 * B + Q], pos_col, mask_ptr, mask_idx)
+
+    def numpy(self):
+        """dict of the host copies (synchronises)"""
+        get = lambda t: None if t is None else t.cpu().numpy()
+        return dict(anchor=get(self.anchor), qnode=get(self.qnode), pos_col=get(self.pos_col), mask_ptr=get(self.mask_ptr),
+                    mask_idx=get(self.mask_idx))
+
+    def record_stream(self, stream):
+        """mark the batch's own views as used on `stream` (the resident mask CSR and the cached pos_col outlive every batch)"""
+        self.anchor.record_stream(stream)
+        self.qnode.record_stream(stream)
+
+
 # ---- sampling_mode 0 (validation batches of the shipped configs): every parent, then at most k negatives ---------------------------------
 
 def _check_groups(dataset):

@@ -61,11 +61,15 @@ class StepLog:
             raise ValueError("StepLog needs a capacity of at least one step")
         if self.device.type != "cuda":
             raise RuntimeError("taxoexpan_amd.trainer.StepLog lives on the GPU (no CPU path; host_step_log is the restatement)")
-        # one fp64 buffer, so that read() is ONE copy: [acc (2) | first_bad (1, as int64) | gnorm2 (capacity) | loss (capacity fp32)]
+        # one fp64 buffer, so that read() is ONE copy: [acc (2) | first_bad (1, as int64) | gnorm2 (capacity) | loss (capacity fp32) |
+        # counter (1, as int64)]
         c = self.capacity
-        self._buf = torch.zeros(3 + c + (c + 1) // 2, dtype=torch.float64, device=self.device)
+        self._buf = torch.zeros(4 + c + (c + 1) // 2, dtype=torch.float64, device=self.device)
         self._acc, self._first_bad = self._buf[0:2], self._buf[2:3].view(torch.int64)
         self._gnorm2, self._loss = self._buf[3:3 + c], self._buf[3 + c:].view(torch.float32)[:c]
+        # an int64 word the log itself never writes: a loss may add to it on the device (loss.in_batch_info_nce's valid_total); it comes
+        # back with read() and is cleared by reset()
+        self.counter = self._buf[-1:].view(torch.int64)
         self._first_bad.fill_(-1)
         self._ws, self._ws_bytes = None, 0
         self._table = None
@@ -124,11 +128,11 @@ class StepLog:
                          first_bad=self._first_bad.data_ptr() if first_bad else None, keep=(self._buf,))
 
     def read(self):
-        """the epoch's one read-back: dict(loss fp32 [n], grad_norm fp64 [n], loss_sum, n_steps, first_nonfinite (-1: none))"""
+        """the epoch's one read-back: dict(loss fp32 [n], grad_norm fp64 [n], loss_sum, n_steps, first_nonfinite (-1: none), counter)"""
         host = self._buf.cpu().numpy()
         c, n = self.capacity, self.n_recorded
         return dict(loss=host[3 + c:].view(np.float32)[:n].copy(), grad_norm=np.sqrt(host[3:3 + n]), loss_sum=float(host[0]),
-                    n_steps=int(host[1]), first_nonfinite=int(host[2:3].view(np.int64)[0]))
+                    n_steps=int(host[1]), first_nonfinite=int(host[2:3].view(np.int64)[0]), counter=int(host[-1:].view(np.int64)[0]))
 
     def reset(self):
         """clear the log for the next epoch"""
@@ -141,7 +145,8 @@ def _is_info_nce(loss_fn):
     return getattr(loss_fn, "__name__", "").startswith("info_nce")        # trainer.py:20 tests the config's loss NAME the same way
 
 
-def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None, max_grad_norm=None, freeze_on_nonfinite=False):
+def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None, max_grad_norm=None, freeze_on_nonfinite=False,
+                in_batch=False):
     """trainer.py:41-77 on the device: model.train(), then per batch zero_grad, forward, loss, backward, ONE txe_step_log launch,
     optimizer.step() -- no .item(), .cpu() or synchronize between the first batch and the last (what `loader` does to build a batch is
     its own business), then one read-back of the log.
@@ -168,10 +173,26 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         Model and optimizer are then exactly as after step s - 1 (the forward and backward passes of the later steps still ran).
     An optimizer that averages its parameters (optim.Adam(ema_decay=...)) does so inside the same optimizer launch; nothing here changes.
     A frozen run freezes the averages too: the launch that skips the update skips the average, and the discounted step counts let a
-    warm-up schedule of the decay resume where the device stopped."""
+    warm-up schedule of the decay resume where the device stopped.
+    in_batch (an addition; off: the loop is launch for launch what it was, the dict has no new key): every query is scored against EVERY
+    egonet of its batch, not only its own 1 + negative_size -- per batch `hg = encode_graph(model, g, h, pos)`, then
+    `loss.in_batch_info_nce(model.match, hg, qf.rows, g.in_batch)`, then backward, log and step as above.  The loader
+    must attach `g.in_batch` (DeviceBatchLoader(sampler="device", in_batch=True)) and the matcher must be BIM / LBM; loss_fn cannot be
+    given with it -- each a ValueError before the first optimizer step.  The dict gains mean_negatives = the valid negative columns per
+    query, averaged over the epoch: the log's int64 counter word (StepLog.counter), which the loss launches add to and which comes
+    back in the log's one read-back."""
+    if in_batch:
+        if loss_fn is not None:
+            raise ValueError("train_epoch: in_batch=True brings its own loss (loss.in_batch_info_nce); loss_fn cannot be given with it")
+        from .loss import is_bilinear_matcher
+        match = getattr(model, "match", None)
+        if not is_bilinear_matcher(match):
+            raise ValueError(f"train_epoch: in_batch=True needs a BIM / LBM matcher, the model has {type(match).__name__}")
+        if getattr(loader, "in_batch", True) is False:
+            raise ValueError("train_epoch: in_batch=True needs a loader that attaches g.in_batch (DeviceBatchLoader(in_batch=True))")
     if loss_fn is None:
         from .loss import info_nce_loss as loss_fn
-    info_nce = _is_info_nce(loss_fn)
+    info_nce = _is_info_nce(loss_fn) and not in_batch
     if info_nce and group_size is None:
         k = getattr(getattr(loader, "dataset", None), "negative_size", None)
         if k is None:
@@ -194,6 +215,10 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         if hasattr(loader, "__len__") and log.capacity < len(loader):
             raise ValueError(f"the StepLog holds {log.capacity} steps, the loader yields {len(loader)}")     # before any optimizer step
         log.reset()
+    if in_batch:
+        from .loss import in_batch_info_nce
+        from .model import encode_graph
+        valid_total, n_queries = log.counter, 0                        # (cleared with the log, read back with it)
     model.train()                                                      # trainer.py:42
     n_batches = 0
     for batch in loader:
@@ -205,14 +230,21 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         h = h.to(dev, non_blocking=True)
         qf = qf.to(dev, non_blocking=True) if torch.is_tensor(qf) else qf
         label = label.to(dev, non_blocking=True)
+        if in_batch and getattr(g, "in_batch", None) is None:
+            raise ValueError("train_epoch: in_batch=True, but a batch has no g.in_batch (DeviceBatchLoader(sampler='device', in_batch=True))")
         optimizer.zero_grad()                                          # trainer.py:50
-        prediction = model(g, h, qf)
-        if info_nce:
-            if prediction.numel() % group_size:
-                raise ValueError(f"a batch of {prediction.numel()} scores is no multiple of group_size {group_size}")
-            loss = loss_fn(prediction.reshape(-1, group_size), None)
+        if in_batch:
+            hg = encode_graph(model, g, h, g.ndata["pos"].to(dev))
+            loss = in_batch_info_nce(model.match, hg, getattr(qf, "rows", qf), g.in_batch, valid_total=valid_total)
+            n_queries += g.in_batch.Q
         else:
-            loss = loss_fn(prediction, label)
+            prediction = model(g, h, qf)
+            if info_nce:
+                if prediction.numel() % group_size:
+                    raise ValueError(f"a batch of {prediction.numel()} scores is no multiple of group_size {group_size}")
+                loss = loss_fn(prediction.reshape(-1, group_size), None)
+            else:
+                loss = loss_fn(prediction, label)
         loss.backward()                                                # trainer.py:60
         log.record(loss, params)
         if guarded:                                                    # only what was asked for is passed
@@ -225,8 +257,11 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
     rec = log.read()
     if freeze_on_nonfinite and rec["first_nonfinite"] >= 0:
         optimizer.discount_frozen_steps(n_batches - rec["first_nonfinite"])
-    return dict(loss=rec["loss_sum"] / n_batches if n_batches else float("nan"), n_batches=n_batches, losses=rec["loss"],
-                grad_norms=rec["grad_norm"], first_nonfinite=rec["first_nonfinite"])
+    out = dict(loss=rec["loss_sum"] / n_batches if n_batches else float("nan"), n_batches=n_batches, losses=rec["loss"],
+               grad_norms=rec["grad_norm"], first_nonfinite=rec["first_nonfinite"])
+    if in_batch:                                                       # (valid pairs - the positives) per query
+        out["mean_negatives"] = (rec["counter"] - n_queries) / n_queries if n_queries else float("nan")
+    return out
 
 
 class TrainingDiverged(RuntimeError):
@@ -299,7 +334,7 @@ def _checked_hard_negatives(cfg, train_loader):
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
         loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False,
-        hard_negatives=None, averaged=False):
+        hard_negatives=None, averaged=False, in_batch=False):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -338,7 +373,9 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     follow the AVERAGED model, and every checkpoint (checkpoint-epochN.pth, model_best.pth, last_finite.pth) gains "ema_state_dict", the
     model's state_dict() taken inside that context, as copies (load_averaged reads it).  "state_dict" and "optimizer" stay the raw
     weights and the full optimizer state, the average included, so `resume=` continues exactly.  Hard-negative mining keeps ranking
-    with the raw model, the one being trained: its negatives are meant to be hard for the weights that the next step updates."""
+    with the raw model, the one being trained: its negatives are meant to be hard for the weights that the next step updates.
+    in_batch=True goes to train_epoch (see there; passed only when set): the epochs train on in-batch negatives and their logs gain
+    mean_negatives; validation is unchanged, and hard negatives compose (they only change which anchors a batch holds)."""
     if averaged and not (hasattr(optimizer, "averaged_parameters") and any(g.get("ema_decay") is not None for g in optimizer.param_groups)):
         raise ValueError("fit(averaged=True) needs an optimizer with averaged_parameters() and an ema_decay in at least one parameter "
                          f"group (taxoexpan_amd.optim.Adam(ema_decay=...)); got {type(optimizer).__name__}")
@@ -377,6 +414,8 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
         guard_args["max_grad_norm"] = max_grad_norm
     if freeze_on_nonfinite:
         guard_args["freeze_on_nonfinite"] = True
+    if in_batch:
+        guard_args["in_batch"] = True
     for epoch in range(start_epoch, epochs + 1):
         mined = None
         if hard is not None and epoch >= hard["start"] and (epoch - hard["start"]) % hard["every"] == 0:
