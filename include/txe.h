@@ -579,11 +579,16 @@ int txe_gat_collapse_bwd(const struct txe_graph_batch* batch, const struct txe_g
  * the fused sweep reads its "dZ[g]" rows as Tf[zrow[g]] with dsl_g folded into the node coefficients -- d_hg may be NULL, dZ is never
  * formed.
  * | TXE_FUSED_NO_EGO_WALK: the source-side sweep does not walk egonets from registers, whatever the head count (the A/B switch).
+ * | TXE_WALK_NO_REFORM: the egonet walk (Hp == 4) loads the X rows of parents and siblings.  Without the bit it forms their feature
+ * columns again from Yp, alpha_p and the dropout seed -- bit-identical, and a quarter of the sweep's reads less -- which REQUIRES that
+ * X's columns [0, Kh) are what txe_gat_aggregate_fwd wrote for this Yp / alpha_p with out_mode 1 and act_slope (or out_mode 0 and
+ * act_slope 1), not the dropped form its nx_kp > 0 && nx_a12 == NULL call stores.  A caller that cannot vouch for that sets the bit.
  * txe_gat_fused_bwd_supported: 1 if the shape qualifies (Hp in {1,2,4}, Hp*Dp % 16 == 0, <= 128 columns behind the feature part). */
 int txe_gat_fused_bwd_supported(int Kh, int Pd, int Hp, int Dp);
 size_t txe_gat_collapse_bwd_fused_ws_bytes(int n_nodes, int n_edges, int G, int Kh, int Pd, int D, int vocab, int Hp);
 enum { TXE_FUSED_DZ = 1, TXE_FUSED_DW = 2, TXE_FUSED_SWEEP = 4, TXE_FUSED_REDUCE = 8, TXE_FUSED_ALL = 15, TXE_FUSED_DW_BESIDE = 128,
        TXE_FUSED_DZ_GIVEN = 256, TXE_FUSED_EDOT = 512, TXE_FUSED_NO_EGO_WALK = 1024 };
+enum { TXE_WALK_NO_REFORM = 2048 };    /* a `phases` bit of txe_gat_collapse_bwd_fused like the ones above: how the egonet walk gets its rows */
 struct txe_gat_fold_below {    /* the GATLayer below the folded one */
     const float* Yp; long long ld_yp; int Hp, Dp; float attn_slope_p, attn_drop_p_p; unsigned long long seed_p; const float* alpha_p;
     float* d_Yp; long long ld_dyp; int n_pad; float* dz_p;

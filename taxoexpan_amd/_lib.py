@@ -10,6 +10,7 @@ TAIL_CHAIN_BYTES = 1024        # TXE_TAIL_CHAIN_BYTES of include/txe.h
 DENSE_DX, DENSE_DW, DENSE_REDUCE, DENSE_ALL, DENSE_DX_SPLIT, PH_DEFER = 1, 2, 4, 7, 16, 64
 FUSED_DZ, FUSED_DW, FUSED_SWEEP, FUSED_REDUCE, FUSED_ALL = 1, 2, 4, 8, 15
 FUSED_DW_BESIDE, FUSED_DZ_GIVEN, FUSED_EDOT, FUSED_NO_EGO_WALK = 128, 256, 512, 1024
+WALK_NO_REFORM = 2048          # TXE_WALK_NO_REFORM: one more `phases` bit of txe_gat_collapse_bwd_fused
 FOLD_A12_READY, FOLD_HG_SPLIT = 1, 2
 STEP_LOG_CHUNK = 4096          # TXE_STEP_LOG_CHUNK: gradient elements per workgroup of txe_step_log
 

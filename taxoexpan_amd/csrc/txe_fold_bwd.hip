@@ -21,6 +21,7 @@
 #include "txe_gather.h"
 #include "txe_tail.h"
 #include "txe_fold.h"
+#include "txe_ego_row.h"
 
 namespace txe {
 
@@ -53,6 +54,9 @@ struct FusedBwdArgs {
 // staging of the folded rows, the partial rows written at the end), and a last partial round costs a whole one: on the 18 k-node
 // training batch 24 nodes make 745 workgroups = one round of 768 (141 us), 16 make 1.46 rounds (153 us), 32 three quarters of one (154 us).
 static inline int fb_nodes_per_wg(int n_nodes, int occupancy = 3) {
+#ifdef TXE_FB_NPW
+    return TXE_FB_NPW;                  // (a build for measurements: the window forced, 12..FB_NODES)
+#endif
     const int slots = occupancy * device_cu_count();
     int best = 16;
     double best_cost = 1e30;
@@ -388,7 +392,12 @@ __global__ __launch_bounds__(256) void egonet_walk_plan_kernel(const int* __rest
 #ifndef TXE_EGO_SLOTS
 #define TXE_EGO_SLOTS 1
 #endif
-template <bool MASK, int NI>
+// REFORM: the X' columns [0, F) of a parent or sibling entry are not loaded but formed again from rows the walk holds anyway -- the node's
+// own ft row, the hub's ft row (fth) and the staged coefficients alpha * dropout factor, which are the forward's, bit for bit
+// (ego_row_elem, txe_ego_row.h: the expression the forward walk wrote the row with).  Only a hub's row carries information the walk
+// does not hold.  Hub and foreign-hub entries, the tail columns [F, Kp) and everything the generic body walks load X' as before.
+// The caller vouches that X' columns [0, F) ARE leaky(aggregate(Y), act_slope), stored un-dropped (act_slope 1: no activation).
+template <bool MASK, int NI, bool REFORM = false>
 __global__ __launch_bounds__(256, (NI >= 3) ? 2 : TXE_EGO_OCC) void gat_fused_bwd_ego_kernel(const FusedBwdArgs a) {
     __shared__ int s_v[4], s_p[4], s_ni[4 * FB_NODES];                         // (the generic body's per-node table; its edge tables are not used)
     __shared__ float s_cn[4], s_g1[4], s_g2[4], s_nf[4 * FB_NODES];
@@ -609,7 +618,9 @@ __global__ __launch_bounds__(256, (NI >= 3) ? 2 : TXE_EGO_OCC) void gat_fused_bw
     };
 
     // the walk, NS entries per round trip: entry nw first if it is a foreign hub, then the positions
-    constexpr int NS = TXE_EGO_SLOTS;
+    // (REFORM: two entries per trip pay once most entries ask for two rows instead of three -- rows of 2,048 columns 101 -> 94 us with
+    //  168 VGPRs and 4 of them spilled; loading walk: two entries spilled 10-37 and lost, DESIGN 4.3.  NI >= 3 not measured: one entry)
+    constexpr int NS = (REFORM && NI <= 2) ? 2 : TXE_EGO_SLOTS;
     for (int t0 = (t_role[nw] == EGO_FOREIGN) ? -1 : 0; t0 < nw; t0 += NS) {
         // ---- every load of the two entries first (rows, masks, edge scalars), nothing in between ----
         int vv[NS], role[NS], ps[NS], ph[NS], pv[NS];
@@ -623,10 +634,23 @@ __global__ __launch_bounds__(256, (NI >= 3) ? 2 : TXE_EGO_OCC) void gat_fused_bw
             cnv[q] = uni(t_cn[t]); g1v[q] = uni(t_g1[t]); g2v[q] = uni(t_g2[t]);
             const int dzr = uni(t_dz[t]);
             cfs[q] = uni(t_coef[t][hw]); fds[q] = uni(t_fd[t][hw]); cfh[q] = uni(t_coef[t][4 + hw]); fdh2[q] = uni(t_fd[t][4 + hw]);
+            if constexpr (REFORM) {
+                // a hub's X' row only (wave-uniform branch, and the FIRST load of the entry: every load behind the merge is counted
+                // alike on both sides, so the waits for them stay exact)
+                if (role[q] == EGO_HUB || role[q] == EGO_FOREIGN) {
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) vload<4>(a.X + (long long)vv[q] * Kp + off[i], xv[q][i]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NI; ++i)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) xv[q][i][k] = 0.f;
+                }
+            }
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 vload<4>(a.Y + (long long)vv[q] * a.ld_y + off[i], ft[q][i]);
-                vload<4>(a.X + (long long)vv[q] * Kp + off[i], xv[q][i]);
+                if constexpr (!REFORM) vload<4>(a.X + (long long)vv[q] * Kp + off[i], xv[q][i]);
                 vload<4>(a.dZ + (long long)dzr * Kp + off[i], dz[q][i]);
                 mv[q][i] = fb_keep<MASK>(a.mask, a.mask_ld, vv[q], off[i]);
             }
@@ -644,6 +668,21 @@ __global__ __launch_bounds__(256, (NI >= 3) ? 2 : TXE_EGO_OCC) void gat_fused_bw
             const float fd = fds[q], coef = cfs[q];
             const float go1 = own ? g1v[q] : 0.f, go2 = own ? g2v[q] : 0.f;
             float part = 0.f;
+            if constexpr (REFORM) {
+                if (role[q] == EGO_PRE || role[q] == EGO_POST) {          // (wave-uniform) the row the forward stored, formed again
+                    const bool sib = role[q] == EGO_POST;
+                    // a sibling's in-list is [hub, self] -- or [self, hub]: one wave per node summed it in that order
+                    const bool swp = sib && ps[q] < ph[q];
+                    const float ca = swp ? cfh[q] : cfs[q], cb = swp ? cfs[q] : cfh[q];
+#pragma unroll
+                    for (int i = 0; i < NI; ++i)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const float ya = swp ? fth[i][k] : ft[q][i][k], yb = swp ? ft[q][i][k] : fth[i][k];
+                            xv[q][i][k] = ego_row_elem(ca, ya, sib, cb, yb, false, 0.f, true, a.act_slope);
+                        }
+                }
+            }
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 float w1[4], w2[4], a1[4], a2[4];
@@ -978,6 +1017,8 @@ size_t txe_gat_collapse_bwd_fused_ws_bytes(int n_nodes, int n_edges, int G, int 
 // independent weight-gradient GEMM with the sweeps on a second stream, separate calls with _DZ (dZ GEMM), _DW (dW GEMM partials: needs
 // only d_hg and Z), _SWEEP (sweeps + first reduction stage: needs DZ), _REDUCE (final reductions: needs DW and SWEEP) and the same workspace.
 // phases | TXE_FUSED_NO_EGO_WALK: the source-side sweep does not walk egonets from registers (gat_fused_bwd_kernel for every head count: the A/B switch).
+// phases | TXE_WALK_NO_REFORM: the egonet walk loads every X' row instead of forming the parents' and siblings' rows again from Yp (the
+// A/B switch -- and what a caller must say whose X' feature columns are not leaky(aggregate of Yp, act_slope), stored un-dropped).
 int txe_gat_collapse_bwd_fused(const struct txe_graph_batch* batch, const struct txe_gat_fold_layer* layer, const struct txe_gat_fold_below* below,
                                const struct txe_fold_match* match, const struct txe_gat_fold_grads* grads, const float* d_hg, long long ld_dhg,
                                float act_slope, int phases, const float* dw_main, int dw_slices, const int* walk_plan, void* chain, void* ws,
@@ -1082,18 +1123,24 @@ int txe_gat_collapse_bwd_fused(const struct txe_graph_batch* batch, const struct
             a.plan = walk_plan;
             const int nvec = F / 16, ni = (nvec + 63) / 64, nwh = 4 / Hp;
             // algorithmic bytes: read X' (own row + once per out-edge is an L2 matter), dZ, Y; write d_Y
+            // (reform: a batch of egonets has one hub per graph, and only the hubs' feature columns of X' are read)
             char name[64];
             const bool ego = Hp == 4 && !(phases & TXE_FUSED_NO_EGO_WALK);            // one head per wave: the egonet-walking variant (generic graphs inside)
+            // the walk forms the X' rows of parents and siblings again instead of reading them (REFORM): unless the caller says that X' is
+            // not the plain activated aggregate of Yp (| TXE_WALK_NO_REFORM: stored dropped, or written by something else).  Same launch name.
+            const bool reform = ego && X != nullptr && !(phases & TXE_WALK_NO_REFORM);
             if (ego) snprintf(name, sizeof(name), "gat_fused_bwd_ego_kernel<%s, %d>", mk ? "true" : "false", ni);
             else snprintf(name, sizeof(name), "gat_fused_bwd_kernel<%s, %d, %d>", mk ? "true" : "false", ni, nwh);
-            ProfScope prof(name, s, 4.0 * (n_nodes * ((double)Kp + 2.0 * F) + (double)G * Kp), 1);
+            const double x_skipped = reform ? (double)(n_nodes > G ? n_nodes - G : 0) * F : 0.0;
+            ProfScope prof(name, s, 4.0 * (n_nodes * ((double)Kp + 2.0 * F) + (double)G * Kp - x_skipped), 1);
 #define TXE_FB(M_, NI_, NW_) hipLaunchKernelGGL((gat_fused_bwd_kernel<M_, NI_, NW_>), dim3(fw.nblocks), dim3(256), (size_t)(4 * Kp + a.vocab * (Pd > 0 ? Pd : 1)) * sizeof(float), s, a)
 #define TXE_FB_NI(M_, NW_) do { if (ni == 1) TXE_FB(M_, 1, NW_); else if (ni == 2) TXE_FB(M_, 2, NW_); else if (ni == 3) TXE_FB(M_, 3, NW_); else TXE_FB(M_, 4, NW_); } while (0)
 #define TXE_FB_NW(M_) do { if (nwh == 1) TXE_FB_NI(M_, 1); else if (nwh == 2) TXE_FB_NI(M_, 2); else TXE_FB_NI(M_, 4); } while (0)
             if (ego) {
-#define TXE_FBE(M_, NI_) hipLaunchKernelGGL((gat_fused_bwd_ego_kernel<M_, NI_>), dim3(fw.nblocks), dim3(256), (size_t)(4 * Kp + a.vocab * (Pd > 0 ? Pd : 1)) * sizeof(float), s, a)
-#define TXE_FBE_NI(M_) do { if (ni == 1) TXE_FBE(M_, 1); else if (ni == 2) TXE_FBE(M_, 2); else if (ni == 3) TXE_FBE(M_, 3); else TXE_FBE(M_, 4); } while (0)
-                if (mk) TXE_FBE_NI(true); else TXE_FBE_NI(false);
+#define TXE_FBE(M_, NI_, R_) hipLaunchKernelGGL((gat_fused_bwd_ego_kernel<M_, NI_, R_>), dim3(fw.nblocks), dim3(256), (size_t)(4 * Kp + a.vocab * (Pd > 0 ? Pd : 1)) * sizeof(float), s, a)
+#define TXE_FBE_NI(M_, R_) do { if (ni == 1) TXE_FBE(M_, 1, R_); else if (ni == 2) TXE_FBE(M_, 2, R_); else if (ni == 3) TXE_FBE(M_, 3, R_); else TXE_FBE(M_, 4, R_); } while (0)
+                if (reform) { if (mk) TXE_FBE_NI(true, true); else TXE_FBE_NI(false, true); }
+                else if (mk) TXE_FBE_NI(true, false); else TXE_FBE_NI(false, false);
 #undef TXE_FBE_NI
 #undef TXE_FBE
             } else if (mk) TXE_FB_NW(true); else TXE_FB_NW(false);

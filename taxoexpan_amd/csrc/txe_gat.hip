@@ -14,6 +14,7 @@
 // and writes one row of H*D floats.  Workgroups are remapped so that one XCD (one L2) owns a contiguous
 // range of destination nodes -- the nodes of an egonet share their source rows.
 #include "txe_gather.h"
+#include "txe_ego_row.h"
 
 namespace txe {
 
@@ -666,10 +667,7 @@ __global__ __launch_bounds__(256, (NI >= 3) ? 3 : TXE_EF_OCC) void gat_aggregate
 #pragma unroll
             for (int i = 0; i < NI; ++i)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float tmp = fmaf(cr, y[i][k], (fl == 2) ? 0.f : acc[i][k]);
-                    acc[i][k] = fl ? tmp : acc[i][k];
-                }
+                for (int k = 0; k < 4; ++k) acc[i][k] = ego_run_acc(cr, y[i][k], fl, acc[i][k]);
         }
         auto step = [&](const int t, const float (&cur)[NI][4], const unsigned (&kbc)[NI], const float txc, const unsigned tkc) {
             const int v = u0 + t;
@@ -684,12 +682,10 @@ __global__ __launch_bounds__(256, (NI >= 3) ? 3 : TXE_EF_OCC) void gat_aggregate
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const float y = TAB ? cur[i][k] + tv[k] : cur[i][k];
-                    const float base = (kind == EF_HUBREF) ? fmaf(ch, hub[i][k], 0.f) : (hasrun ? acc[i][k] : 0.f);
-                    float r = fmaf(cs, y, base);
-                    const float tmp = fmaf(cr, y, (fl == 2) ? 0.f : acc[i][k]);
-                    acc[i][k] = fl ? tmp : acc[i][k];
+                    // (txe_ego_row.h: the fused backward walk forms the same element again instead of reading it back)
+                    float r = ego_row_elem(cs, y, kind == EF_HUBREF, ch, hub[i][k], hasrun != 0, acc[i][k], a.out_mode == 1, a.act_slope);
+                    acc[i][k] = ego_run_acc(cr, y, fl, acc[i][k]);
                     hub[i][k] = ish ? y : hub[i][k];
-                    if (a.out_mode == 1) r = leaky(r, a.act_slope);
                     if constexpr (NX == 3) r = ((kbc[i] >> k) & 1u) ? r * a.nx.scale : 0.f;
                     res[k] = r;
                 }

@@ -58,6 +58,7 @@ _FWD_SWEEP = 0              # txe_gat_aggregate_fwd's npw argument (0 = chosen f
 _NO_VIRTUAL_X = False       # a first layer's input X = dropout([h | Emb[pos]]) is written by the preparation launch and read back by the packs
 _NO_WALK_PLAN = False       # the egonet-walking backward sweep works the graphs' shapes out of the CSR arrays in every workgroup (no per-batch plan)
 _NO_EGO_WALK = False        # the forward sweep runs one wave per node and the fused backward sweep fetches X'[v] per out-edge, instead of walking egonets
+_NO_REFORM_X = False        # the egonet-walking backward sweep loads the X' rows of parents and siblings instead of forming them again from Y
 _I32_MEMO = {}       # id(source tensor) -> (weakref, version, device, int32 copy): `pos` is converted once per batch, not once per module
 
 
@@ -754,7 +755,12 @@ def _gat_collapse_bwd_fused(csr, st, sp, rpos, pw, vocab, attn_p, attn_slope, d_
     # one set of descriptors for every call of this backward pass: the calls differ in `phases` alone
     args = (_lib.ref(batch), _lib.ref(layer), _lib.ref(below), _lib.ref(match), _lib.ref(grads), ptr(d_hg), ld, act_slope if act_slope else 1.0)
     rest = (ptr(lk.part) if lk.S > 0 else None, lk.S, ptr(plan), chain.ptr if chain is not None else None, ptr(ws), wsb)
-    always = (_lib.FUSED_EDOT if edot else 0) | (_lib.FUSED_NO_EGO_WALK if _NO_EGO_WALK else 0)
+    # the walk may form the parents' and siblings' X' rows again only where X' IS the activated aggregate of the layer below, stored
+    # un-dropped (the folded layer's input always is un-dropped: _x_dropped_ok; out_mode 1 <=> an activation between the layers)
+    reform = sp.H == 4 and not _NO_EGO_WALK and not _NO_REFORM_X and act_slope is not None and not st.x_dropped and st.X is not None
+    note_route("bwd_walk", "reform" if reform else ("load" if sp.H == 4 and not _NO_EGO_WALK else "edges"))
+    always = ((_lib.FUSED_EDOT if edot else 0) | (_lib.FUSED_NO_EGO_WALK if _NO_EGO_WALK else 0)
+              | (0 if reform else _lib.WALK_NO_REFORM))
 
     def run(phases):
         call("txe_gat_collapse_bwd_fused", *args, phases | always, *rest, _lib.stream_ptr())

@@ -68,4 +68,13 @@ else:
     for i in range(steps):
         bench.train_step(model, opt, batches[i % 2], target, 1)
     torch.cuda.synchronize()
+    # TXE_PROF_AB = ops._NO_REFORM_X (any switch of the package): the same steps once more with it set, in the same pass -- where the two
+    # routes launch kernels of different names (template arguments), one counter pass shows both
+    if os.environ.get("TXE_PROF_AB"):
+        import importlib
+        mod_name, attr = os.environ["TXE_PROF_AB"].rsplit(".", 1)
+        setattr(importlib.import_module("taxoexpan_amd." + mod_name), attr, True)
+        for i in range(steps):
+            bench.train_step(model, opt, batches[i % 2], target, 1)
+        torch.cuda.synchronize()
     print("N", [b["n_nodes"] for b in batches], "E", [b["n_edges"] for b in batches])
