@@ -695,6 +695,23 @@ int txe_group_rank(const float* score, const void* labels, int label_bytes, int 
  * acc[n_which] += n_groups, acc[n_which + 1] += n_pos.  TXE_ERR_ARG: a NULL pointer, n_which outside [1, 16], an id above 6. */
 int txe_group_metrics(const int* ranks, const int* pos_off, const int* counts, unsigned long long which, int n_which, double* acc, void* stream);
 
+/* ---- taxonomy-aware evaluation (taxoexpan_amd/taxometric.py): Wu & Palmer inputs and error relations of predicted parents,
+ * one launch.  The taxonomy index of n_nodes nodes, built and validated on the host and trusted here: depth [n_nodes] = 1 for a node
+ * without parents, else 1 + the maximum depth of its parents; anc_ptr [n_nodes + 1] / anc_idx = per node the node itself and everything
+ * reachable upward, ascending by id; par_ptr [n_nodes + 1] / par_idx = the direct parents.  lca_depth(a, b) = the maximum depth over
+ * anc(a) & anc(b), 0 when they share nothing.  For slot (q, r), q < Q, r < K: a = pred[q K + r], the golds of q are
+ * gold_idx[gold_off[q] .. gold_off[q + 1]) (offsets clamped to [0, n_gold]; a gold outside [0, n_nodes) is skipped).  Among them j* =
+ * the one with the largest 2 lca_depth(a, g_j) / (depth a + depth g_j), compared exactly as 64-bit cross products; ties by the smaller
+ * relation code, then the smaller j.  Written per slot: lca_depth, best_gold = j* (the position in q's list) and relation of a to that
+ * gold, the first that holds of 0 EXACT a == b, 1 ANCESTOR a in anc(b), 2 DESCENDANT b in anc(a), 3 SIBLING a direct parent in common,
+ * 4 RELATED lca_depth > 0, 5 UNRELATED.  a outside [0, n_nodes) or no usable gold: lca_depth 0, best_gold -1, relation 6 (NONE).  No id
+ * of pred or gold_idx is used as an address before it is compared with n_nodes.  Every output element has one writer; no atomics, no
+ * floating point: the same inputs give the same bits.
+ * TXE_ERR_ARG (before any launch): a NULL pointer, K < 1, Q < 0, n_nodes < 0, n_gold < 0, Q K >= 2^31.  Q == 0: TXE_OK, no launch. */
+int txe_taxo_slots(const int* anc_ptr, const int* anc_idx, const int* depth, const int* par_ptr, const int* par_idx, int n_nodes,
+                   const int* pred, int Q, int K, const int* gold_off, const int* gold_idx, int n_gold, int* lca_depth, int* best_gold,
+                   int* relation, void* stream);
+
 /* ---- optional per-kernel timing (debug / bench): HIP events on the launch stream around every kernel launch, with the
  * algorithmic work (flops or compulsory bytes) its launcher attributes to it.  Global state (see the conventions at the top); off by
  * default.  txe_profile_get synchronises on record i's events. */

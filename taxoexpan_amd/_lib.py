@@ -144,6 +144,7 @@ SIGNATURES = {
     "txe_group_rank_ws_bytes": (SZ, [I]),
     "txe_group_rank": (I, [P, P, I, I, I, P, P, P, P, SZ, P]),
     "txe_group_metrics": (I, [P, P, P, U64, I, P, P]),
+    "txe_taxo_slots": (I, [P, P, P, P, P, I, P, I, I, P, P, I, P, P, P, P]),
     "txe_row_normalize": (I, [P, L, I, I, P, L, P]),
     "txe_select_k_ws_bytes": (SZ, [I, I]),
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),

@@ -193,10 +193,12 @@ def _best_retrieved(score, ret_dst, ridx, topk, larger_is_better):
     return torch.where(idx == empty, torch.full_like(idx, -1), idx)
 
 
-def _case_rows(dataset, queries, pos_off, ranks, top, metric_names):
+def _case_rows(dataset, queries, pos_off, ranks, top, metric_names, per_query_values=None):
     """the case-study table of test_fast.py:112-147: per test query its name, true parents, predicted top-5 parents and every
-    metric evaluated on that query's ranks alone (`metric([ranks])`, model/metric.py:62-90), as strings"""
+    metric evaluated on that query's ranks alone (`metric([ranks])`, model/metric.py:62-90), as strings.
+    per_query_values: {name: one value per query} for the columns that are not functions of the ranks ("wu_palmer")"""
     r = ranks.cpu().to(torch.float64).numpy()
+    extra = per_query_values or {}
     per_query = {
         "macro_mr": lambda x: float(x.mean()), "micro_mr": lambda x: float(x.mean()),
         "hit_at_1": lambda x: float(1.0 * np.sum(x <= 1) / len(x)), "hit_at_3": lambda x: float(1.0 * np.sum(x <= 3) / len(x)),
@@ -207,12 +209,28 @@ def _case_rows(dataset, queries, pos_off, ranks, top, metric_names):
     for i, q in enumerate(queries):
         x = r[pos_off[i]:pos_off[i + 1]]
         rows.append([vocab[q], ", ".join(vocab[p] for p in dataset.node2parents[q]), ", ".join(vocab[p] for p in top[i])] +
-                    [str(per_query[m](x)) for m in metric_names])
+                    [str(float(extra[m][i])) if m in extra else str(per_query[m](x)) for m in metric_names])
     return rows
 
 
+def _taxonomic(index_dev, best, pos_off, gold_idx, Q):
+    """the taxonomy-aware evaluation of the best lists `best` [Q, K] (node ids, -1 = no prediction) against the gold parents
+    `gold_idx` under `pos_off`: (scalar metrics, dict of the [Q, K] device tensors)"""
+    from . import taxometric
+    dev = index_dev.device
+    if Q == 0 or best.shape[1] == 0:
+        empty = torch.zeros((Q, 0), dtype=torch.int32, device=dev)
+        return taxometric.summarize(empty, empty.to(torch.float64)), dict(pred=empty, lca_depth=empty, best_gold=empty, relation=empty,
+                                                                           wu_palmer=empty.to(torch.float64))
+    pred = best.to(torch.int32).contiguous()
+    out = taxometric.taxonomic_slots(index_dev, pred, pos_off, gold_idx)
+    node = taxometric.best_gold_nodes(out["best_gold"], pos_off, gold_idx)
+    wup = taxometric.wu_palmer(index_dev, pred, node, out["lca_depth"])
+    return taxometric.summarize(out["relation"], wup), dict(pred=pred, wu_palmer=wup, **out)
+
+
 def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0, batch_size=-1, case=None, metric_names=CASE_METRICS,
-             topk=5, retrieve=None, nll=False):
+             topk=5, retrieve=None, nll=False, taxonomic=False, taxonomy_index=None):
     """dataset: taxoexpan_amd.dataset.MaskedGraphDataset in 'validation' or 'test' mode.  Returns (metrics dict, ranks int32
     [n_positives], pos_off [Q+1], queries list).  Queries whose true parents are not candidate positions are skipped, like the
     reference's rearrange() would fail on them.
@@ -236,6 +254,17 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     the positives the ranks were counted against.  Non-finite values propagate: a NaN or +-Inf score of a positive or in a query's row
     makes that query's term, and so the mean, NaN or +-Inf.  Not with retrieve=k (ValueError before any launch): a partition over a
     retrieved subset is not the likelihood.  With nll=False the dict, the ranks and the offsets are what they were without it.
+    taxonomic: truthy (True, or a dict -- an empty one too) = also judge the best `topk` list of every query (the list `case` shows:
+    _best_parents, or _best_retrieved with retrieve=k, computed once for both) on the masked taxonomy `dataset.graph.pred`
+    (taxometric.py; one more launch, csrc/txe_taxometric.hip).  Gold = the query's true parents among the candidates, the
+    ones the ranks are counted for.  The metrics dict gains wu_palmer (mean over queries of Wu & Palmer similarity between the first
+    prediction and the gold parent nearest to it), wu_palmer_at_k (the best value in the list), taxonomic_k (the list's length) and
+    rel_exact / rel_ancestor / rel_descendant / rel_sibling / rel_related / rel_unrelated / rel_none: the shares of queries by the first
+    prediction's relation to that gold (too general, too specific, ...; rel_none: no prediction, an empty retrieved slot).  A dict is
+    also filled with the [Q, K] device tensors pred (node ids), lca_depth, best_gold, relation, wu_palmer.  taxonomy_index: a
+    taxometric.TaxonomyIndex of that taxonomy (or its .to(device)) to reuse; default TaxonomyIndex.from_dataset(dataset).  "wu_palmer"
+    in `metric_names` adds the first prediction's value as a per-query column of the case study (ValueError before any launch without
+    `taxonomic`).  Every other metric, the ranks and the offsets are bit-equal to a call without it.
     Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): evaluate(model, ...)` evaluates the averaged
     model -- the parameters are the averages inside the context; or load a checkpoint's with trainer.load_averaged."""
     device = torch.device(device)
@@ -243,6 +272,12 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
         if nll:
             raise ValueError("evaluate: nll=True scores every candidate; with retrieve=k the partition over a retrieved subset is not the likelihood")
         retrieve = _retrieve_args(retrieve, None, None)[0]
+    want_taxo = isinstance(taxonomic, dict) or bool(taxonomic)
+    if case is not None and "wu_palmer" in metric_names and not want_taxo:
+        raise ValueError('evaluate: the "wu_palmer" column of the case study needs taxonomic=True')
+    if want_taxo:
+        from .taxometric import TaxonomyIndex
+        tindex = (taxonomy_index if taxonomy_index is not None else TaxonomyIndex.from_dataset(dataset)).to(device)
     cand = sorted(dataset.all_positions)                                    # test_fast.py:93
     index = {a: i for i, a in enumerate(cand)}
     dtax = dataset.device_taxonomy(device)
@@ -277,16 +312,28 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
                 ranks = _device_group_ranks(score, label, 1 if larger_is_better else 0)[0][:len(pos_idx)]
             else:
                 ranks = torch.zeros(0, dtype=torch.int32, device=device)
-        if case is not None:                                               # test_fast.py:112-147
+        if case is not None or want_taxo:                                  # the best `topk` list, once for both
             cand_ids = torch.as_tensor(np.asarray(cand, dtype=np.int64), device=device)
             if retrieve is None:
-                top = _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock).cpu().tolist()
+                best = _best_parents(model, hg, qf, cand_ids, topk, larger_is_better, qblock)
             elif queries:
-                best = _best_retrieved(score, ret_dst, ridx, topk, larger_is_better).cpu().tolist()
-                top = [[cand[i] for i in row if i >= 0] for row in best]
+                best = _best_retrieved(score, ret_dst, ridx, topk, larger_is_better)      # candidate rows, -1 = an empty slot
             else:
-                top = []
-            rows = _case_rows(dataset, queries, pos_off, ranks, top, metric_names)
+                best = torch.zeros((0, 0), dtype=torch.int32, device=device)
+        if want_taxo:
+            nodes = best
+            if retrieve is not None and best.numel():
+                nodes = torch.where(best >= 0, cand_ids[best.long().clamp(min=0)], torch.full_like(best, -1, dtype=torch.int64))
+            taxo_metrics, taxo_tensors = _taxonomic(tindex, nodes, pos_off, np.asarray(cand, dtype=np.int64)[pos_idx], len(queries))
+            if isinstance(taxonomic, dict):
+                taxonomic.update(taxo_tensors)
+        if case is not None:                                               # test_fast.py:112-147
+            top = best.cpu().tolist() if retrieve is None else [[cand[i] for i in row if i >= 0] for row in best.cpu().tolist()]
+            per_query_values = None
+            if "wu_palmer" in metric_names:
+                w = taxo_tensors["wu_palmer"]
+                per_query_values = {"wu_palmer": w[:, 0].cpu().tolist() if w.shape[1] else [float("nan")] * len(queries)}
+            rows = _case_rows(dataset, queries, pos_off, ranks, top, metric_names, per_query_values)
             if isinstance(case, list):
                 case.extend(rows)
             else:
@@ -304,6 +351,8 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
         metrics["n_retrieved"] = retrieve
     if nll:
         metrics["nll"] = nll_value
+    if want_taxo:
+        metrics.update(taxo_metrics)
     return metrics, ranks, pos_off, queries
 
 
