@@ -860,6 +860,50 @@ size_t txe_step_log_ws_bytes(int n_chunks);
 int txe_step_log(const float* loss, int n_tensors, const float* const* grads, const long long* numel, long long step, long long capacity,
                  float* loss_log, double* gnorm2_log, double* acc, long long* first_bad, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the term-embedding table as a trainable input (csrc/txe_rowgrad.hip; an addition: the reference freezes its embeddings).
+ * A batch reads the table through two gathers -- ids_a [n_a], the batch's `_id` (x = features[_id]), and ids_b [n_b], the distinct query
+ * ids -- and backward leaves one gradient row per occurrence: d_a [n_a][ld_a >= d], d_b [n_b][ld_b >= d].  Occurrence i < n_a is a's
+ * i-th, occurrence n_a + j is b's j-th.  Either side may be empty.
+ *
+ * txe_rowgrad_group sorts the occurrences by table row -- one STABLE radix sort over the ceil(log2(n_rows + 1)) key bits, so within a
+ * row the occurrence indices ascend, all of a's before b's -- and lists the segments.  An id outside [0, n_rows) is given the key n_rows
+ * before anything is addressed with it: it forms the last segment, which nothing reads; it is never an error.  ws afterwards, as int32
+ * words, e = the smallest multiple of 64 >= max(n_a + n_b, 1):
+ *   [0]                    n_seg, the number of segments (the dropped ids' segment included)
+ *   [64, 64 + n)           rows: the sorted keys              [64 + e, ...)   occ: the occurrence indices in sorted order
+ *   [64 + 2e, ... + n_seg) heads: the sorted position at which segment s begins (ascending; segment s ends where s + 1 begins, the last at n)
+ * and scratch behind.  n_a + n_b == 0: TXE_OK, nothing launched, ws not looked at.
+ *
+ * txe_sparse_adam_rows: for every row that occurs (and whose trainable byte, if the array is given, is not 0) the gradient rows of its
+ * occurrences are summed in fp32 in an order that depends on the segment's length L alone,
+ *   L <= 64:  s = g_0; s = s + g_k (k = 1 .. L-1)
+ *   L >  64:  c = ceil(L / 16); the slices [j c, min(L, (j+1) c)) are summed as above into p_j; s = p_0; s = s + p_j (j = 1 .. ceil(L / c) - 1)
+ * and txe_adam_step's update with weight_decay 0 and `step` (the GLOBAL count of this update, >= 1) is applied to that row of weight,
+ * exp_avg, exp_avg_sq and max_exp_avg_sq (NULL: plain Adam), all [n_rows][ld_w >= d]: the same expression with the same fma placement,
+ * element for element.  Rows that do not occur are neither read nor written (lazy Adam: their moments do not decay); there is no
+ * weight_decay argument because a decay applied only to the rows of a batch would be another regulariser than the dense one.  One
+ * writer per table element, no floating-point atomics: two calls on the same inputs give the same bytes.  ws is what txe_rowgrad_group
+ * left for the same ids, n_a, n_b and n_rows, enqueued earlier on the same stream.  first_bad has the meaning and the ORDERING CONTRACT
+ * of txe_adam_step_guarded: *first_bad >= 0 and no thread loads or stores anything.  Accesses are 16 bytes per lane where every pointer
+ * is 16-byte aligned and every pitch a multiple of 4, 8 bytes where 8 and 2 hold, single elements otherwise.
+ * TXE_ERR_ARG with nothing launched (both entry points, as far as they have the argument): a negative count, n_a + n_b >= 2^31, d < 1,
+ * a NULL ids / gradient pointer of a non-empty side, a pitch below d, a NULL weight / exp_avg / exp_avg_sq, step < 1, a beta outside
+ * [0, 1), and with n_a + n_b > 0 a NULL ws or ws_bytes < txe_rowgrad_ws_bytes(n_a, n_b).  The scratch part of that size is asked of the
+ * sort and select library once per n; a query that fails makes txe_rowgrad_ws_bytes 0 and the two entry points TXE_ERR_LAUNCH (on a host
+ * without a GPU, where nothing can be launched and only these checks run, the scratch counts as 0: a size holds for the machine it was
+ * asked on). */
+/* txe_rows_run_sum: the backward of ops.RepeatedRows.dense() when the distinct query rows ask for a gradient: dst [U][ld_dst >= r], row
+ * u = src[run_off[u]] + src[run_off[u] + 1] + ... + src[run_off[u+1] - 1] of src [G][ld_src >= r], fp32, left to right (an empty run
+ * gives 0; offsets are clamped to [0, G]) -- no atomics, the same bytes every time, where torch's index_add_ of repeat_interleave's
+ * backward promises no order.  TXE_ERR_ARG: a negative count, r < 1, a pitch below r, a NULL pointer with U > 0.  U == 0: no launch. */
+int txe_rows_run_sum(const float* src, long long ld_src, const int* run_off, int U, int G, int r, float* dst, long long ld_dst, void* stream);
+size_t txe_rowgrad_ws_bytes(int n_a, int n_b);
+int txe_rowgrad_group(const int* ids_a, int n_a, const int* ids_b, int n_b, int n_rows, void* ws, size_t ws_bytes, void* stream);
+int txe_sparse_adam_rows(float* weight, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, long long ld_w, int n_rows, int d,
+                         const float* d_a, long long ld_a, int n_a, const float* d_b, long long ld_b, int n_b, const void* ws,
+                         size_t ws_bytes, const unsigned char* trainable, double lr, double beta1, double beta2, double eps,
+                         long long step, const long long* first_bad, void* stream);
+
 /* ---- fp32 products on the bf16 matrix pipe (replaces the fp32-MFMA route of model_zoo.py:83 `self.fc(...)` for the first
  * layer's projection).  A packed operand holds every fp32 element as the EXACT sum of three bf16 numbers (three planes, stored as 1-KB
  * MFMA fragments: csrc/txe_gemm_split.h); txe_gemm_nt_split forms C [M][N] = A [M][K] B[N][K]^T from six of the nine plane products with

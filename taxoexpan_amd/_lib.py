@@ -162,6 +162,10 @@ SIGNATURES = {
     "txe_tensor_swap": (I, [I, P, P, P, P]),
     "txe_step_log_ws_bytes": (SZ, [I]),
     "txe_step_log": (I, [P, I, P, P, L, L, P, P, P, P, P, SZ, P]),
+    "txe_rows_run_sum": (I, [P, L, P, I, I, I, P, L, P]),
+    "txe_rowgrad_ws_bytes": (SZ, [I, I]),
+    "txe_rowgrad_group": (I, [P, I, P, I, I, P, SZ, P]),
+    "txe_sparse_adam_rows": (I, [P, P, P, P, L, I, I, P, L, I, P, L, I, P, SZ, P, D, D, D, D, L, P, P]),
     "txe_dropout_uniform_host": (F, [U64, U64]),
     "txe_dropout_mask_word_host": (C.c_uint, [U64, U64, F]),
     "txe_profile_enable": (I, [I]),

@@ -6,6 +6,7 @@
 // The same launch can keep an exponential moving average of the parameters (txe_adam_step_ema: two more streams), and
 // tensor_swap_kernel exchanges the parameters with those averages in one launch of the same shape (txe_tensor_swap).
 #include "txe_common.h"
+#include "txe_adam.h"          // AdamScalars, adam_scalars, adam_one: the update itself, shared with txe_rowgrad.hip
 
 #include <math.h>
 
@@ -25,10 +26,6 @@ struct AdamTable {
     int count;
 };
 
-struct AdamScalars {
-    float one_minus_b1, b2, one_minus_b2, eps, wd, step_size, bc2_sqrt;
-};
-
 // The averaged weights of txe_adam_step_ema: a seventh pointer table beside AdamTable's (same order of tensors) and 1 - decay of this step.
 // Only the EMA kernels take it; adam_kernel / adam_guarded_kernel have the arguments they had.
 struct AdamEma {
@@ -44,20 +41,6 @@ struct AdamGuard {
     const double* gnorm2;           // the squared global L2 norm of the gradients: every g is scaled by min(1, max_norm / (sqrt(.) + 1e-6))
     double max_grad_norm;
 };
-
-// The products that hipcc contracts under its default -ffp-contract=fast are spelled as fmaf here, so that the arithmetic is a property
-// of the source (optim.host_guarded_adam restates it operation for operation): m = fma(1-b1, g - m, m), v = fma(g, (1-b2) g, b2 v).
-template <bool GUARD>
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float& vm, bool ams, const AdamScalars& c, float coef) {
-    if (GUARD) g *= coef;                                   // coef == 1: g unchanged, bit for bit
-    g = fmaf(c.wd, p, g);                                   // wd == 0: g unchanged
-    m = fmaf(c.one_minus_b1, g - m, m);                     // lerp(m, g, 1 - beta1)
-    v = fmaf(g, c.one_minus_b2 * g, c.b2 * v);
-    float d;
-    if (ams) { vm = fmaxf(vm, v); d = sqrtf(vm) / c.bc2_sqrt + c.eps; }
-    else d = sqrtf(v) / c.bc2_sqrt + c.eps;
-    p -= c.step_size * m / d;
-}
 
 // e = lerp(e, p_new, 1 - decay) in the form m has: one subtraction, one fma (optim.host_ema_update restates it); p_new is the fp32 value
 // that the same thread stores
@@ -198,15 +181,7 @@ int adam_step(int n_tensors, float* const* params, const float* const* grads, fl
               long long step, const AdamGuard* guard, void* stream, float* const* ema = nullptr, double ema_decay = 0.0) {
     if (n_tensors < 0 || step < 1 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel))) return TXE_ERR_ARG;
     if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return TXE_ERR_ARG;
-    AdamScalars c;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    c.one_minus_b1 = (float)(1.0 - beta1);
-    c.b2 = (float)beta2;
-    c.one_minus_b2 = (float)(1.0 - beta2);
-    c.eps = (float)eps;
-    c.wd = (float)weight_decay;
-    c.step_size = (float)(lr / bc1);
-    c.bc2_sqrt = (float)sqrt(bc2);
+    const AdamScalars c = adam_scalars(lr, beta1, beta2, eps, weight_decay, step);
     const bool ams = max_exp_avg_sq != nullptr;
     AdamEma E;
     E.one_minus_d = (float)(1.0 - ema_decay);

@@ -150,18 +150,30 @@ def begin_device_batch(dtax, anchors, exclude, query_ids, expand_factor=50, seed
     return dict(job=job, packed=packed, B=B, side=side, dev=dev, n_runs=n_runs if repeated_queries else None)
 
 
-def finish_device_batch(pending, features):
+def finish_device_batch(pending, features, table=None):
     """Second half of build_device_batch: waits for the node count of the batch begun earlier (the one host synchronisation of the
     construction; behind work enqueued a whole step ago it returns at once), fills the node table and both CSR views and gathers the
     node / query features on the builder's stream; the CURRENT stream is made to wait for the finished batch, and every tensor of the
-    batch is marked as used on it (caching-allocator safety).  Returns dict(g, x, pos, qf, n_nodes, n_edges)."""
+    batch is marked as used on it (caching-allocator safety).  Returns dict(g, x, pos, qf, n_nodes, n_edges).
+    table (a feature_table.FeatureTable whose weight is `features`; needs repeated_queries): the table changes between batches, so the
+    builder's stream waits for table.updated -- the event recorded behind the table's last step -- after the node table and the CSR
+    views are filled and before the two gathers; the batch's rows are then the table after that step.  The graph gains g.query_ids,
+    the int32 [U] ids of the gathered query rows (a view of the packed array)."""
     from .graph import device_egonet_finish
     side, dev, packed, B = pending["side"], pending["dev"], pending["packed"], pending["B"]
     main = torch.cuda.current_stream(dev)
     with torch.cuda.stream(side):
-        g = device_egonet_finish(pending["job"], with_features=True)
-        x = g.ndata.pop("x")
         U = pending["n_runs"]
+        if table is None:
+            g = device_egonet_finish(pending["job"], with_features=True)
+            x = g.ndata.pop("x")
+        else:
+            if U is None:
+                raise ValueError("a feature table needs repeated_queries=True (its query-side gradient is taken per distinct row)")
+            g = device_egonet_finish(pending["job"], with_features=False)
+            side.wait_event(table.updated)
+            x = features.index_select(0, g.ndata["_id"].long())
+            g.query_ids = packed[2 * B:2 * B + U]
         if U is None:
             qt = qf = features.index_select(0, packed[2 * B:3 * B])
         else:                                                     # only the distinct query rows are gathered
@@ -215,12 +227,18 @@ class DeviceBatchLoader:
     draws every parent and at most negative_size negatives per query, labels an int64 device tensor.  The batch size B is then known on
     the device only, so three batches are in flight: each next() after the first finishes batch b (its node count, read back one next()
     ago), begins the egonet count of batch b+1 (its B, read back one next() ago) and samples batch b+2 -- no next() waits on work it
-    enqueued itself."""
+    enqueued itself.
+    feature_table (a feature_table.FeatureTable; needs repeated_queries=True, ValueError otherwise; default None: nothing changes): the
+    loader gathers from table.weight, which the table's step rewrites between batches.  Batch b+1 is still BEGUN (sampled, uploaded, its
+    node counts launched) while step b runs; its two gathers wait on the side stream for table.updated, so its rows are the table after
+    step b (finish_device_batch).  Every graph gains g.query_ids, the int32 [U] ids of the distinct query rows."""
 
     def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host",
-                 hard_negatives=None, hard_slots=0, in_batch=False):
+                 hard_negatives=None, hard_slots=0, in_batch=False, feature_table=None):
         if sampler not in ("host", "device"):
             raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
+        if feature_table is not None and not repeated_queries:
+            raise ValueError("feature_table needs repeated_queries=True (the table's query-side gradient is taken per distinct query row)")
         if in_batch and not (sampler == "device" and dataset.sampling_mode == 1 and repeated_queries):
             raise ValueError("in_batch=True needs sampler='device', a sampling_mode 1 dataset and repeated_queries=True (the in-batch "
                              "groups are views of the device sampler's index array)")
@@ -230,7 +248,15 @@ class DeviceBatchLoader:
         self.repeated_queries = bool(repeated_queries)
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         self.shuffle, self.seed, self.drop_last = shuffle, int(seed), drop_last
-        self.dtax = dataset.device_taxonomy(self.device)
+        self.feature_table = feature_table
+        if feature_table is None:
+            self.dtax = dataset.device_taxonomy(self.device)
+        else:                                                     # the table's storage IS the resident feature table
+            dev = self.device if self.device.index is not None else torch.device(self.device.type, torch.cuda.current_device())
+            if feature_table.device != dev or tuple(feature_table.weight.shape) != tuple(dataset.node_features.shape):
+                raise ValueError("feature_table lives on another device or has another shape than the dataset's feature table")
+            self.dtax = feature_table.dtax if feature_table.dataset is dataset else dataset.device_taxonomy(self.device)
+            self.dtax.features = feature_table.weight
         self.features = self.dtax.features
         self._side = torch.cuda.Stream(device=self.device)
         self.sampler = None
@@ -282,7 +308,7 @@ class DeviceBatchLoader:
         nxt = begin(0) if len(self) else None
         for b in range(len(self)):
             label, pending = nxt
-            batch = finish_device_batch(pending, self.features)
+            batch = finish_device_batch(pending, self.features, self.feature_table)
             nxt = begin(b + 1) if b + 1 < len(self) else None
             yield batch["g"], batch["x"], batch["qf"], torch.as_tensor(label).to(self.device, non_blocking=True)
 
@@ -319,7 +345,7 @@ class DeviceBatchLoader:
             nxt = begin(0) if len(self) else None
             for b in range(len(self)):
                 Q, pending = nxt
-                batch = finish_device_batch(pending, self.features)
+                batch = finish_device_batch(pending, self.features, self.feature_table)
                 nxt = begin(b + 1) if b + 1 < len(self) else None
                 if self.in_batch:
                     batch["g"].in_batch = self._in_batch_groups(pending["packed"], Q)
@@ -338,7 +364,7 @@ class DeviceBatchLoader:
         nxt = begin(0, sampled.pop(0)) if nb else None
         for b in range(nb):
             pending, labels = nxt
-            batch = finish_device_batch(pending, self.features)
+            batch = finish_device_batch(pending, self.features, self.feature_table)
             if self._side is not main:
                 labels.record_stream(main)
             nxt = begin(b + 1, sampled.pop(0)) if b + 1 < nb else None

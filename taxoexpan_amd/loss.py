@@ -87,7 +87,7 @@ def is_bilinear_matcher(match):
     return hasattr(match, "W") and hasattr(match, "apply_exp")
 
 
-def in_batch_info_nce(match, hg, queries, groups, valid_total=None):
+def in_batch_info_nce(match, hg, queries, groups, valid_total=None, query_grad=False):
     """The in-batch loss of one training batch: every query against EVERY graph vector of the batch, not only its own
     1 + negative_size -- the other queries' egonets are negatives whose encoder work is already paid -- without the columns the taxonomy
     forbids (sampler.InBatchGroups: an anchor in node2masks[query] is the query's other parent, a sibling's positive or a descendant).
@@ -95,7 +95,8 @@ def in_batch_info_nce(match, hg, queries, groups, valid_total=None):
     model(g, h, qf).  hg [G, l]: the graph vectors, e.g. encode_graph's (a DeferredGraphVector is materialised: the folded output layer
     never forms the hg this product needs).  queries [Q, r]: one row per query (a batch's `qf.rows`; an ops.RepeatedRows gives them).
     valid_total: None, or an int64 [1] device counter that gains the batch's valid pairs (train_epoch's mean_negatives).
-    Returns the sum-reduced loss as a LossTensor; gradients reach hg and match.W, not the queries."""
+    Returns the sum-reduced loss as a LossTensor; gradients reach hg and match.W, not the queries -- query rows that ask for a gradient
+    are refused (ValueError) unless query_grad=True, which train_epoch passes when a feature_table.FeatureTable trains them."""
     from . import ops
     from .model_zoo import _graph_vector
     if not is_bilinear_matcher(match):
@@ -107,7 +108,8 @@ def in_batch_info_nce(match, hg, queries, groups, valid_total=None):
         raise ValueError("in_batch_info_nce takes graph vectors [G, l] and query rows [Q, r]")
     if not hg.is_cuda:
         raise RuntimeError("taxoexpan_amd.loss.in_batch_info_nce runs on the MI355X only (no CPU path; loss.host_in_batch_nce is the restatement)")
-    return ops.InBatchNCEFunction.apply(hg, match.W.weight, queries, bool(match.apply_exp), groups, valid_total).as_subclass(LossTensor)
+    return ops.InBatchNCEFunction.apply(hg, match.W.weight, queries, bool(match.apply_exp), groups, valid_total,
+                                        bool(query_grad)).as_subclass(LossTensor)
 
 
 def host_in_batch_valid(pos_col, anchor, qnode, mask_ptr=None, mask_idx=None):

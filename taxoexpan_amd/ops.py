@@ -1447,12 +1447,38 @@ class RepeatedRows:
         return 2
 
     def dense(self):
+        # rows on the device that ask for a gradient (a trainable feature table's leaves): their gradient is a fixed-order run sum
+        if self.rows.requires_grad and self.rows.is_cuda and torch.is_grad_enabled():
+            return RepeatRowsFunction.apply(self.rows, self.run_off, self.n_rows)
         cnt = (self.run_off[1:] - self.run_off[:-1]).long()
         return self.rows.repeat_interleave(cnt, dim=0, output_size=self.n_rows)
 
     def to(self, device):
         rows = self.rows.to(device)
         return RepeatedRows(rows, self.run_off.to(rows.device), self.n_rows)
+
+
+class RepeatRowsFunction(torch.autograd.Function):
+    """RepeatedRows.dense() for rows that ask for a gradient (feature_table.FeatureTable: the distinct query rows are leaves).  Forward is
+    the repeat_interleave that dense() always was, the same bits; backward sums each run's pair gradients left to right in one launch
+    (txe_rows_run_sum) -- repeat_interleave's own backward is an index_add_ with floating-point atomics, whose order changes from run
+    to run."""
+
+    @staticmethod
+    def forward(ctx, rows, run_off, n_rows):
+        _need_cuda(rows)
+        ctx.run_off, ctx.shape = run_off, rows.shape
+        cnt = (run_off[1:] - run_off[:-1]).long()
+        return rows.repeat_interleave(cnt, dim=0, output_size=n_rows)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        d_out, ld = _rows(_f32(d_out))
+        U, r = ctx.shape
+        d_rows = _empty((U, r), d_out)
+        with _lib.on_device(d_out.device):
+            call("txe_rows_run_sum", ptr(d_out), ld, ptr(ctx.run_off), U, d_out.shape[0], r, ptr(d_rows), r, _lib.stream_ptr())
+        return d_rows, None, None
 
 
 def dense_rows(x):
@@ -1560,14 +1586,16 @@ class InBatchNCEFunction(torch.autograd.Function):
     masked by the taxonomy (txe_inbatch_nce).  hg [G, l] (materialised), W [1, l, r], queries [Q, r] (one row per query), groups: a
     sampler.InBatchGroups of the same Q and G.  Forward: V = q W^T, B = V hg^T (txe_gemm_plain, layout 0), exp in place for LBM
     (txe_inbatch_exp), then the loss launch, which leaves the gradient to B in place of the scores.  Backward: d_hg = dB^T V, dV = dB hg,
-    dW = dV^T q (layouts 2, 1, 2).  No gradient to the queries.  valid_total: None, or an int64 [1] device counter that gains the
+    dW = dV^T q (layouts 2, 1, 2).  No gradient to the queries, unless query_grad=True (a trainable feature table: d_q = dV W, layout 1;
+    without it queries that ask for a gradient are refused).  valid_total: None, or an int64 [1] device counter that gains the
     batch's valid (query, column) pairs.  Returns the sum-reduced fp32 loss (a 0-dim tensor)."""
 
     @staticmethod
-    def forward(ctx, hg, W, queries, apply_exp, groups, valid_total=None):
+    def forward(ctx, hg, W, queries, apply_exp, groups, valid_total=None, query_grad=False):
         _need_cuda(hg, W, queries)
-        if queries.requires_grad:
-            raise ValueError("InBatchNCEFunction: the queries are taxonomy features and get no gradient (detach them)")
+        if queries.requires_grad and not query_grad:
+            raise ValueError("InBatchNCEFunction: the queries are taxonomy features and get no gradient (detach them, or pass "
+                             "query_grad=True when the feature table trains)")
         hg, ldh = _rows(hg)
         q, ldq = _rows(queries)
         Wf = _f32(W).reshape(W.shape[-2], W.shape[-1])
@@ -1596,28 +1624,33 @@ class InBatchNCEFunction(torch.autograd.Function):
             ws = _ws(wsb, hg)
             call("txe_inbatch_nce", ptr(B), G, Q, G, ptr(groups.pos_col), ptr(groups.anchor), ptr(groups.qnode), ptr(groups.mask_ptr),
                  ptr(groups.mask_idx), int(bool(apply_exp)), ptr(loss), ptr(B), G, None, ptr(valid_total), ptr(ws), wsb, _lib.stream_ptr())
-        ctx.misc = (hg, ldh, q, ldq, V, B, W.shape)
+        ctx.misc = (hg, ldh, q, ldq, V, B, W.shape, Wf)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         if ctx.misc is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         from .loss import _scaled
-        hg, ldh, q, ldq, V, dB, wshape = ctx.misc
+        hg, ldh, q, ldq, V, dB, wshape, Wf = ctx.misc
         (G, l), (Q, r) = hg.shape, q.shape
         dB = _scaled(dB, grad_loss)
-        d_hg = dW = None
+        d_hg = dW = d_q = None
         with _lib.on_device(hg.device):
             if ctx.needs_input_grad[0]:
                 d_hg = _empty((G, l), hg)
                 _plain_gemm(2, dB, G, V, l, d_hg, l, G, l, Q)
-            if ctx.needs_input_grad[1]:
-                dV, dW = _empty((Q, l), hg), _empty((l, r), hg)
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                dV = _empty((Q, l), hg)
                 _plain_gemm(1, dB, G, hg, ldh, dV, l, Q, l, G)
+            if ctx.needs_input_grad[1]:
+                dW = _empty((l, r), hg)
                 _plain_gemm(2, dV, l, q, ldq, dW, r, l, r, Q)
                 dW = dW.reshape(wshape)
-        return d_hg, dW, None, None, None, None
+            if ctx.needs_input_grad[2]:                       # (query_grad=True: forward refuses otherwise) d_q = dV W
+                d_q = _empty((Q, r), hg)
+                _plain_gemm(1, dV, l, Wf, r, d_q, r, Q, r, l)
+        return d_hg, dW, d_q, None, None, None, None
 
 
 def gcn_folded_graph_vector_ok(csr, cfg, params):

@@ -146,7 +146,7 @@ def _is_info_nce(loss_fn):
 
 
 def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None, max_grad_norm=None, freeze_on_nonfinite=False,
-                in_batch=False):
+                in_batch=False, feature_table=None):
     """trainer.py:41-77 on the device: model.train(), then per batch zero_grad, forward, loss, backward, ONE txe_step_log launch,
     optimizer.step() -- no .item(), .cpu() or synchronize between the first batch and the last (what `loader` does to build a batch is
     its own business), then one read-back of the log.
@@ -180,7 +180,15 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
     must attach `g.in_batch` (DeviceBatchLoader(sampler="device", in_batch=True)) and the matcher must be BIM / LBM; loss_fn cannot be
     given with it -- each a ValueError before the first optimizer step.  The dict gains mean_negatives = the valid negative columns per
     query, averaged over the epoch: the log's int64 counter word (StepLog.counter), which the loss launches add to and which comes
-    back in the log's one read-back."""
+    back in the log's one read-back.
+    feature_table (an addition; None: the loop is launch for launch what it was): a feature_table.FeatureTable that the loader gathers from
+    (DeviceBatchLoader(feature_table=...)).  After zero_grad, feature_table.leaves(g, qf, h) makes the batch's node features and distinct
+    query rows leaves; the log reads their gradients beside the parameters' -- the non-finite check covers them, and grad_norms then
+    INCLUDE the per-occurrence feature gradients -- and feature_table.step(guard=...) runs right after optimizer.step(...).  Works with
+    every loss_fn and with in_batch=True.  max_grad_norm (the argument's or a parameter group's) together with a table is a ValueError
+    before the first step: the logged norm is over occurrences, not the table gradient's norm, and clipping the table is out of scope.
+    freeze_on_nonfinite freezes the table with the model and discounts its steps as the optimizer's.  Averaged weights do not cover
+    the table."""
     if in_batch:
         if loss_fn is not None:
             raise ValueError("train_epoch: in_batch=True brings its own loss (loss.in_batch_info_nce); loss_fn cannot be given with it")
@@ -204,6 +212,9 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
     max_grad_norm = _checked_max_norm(max_grad_norm)
     clip = max_grad_norm is not None or any(g.get("max_grad_norm") is not None for g in optimizer.param_groups)
     guarded = clip or bool(freeze_on_nonfinite)
+    if clip and feature_table is not None:
+        raise ValueError("train_epoch: max_grad_norm cannot be combined with a feature_table (the step log's norm is over per-occurrence "
+                         "gradients and is not the table gradient's norm; clipping the table is out of scope)")
     if guarded and "guard" not in inspect.signature(optimizer.step).parameters:
         raise ValueError(f"max_grad_norm / freeze_on_nonfinite need an optimizer whose step() takes `guard` (taxoexpan_amd.optim.Adam); "
                          f"{type(optimizer).__name__}.step does not")
@@ -233,9 +244,16 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         if in_batch and getattr(g, "in_batch", None) is None:
             raise ValueError("train_epoch: in_batch=True, but a batch has no g.in_batch (DeviceBatchLoader(sampler='device', in_batch=True))")
         optimizer.zero_grad()                                          # trainer.py:50
+        logged = params
+        if feature_table is not None:
+            h, qf, _ids, _qids = feature_table.leaves(g, qf, h)
+            logged = params + [h, qf.rows]
         if in_batch:
             hg = encode_graph(model, g, h, g.ndata["pos"].to(dev))
-            loss = in_batch_info_nce(model.match, hg, getattr(qf, "rows", qf), g.in_batch, valid_total=valid_total)
+            if feature_table is not None:
+                loss = in_batch_info_nce(model.match, hg, qf.rows, g.in_batch, valid_total=valid_total, query_grad=True)
+            else:
+                loss = in_batch_info_nce(model.match, hg, getattr(qf, "rows", qf), g.in_batch, valid_total=valid_total)
             n_queries += g.in_batch.Q
         else:
             prediction = model(g, h, qf)
@@ -246,17 +264,22 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
             else:
                 loss = loss_fn(prediction, label)
         loss.backward()                                                # trainer.py:60
-        log.record(loss, params)
+        log.record(loss, logged)
         if guarded:                                                    # only what was asked for is passed
             guard = log.guard(gnorm2=clip, first_bad=bool(freeze_on_nonfinite))
             guard.max_grad_norm = max_grad_norm
             optimizer.step(guard=guard)
         else:
+            guard = None
             optimizer.step()                                           # trainer.py:61
+        if feature_table is not None:
+            feature_table.step(guard=guard)
         n_batches += 1
     rec = log.read()
     if freeze_on_nonfinite and rec["first_nonfinite"] >= 0:
         optimizer.discount_frozen_steps(n_batches - rec["first_nonfinite"])
+        if feature_table is not None:
+            feature_table.discount_frozen_steps(n_batches - rec["first_nonfinite"])
     out = dict(loss=rec["loss_sum"] / n_batches if n_batches else float("nan"), n_batches=n_batches, losses=rec["loss"],
                grad_norms=rec["grad_norm"], first_nonfinite=rec["first_nonfinite"])
     if in_batch:                                                       # (valid pairs - the positives) per query
@@ -273,15 +296,18 @@ class TrainingDiverged(RuntimeError):
         self.epoch, self.step, self.logs, self.checkpoint = epoch, step, list(logs), checkpoint
 
 
-def _checkpoint_state(model, optimizer, epoch, monitor_best, config, averaged=False):
+def _checkpoint_state(model, optimizer, epoch, monitor_best, config, averaged=False, feature_table=None):
     """averaged: one more key, "ema_state_dict" = the model's state_dict() with the averages swapped in, as copies (the swap goes back
-    before anything else is read: "state_dict" and "optimizer" are the raw weights and the full state, as ever)"""
+    before anything else is read: "state_dict" and "optimizer" are the raw weights and the full state, as ever); feature_table: one more
+    key, "feature_table" = its state_dict()"""
     state = {}
     if averaged:
         with optimizer.averaged_parameters():
             state["ema_state_dict"] = {k: v.detach().clone() for k, v in model.state_dict().items()}
     state.update({"arch": type(model).__name__, "epoch": epoch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
                   "monitor_best": monitor_best, "config": config})
+    if feature_table is not None:
+        state["feature_table"] = feature_table.state_dict()
     return state
 
 
@@ -295,9 +321,9 @@ def load_averaged(model, path):
     return ckpt
 
 
-def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, save_best, averaged=False):
+def _save_checkpoint(save_dir, model, optimizer, epoch, monitor_best, config, save_best, averaged=False, feature_table=None):
     """base_trainer.py:126-149"""
-    state = _checkpoint_state(model, optimizer, epoch, monitor_best, config, averaged)
+    state = _checkpoint_state(model, optimizer, epoch, monitor_best, config, averaged, feature_table)
     os.makedirs(str(save_dir), exist_ok=True)
     torch.save(state, os.path.join(str(save_dir), f"checkpoint-epoch{epoch}.pth"))
     if save_best:
@@ -334,7 +360,7 @@ def _checked_hard_negatives(cfg, train_loader):
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
         loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False,
-        hard_negatives=None, averaged=False, in_batch=False):
+        hard_negatives=None, averaged=False, in_batch=False, feature_table=None):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -375,7 +401,14 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     weights and the full optimizer state, the average included, so `resume=` continues exactly.  Hard-negative mining keeps ranking
     with the raw model, the one being trained: its negatives are meant to be hard for the weights that the next step updates.
     in_batch=True goes to train_epoch (see there; passed only when set): the epochs train on in-batch negatives and their logs gain
-    mean_negatives; validation is unchanged, and hard negatives compose (they only change which anchors a batch holds)."""
+    mean_negatives; validation is unchanged, and hard negatives compose (they only change which anchors a batch holds).
+    feature_table (an addition; None: nothing changes): a feature_table.FeatureTable, passed to train_epoch (see there; only when set).
+    Before each validation feature_table.write_back() puts the table into the training dataset's node_features / kv, and
+    feature_table.refresh(valid_loader) does the same for the validation loader's dataset and resident table, so that validation -- and
+    anything that reads host features afterwards -- scores with the trained vectors.  Every checkpoint (checkpoint-epochN.pth,
+    model_best.pth, last_finite.pth) gains "feature_table" = its state_dict(), and `resume=` restores it (a checkpoint without the key
+    is a ValueError).  Averaged weights do not cover the table: with averaged=True the val_* metrics use the averaged model over the
+    raw table."""
     if averaged and not (hasattr(optimizer, "averaged_parameters") and any(g.get("ema_decay") is not None for g in optimizer.param_groups)):
         raise ValueError("fit(averaged=True) needs an optimizer with averaged_parameters() and an ema_decay in at least one parameter "
                          f"group (taxoexpan_amd.optim.Adam(ema_decay=...)); got {type(optimizer).__name__}")
@@ -407,6 +440,10 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
         mnt_best = ckpt["monitor_best"]
         model.load_state_dict(ckpt["state_dict"])
         optimizer.load_state_dict(ckpt["optimizer"])
+        if feature_table is not None:
+            if "feature_table" not in ckpt:
+                raise ValueError(f"{resume} has no 'feature_table': the checkpoint was written by a run that did not train the table")
+            feature_table.load_state_dict(ckpt["feature_table"])
     logs = []
     not_improved_count = 0
     guard_args = {}
@@ -416,6 +453,8 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
         guard_args["freeze_on_nonfinite"] = True
     if in_batch:
         guard_args["in_batch"] = True
+    if feature_table is not None:
+        guard_args["feature_table"] = feature_table
     for epoch in range(start_epoch, epochs + 1):
         mined = None
         if hard is not None and epoch >= hard["start"] and (epoch - hard["start"]) % hard["every"] == 0:
@@ -435,9 +474,12 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
             if freeze_on_nonfinite and save_dir is not None:
                 os.makedirs(str(save_dir), exist_ok=True)
                 checkpoint = os.path.join(str(save_dir), "last_finite.pth")
-                torch.save(_checkpoint_state(model, optimizer, epoch - 1, mnt_best, config, averaged), checkpoint)
+                torch.save(_checkpoint_state(model, optimizer, epoch - 1, mnt_best, config, averaged, feature_table), checkpoint)
             raise TrainingDiverged(epoch, int(result["first_nonfinite"]), logs, checkpoint)
         if valid_loader is not None:                                   # trainer.py:80-82, base_trainer.py:71-72
+            if feature_table is not None:                              # validation reads host features and its own resident table
+                feature_table.write_back()
+                feature_table.refresh(valid_loader)
             if averaged:
                 with optimizer.averaged_parameters():
                     val = validate_fn(model, valid_loader, metrics=metrics, larger_is_better=larger_is_better)
@@ -465,5 +507,5 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
                 if not_improved_count > early_stop:
                     break
         if save_dir is not None and epoch % save_period == 0:         # base_trainer.py:106-107
-            _save_checkpoint(save_dir, model, optimizer, epoch, mnt_best, config, best, averaged)
+            _save_checkpoint(save_dir, model, optimizer, epoch, mnt_best, config, best, averaged, feature_table)
     return logs
