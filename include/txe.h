@@ -735,6 +735,36 @@ int txe_copy_stream(const void* src, void* dst, long long n_bytes, void* stream)
 int txe_info_nce(const float* x, long long ld_x, int B, int Cc, const long long* target, float* loss, float* d_x, long long ld_dx,
                  void* stream);
 
+/* Taxonomy-aware InfoNCE (csrc/txe_taxoloss.hip): txe_info_nce with a Wu & Palmer margin on every negative.  Q groups of
+ * C = 1 + k columns; x[i][c] the model's output, a[i][c] = anchors[i ld_a + c] the taxonomy node of the column's egonet, column 0 the
+ * positive, p_i = a[i][0]; the index (anc_ptr, anc_idx, depth, n_nodes) and lca_depth as for txe_taxo_slots.
+ *   d[i][0] = 0
+ *   d[i][c] = 0                                                                     if a[i][c] or p_i lies outside [0, n_nodes)
+ *                                                                                   (compared BEFORE it addresses anything)
+ *   d[i][c] = 1.0 - 2.0 * lca_depth(a[i][c], p_i) / (depth[a[i][c]] + depth[p_i])   float64; in [0, 1]; 0 iff a[i][c] == p_i; 1 in a forest
+ *   m[i][c] = (float)((double)gamma * d[i][c])                                      one rounding to fp32
+ *   y[i][c] = x[i][c] + m[i][c]                                                     one fp32 add
+ *   row_i   = logsumexp_c y[i][c] - x[i][0]
+ *   loss[0] = sum_i row_i                          (row losses merged in a fixed order, in float64, then one rounding)
+ *   d_x[i][c] = softmax_c(y[i])[c] - [c == 0]      (d is a constant of the batch: no gradient flows into it)
+ * gamma = 0: d_x has the bytes txe_info_nce leaves on the same x with target NULL (both kernels call one row function).  margin (NULL:
+ * not wanted) gets m, [Q][C] with pitch C, bit-equal to the numpy restatement loss.host_taxo_margins; dist_total (NULL: not wanted)
+ * gains sum over i and c >= 1 of floor(d[i][c] 2^20), an integer atomic.  A positive whose closure row has more than
+ * TXE_TAXO_STAGE_CAP entries is searched in global memory instead of LDS; the results do not depend on the route.  One launch over
+ * ceil(Q / rows per workgroup) workgroups, then one launch that adds the row losses in row order: no floating-point atomics, two calls
+ * on the same inputs give the same bytes in loss, d_x and margin.  After the call ws begins with the Q row losses (fp32, row order).
+ * TXE_ERR_ARG before any launch: a NULL among x, anchors, anc_ptr, anc_idx, depth, loss, d_x; Q < 0, C < 1, ld_x / ld_dx / ld_a < C,
+ * Q C >= 2^31, n_nodes < 0; gamma not finite or negative; ws NULL or ws_bytes < txe_info_nce_taxo_ws_bytes(Q).
+ * Q == 0: TXE_OK, loss[0] = 0, nothing else written. */
+#define TXE_TAXO_STAGE_CAP 64
+size_t txe_info_nce_taxo_ws_bytes(int Q);
+int txe_info_nce_taxo(const float* x, long long ld_x, int Q, int C, const int* anchors, long long ld_a,
+                      const int* anc_ptr, const int* anc_idx, const int* depth, int n_nodes, double gamma,
+                      float* loss, float* d_x, long long ld_dx,
+                      float* margin /* [Q][C] pitch C, or NULL */,
+                      long long* dist_total /* += sum over c >= 1 of floor(d * 2^20), or NULL */,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* In-batch negatives (csrc/txe_inbatch.hip): every query row i of S [Q][G] -- the matcher's output for (query i, egonet g) of one
  * training batch -- is a cross entropy over the batch's columns without those whose anchor lies in the query's mask row:
  *   valid(i, g) = (g == pos_col[i]) or anchor[g] not in mask_idx[mask_ptr[qnode[i]] .. mask_ptr[qnode[i] + 1])

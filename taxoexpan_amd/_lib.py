@@ -13,6 +13,7 @@ FUSED_DW_BESIDE, FUSED_DZ_GIVEN, FUSED_EDOT, FUSED_NO_EGO_WALK = 128, 256, 512, 
 WALK_NO_REFORM = 2048          # TXE_WALK_NO_REFORM: one more `phases` bit of txe_gat_collapse_bwd_fused
 FOLD_A12_READY, FOLD_HG_SPLIT = 1, 2
 STEP_LOG_CHUNK = 4096          # TXE_STEP_LOG_CHUNK: gradient elements per workgroup of txe_step_log
+TAXO_STAGE_CAP = 64            # TXE_TAXO_STAGE_CAP: the longest positive closure row txe_info_nce_taxo stages in LDS
 
 P, I, L, F, D, U64, SZ = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_size_t
 
@@ -149,6 +150,8 @@ SIGNATURES = {
     "txe_select_k_ws_bytes": (SZ, [I, I]),
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),
     "txe_info_nce": (I, [P, L, I, I, P, P, P, L, P]),
+    "txe_info_nce_taxo_ws_bytes": (SZ, [I]),
+    "txe_info_nce_taxo": (I, [P, L, I, I, P, L, P, P, P, I, D, P, P, L, P, P, P, SZ, P]),
     "txe_inbatch_nce_ws_bytes": (SZ, [I]),
     "txe_inbatch_nce": (I, [P, L, I, I, P, P, P, P, P, I, P, P, L, P, P, P, SZ, P]),
     "txe_inbatch_exp": (I, [P, L, I, I, P]),

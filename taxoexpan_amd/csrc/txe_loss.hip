@@ -2,6 +2,7 @@
 // regrouping of trainer.py:52-56) with its gradient, in one launch: torch runs log-softmax, nll, their two backward kernels and
 // three fills for it -- seven ~5 us dispatches around 4,096 numbers.
 #include "txe_common.h"
+#include "txe_nce_row.h"
 
 namespace txe {
 
@@ -9,6 +10,7 @@ constexpr int NCE_WAVES = 16;
 
 // One workgroup.  A row occupies a group of GW lanes (GW = 32 when C <= 32, else 64; longer rows loop), so a wave handles 64/GW rows
 // per pass, and the passes of a wave are independent loads issued back to back.  The row losses are combined in a fixed order.
+// The row arithmetic itself is nce_row (txe_nce_row.h), which txe_taxoloss.hip calls too.
 template <int GW>
 __global__ __launch_bounds__(NCE_WAVES * 64) void info_nce_kernel(const float* __restrict__ x, long long ld_x, int B, int Cc,
                                                                   const long long* __restrict__ target, float* __restrict__ loss,
@@ -23,20 +25,8 @@ __global__ __launch_bounds__(NCE_WAVES * 64) void info_nce_kernel(const float* _
         const bool live = b < B;
         const float* row = x + (long long)(live ? b : 0) * ld_x;
         const int t = (live && target) ? (int)target[b] : 0;
-        float m = -INFINITY;
-        for (int c = gl; c < Cc; c += GW) m = fmaxf(m, row[c]);
-#pragma unroll
-        for (int o = GW / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        float s = 0.f;
-        for (int c = gl; c < Cc; c += GW) s += __expf(row[c] - m);
-#pragma unroll
-        for (int o = GW / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        const float inv = 1.f / s;
-        if (live) {
-            float* drow = d_x + (long long)b * ld_dx;
-            for (int c = gl; c < Cc; c += GW) drow[c] = __expf(row[c] - m) * inv - (c == t ? 1.f : 0.f);
-            if (gl == 0) acc += m + __logf(s) - row[t];
-        }
+        const float r = nce_row<GW>([&](int c) { return row[c]; }, Cc, gl, t, live, d_x + (long long)(live ? b : 0) * ld_dx);
+        if (live && gl == 0) acc += r;
     }
     if (gl == 0) s_part[w * RPW + sub] = acc;
     __syncthreads();

@@ -223,6 +223,9 @@ class DeviceBatchLoader:
     negative slots of every query (txe_sample_anchors_hard); set_hard_negatives changes it between epochs.
     in_batch=True (this sampler, repeated_queries=True; ValueError otherwise): every batch's graph carries `g.in_batch`, a
     sampler.InBatchGroups -- views of the sampler's index array and mask CSR for loss.in_batch_info_nce; the 4-tuple keeps its shape.
+    attach_anchors=True (this sampler; ValueError otherwise; default off: the loader launches and yields what it did): every batch's graph
+    carries `g.anchors`, the int32 [Q, 1 + negative_size] view of the sampler's anchors (positive first) that loss.taxo_info_nce reads;
+    with in_batch=True as well, g.anchors and g.in_batch.anchor share storage.
     sampler="device" on a sampling_mode 0 dataset (validation batches of the shipped configs; train / validation): sampler.DeviceGroupSampler
     draws every parent and at most negative_size negatives per query, labels an int64 device tensor.  The batch size B is then known on
     the device only, so three batches are in flight: each next() after the first finishes batch b (its node count, read back one next()
@@ -234,7 +237,7 @@ class DeviceBatchLoader:
     step b (finish_device_batch).  Every graph gains g.query_ids, the int32 [U] ids of the distinct query rows."""
 
     def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host",
-                 hard_negatives=None, hard_slots=0, in_batch=False, feature_table=None):
+                 hard_negatives=None, hard_slots=0, in_batch=False, feature_table=None, attach_anchors=False):
         if sampler not in ("host", "device"):
             raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
         if feature_table is not None and not repeated_queries:
@@ -243,6 +246,10 @@ class DeviceBatchLoader:
             raise ValueError("in_batch=True needs sampler='device', a sampling_mode 1 dataset and repeated_queries=True (the in-batch "
                              "groups are views of the device sampler's index array)")
         self.in_batch = bool(in_batch)
+        if attach_anchors and not (sampler == "device" and dataset.sampling_mode == 1):
+            raise ValueError("attach_anchors=True needs sampler='device' and a sampling_mode 1 dataset (g.anchors is a view of the device "
+                             "sampler's index array, 1 + negative_size columns per query)")
+        self.attach_anchors = bool(attach_anchors)
         if hard_negatives is not None and not (sampler == "device" and dataset.sampling_mode == 1):
             raise ValueError("hard negatives need sampler='device' on a sampling_mode 1 dataset")
         self.repeated_queries = bool(repeated_queries)
@@ -333,6 +340,14 @@ class DeviceBatchLoader:
         groups.record_stream(torch.cuda.current_stream(self.device))
         return groups
 
+    def _anchors(self, packed, Q):
+        """the anchors of the finished batch as int32 [Q, 1 + k] (group-major, positive first): a view of packed[:B] -- the storage
+        g.in_batch.anchor views too --, marked as used on the consumer's stream like the batch's other tensors"""
+        C = 1 + self.sampler.k
+        anchors = packed[:Q * C].view(Q, C)
+        anchors.record_stream(torch.cuda.current_stream(self.device))
+        return anchors
+
     def _iter_device(self, order, epoch):
         n, bs = len(order), self.batch_size
         order_dev = self.sampler.upload_order(order, self._side)     # once per epoch, on the side stream the launches use
@@ -349,6 +364,8 @@ class DeviceBatchLoader:
                 nxt = begin(b + 1) if b + 1 < len(self) else None
                 if self.in_batch:
                     batch["g"].in_batch = self._in_batch_groups(pending["packed"], Q)
+                if self.attach_anchors:
+                    batch["g"].anchors = self._anchors(pending["packed"], Q)
                 yield batch["g"], batch["x"], batch["qf"], self._label(Q)
         finally:
             self.sampler.in_epoch = False

@@ -9,6 +9,8 @@ gradient (no autograd graph of small torch kernels behind it, no read-back):
                       steps on the stream, nothing read back
     host_bce_loss / host_square_exp_loss / host_margin_rank_loss   the numpy float64 restatements (the written definitions; the tests
                       compare against them)
+    taxo_info_nce     an addition: info_nce_loss with a Wu & Palmer margin on every negative, from the anchors of the batch and a resident
+                      taxonomy index (csrc/txe_taxoloss.hip; host_taxo_margins / host_taxo_info_nce: its numpy restatement)
     in_batch_info_nce an addition: every query of a batch against ALL of the batch's egonets, masked by the taxonomy (csrc/txe_inbatch.hip,
                       ops.InBatchNCEFunction; host_in_batch_nce: its float64 restatement)
 
@@ -77,6 +79,137 @@ def info_nce_loss(output, target=None):
     if not output.is_cuda:
         raise RuntimeError("taxoexpan_amd.loss.info_nce_loss runs on the MI355X only (no CPU path)")
     return _InfoNCE.apply(output, target).as_subclass(LossTensor)
+
+
+# ---- taxonomy-aware InfoNCE: Wu & Palmer margins on the negatives --------------------------------------------------------
+
+DIST_SCALE = 2 ** 20           # dist_total counts floor(d * 2^20) per negative
+
+
+def _checked_gamma(gamma, who):
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: gamma must be a finite number >= 0, got {gamma!r}") from None
+    if isinstance(gamma, bool) or not np.isfinite(g) or g < 0:
+        raise ValueError(f"{who}: gamma must be a finite number >= 0, got {gamma!r}")
+    return g
+
+
+class _TaxoInfoNCE(torch.autograd.Function):
+    """txe_info_nce_taxo: forward leaves the loss and d_x; backward scales d_x"""
+
+    @staticmethod
+    def forward(ctx, output, anchors, index, gamma, dist_total):
+        x = output if (output.dtype == torch.float32 and output.stride(-1) == 1) else output.float().contiguous()
+        a = anchors if anchors.stride(-1) == 1 else anchors.contiguous()
+        Q, C = x.shape
+        dev = x.device
+        with _lib.on_device(dev):
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            d_x = torch.empty((Q, C), dtype=torch.float32, device=dev)
+            wsb = _lib.pure("txe_info_nce_taxo_ws_bytes", Q)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            _lib.call("txe_info_nce_taxo", x.data_ptr(), x.stride(0) if Q > 1 else C, Q, C, a.data_ptr(), a.stride(0) if Q > 1 else C,
+                      index.anc_ptr.data_ptr(), index.anc_idx.data_ptr(), index.depth.data_ptr(), index.n_nodes, gamma, loss.data_ptr(),
+                      d_x.data_ptr(), C, None, None if dist_total is None else dist_total.data_ptr(), ws.data_ptr(), wsb,
+                      _lib.stream_ptr())
+        ctx.save_for_backward(d_x)
+        ctx.dtype = output.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (d_x,) = ctx.saved_tensors
+        d = _scaled(d_x, grad_loss)
+        return (d if ctx.dtype == torch.float32 else d.to(ctx.dtype)), None, None, None, None
+
+
+def taxo_info_nce(output, anchors, index, gamma, dist_total=None):
+    """info_nce_loss with a taxonomic margin on every negative (an addition): a negative far from the true parent must be
+    beaten by more.  output [Q, C]: the scores of Q groups, column 0 the positive (train_epoch's regrouping); anchors [Q, C] int32 on
+    the same device: the taxonomy node every column's egonet is anchored at (a DeviceBatchLoader(attach_anchors=True) attaches it as
+    g.anchors); index: TaxonomyIndex.to(device) (TypeError otherwise).  With d = 1 - wu_palmer(anchor, the group's positive) in float64
+    (0 in column 0 and where either node lies outside the index), m = float32(gamma * d) and y = output + m:
+        loss = sum over groups of logsumexp(y) - output[:, 0],    d loss / d output = softmax(y) - [column 0]
+    csrc/txe_taxoloss.hip, one launch and a finish step; loss.host_taxo_info_nce is the written definition.  gamma: finite and >= 0
+    (ValueError otherwise); 0 gives info_nce_loss's gradient bit for bit.  The margin is added to WHATEVER THE MODEL OUTPUTS -- for LBM
+    that is exp(b), not b -- so the scale of gamma is the user's to choose against the scale of the scores.  A query with several
+    parents is measured against the positive of its own group only (its other parents never appear as negatives: node2masks removes
+    them).  No gradient flows into d.  dist_total: None, or an int64 [1] device counter that gains sum over the negatives of
+    floor(d * 2^20) (train_epoch's mean_taxo_distance).  Returns the sum-reduced loss as a LossTensor."""
+    from .taxometric import DeviceTaxonomyIndex
+    if not isinstance(index, DeviceTaxonomyIndex):
+        raise TypeError("taxo_info_nce takes TaxonomyIndex.to(device)")
+    if not (torch.is_tensor(output) and torch.is_tensor(anchors)):
+        raise TypeError("taxo_info_nce takes tensors")
+    if not output.is_cuda:
+        raise RuntimeError("taxoexpan_amd.loss.taxo_info_nce runs on the MI355X only (no CPU path; loss.host_taxo_info_nce is the restatement)")
+    gamma = _checked_gamma(gamma, "taxo_info_nce")
+    if output.dim() != 2 or output.shape[1] < 1:
+        raise ValueError(f"taxo_info_nce takes scores [groups, 1 + negatives], got {tuple(output.shape)}")
+    if tuple(anchors.shape) != tuple(output.shape):
+        raise ValueError(f"one anchor per score: anchors {tuple(anchors.shape)} against scores {tuple(output.shape)}")
+    if anchors.dtype != torch.int32:
+        raise ValueError(f"anchors must be int32, got {anchors.dtype}")
+    if not output.dtype.is_floating_point:
+        raise ValueError(f"scores must be floating point, got {output.dtype}")
+    if anchors.device != output.device or index.device != output.device:
+        raise ValueError("scores, anchors and the taxonomy index must be on one device")
+    if output.numel() >= 2 ** 31:
+        raise ValueError("taxo_info_nce takes fewer than 2^31 scores")
+    if dist_total is not None and not (torch.is_tensor(dist_total) and dist_total.dtype == torch.int64 and dist_total.numel() == 1
+                                       and dist_total.device == output.device):
+        raise ValueError("dist_total must be an int64 [1] tensor on the scores' device")
+    return _TaxoInfoNCE.apply(output, anchors, index, gamma, dist_total).as_subclass(LossTensor)
+
+
+def host_taxo_margins(index, anchors, gamma):
+    """the margins of taxo_info_nce in numpy -- the written definition: (d float64 [Q, C], m float32 [Q, C]).  anchors [Q, C] node ids,
+    column 0 the positive.  d = 1.0 - 2.0 * lca_depth / (depth_a + depth_p) from taxometric's own host helpers (the evaluation metric's
+    integers: an exact product, one correctly rounded quotient, one subtraction); 0 in column 0 and where the anchor or the group's
+    positive lies outside [0, n).  m = float32(float64(gamma) * d): one product, one cast."""
+    from .taxometric import _host_index, _lca_depth
+    index = _host_index(index)
+    gamma = _checked_gamma(gamma, "host_taxo_margins")
+    anchors = np.asarray(anchors)
+    if anchors.ndim != 2 or anchors.shape[1] < 1:
+        raise ValueError(f"anchors must be [groups, 1 + negatives], got {anchors.shape}")
+    anchors = anchors.astype(np.int64)
+    n = index.n_nodes
+    d = np.zeros(anchors.shape, dtype=np.float64)
+    memo = {}
+    for i in range(anchors.shape[0]):
+        p = int(anchors[i, 0])
+        if not 0 <= p < n:
+            continue
+        for c in range(1, anchors.shape[1]):
+            a = int(anchors[i, c])
+            if not 0 <= a < n:
+                continue
+            if (a, p) not in memo:
+                lca = np.float64(_lca_depth(index, a, p))
+                memo[(a, p)] = 1.0 - 2.0 * lca / np.float64(int(index.depth[a]) + int(index.depth[p]))
+            d[i, c] = memo[(a, p)]
+    return d, (np.float64(gamma) * d).astype(np.float32)
+
+
+def host_taxo_info_nce(x, anchors, index, gamma):
+    """numpy float64 restatement of txe_info_nce_taxo -- the written definition: (loss, d_x [Q, C], row_loss [Q]) from
+    y = x.astype(float32) + m in fp32 (host_taxo_margins' m), everything after that in float64"""
+    x32 = np.asarray(x).astype(np.float32)
+    _, m = host_taxo_margins(index, anchors, gamma)
+    if x32.shape != m.shape:
+        raise ValueError(f"one anchor per score: anchors {m.shape} against scores {x32.shape}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = (x32 + m).astype(np.float64)
+        mx = y.max(axis=1, keepdims=True)
+        e = np.exp(y - mx)
+        s = e.sum(axis=1, keepdims=True)
+        row = mx[:, 0] + np.log(s[:, 0]) - x32[:, 0].astype(np.float64)
+        d_x = e / s
+        d_x[:, 0] -= 1.0
+    return float(np.sum(row)), d_x, row
 
 
 # ---- in-batch negatives -------------------------------------------------------------------------------------------------------------

@@ -146,7 +146,7 @@ def _is_info_nce(loss_fn):
 
 
 def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=None, max_grad_norm=None, freeze_on_nonfinite=False,
-                in_batch=False, feature_table=None):
+                in_batch=False, feature_table=None, taxo_margin=None, taxonomy_index=None):
     """trainer.py:41-77 on the device: model.train(), then per batch zero_grad, forward, loss, backward, ONE txe_step_log launch,
     optimizer.step() -- no .item(), .cpu() or synchronize between the first batch and the last (what `loader` does to build a batch is
     its own business), then one read-back of the log.
@@ -188,7 +188,33 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
     every loss_fn and with in_batch=True.  max_grad_norm (the argument's or a parameter group's) together with a table is a ValueError
     before the first step: the logged norm is over occurrences, not the table gradient's norm, and clipping the table is out of scope.
     freeze_on_nonfinite freezes the table with the model and discounts its steps as the optimizer's.  Averaged weights do not cover
-    the table."""
+    the table.
+    taxo_margin (an addition; None: the loop is launch for launch what it was, the dict has no new key): gamma, a finite number >= 0 -- 0.0
+    is a value and runs the new launch.  The loss call becomes `loss.taxo_info_nce(prediction.reshape(-1, group_size), g.anchors,
+    index, gamma, dist_total=log.counter)`: InfoNCE whose negatives carry the margin gamma * (1 - Wu & Palmer similarity
+    to the group's positive); forward, backward, log, guarded step, averaged weights, feature table and hard negatives stay as they
+    are, and the folded route keeps running (no score matrix, no materialised hg).  taxonomy_index: TaxonomyIndex.to(device) of the
+    loader's dataset; None builds TaxonomyIndex.from_dataset(loader.dataset).to(device) here (fit builds it once for all epochs).
+    ValueError before the first optimizer step: together with in_batch=True (margins inside the in-batch loss are out of scope) or with
+    a loss_fn, a loader that does not attach g.anchors (DeviceBatchLoader(sampler="device", attach_anchors=True)), a gamma that is not
+    finite or negative, an index whose n_nodes differs from the dataset's.  The dict gains mean_taxo_distance = the mean of 1 - Wu &
+    Palmer over the epoch's negatives, in steps of 2^-20: the log's int64 counter word / 2^20 / (groups * negatives per group)."""
+    taxo = taxo_margin is not None
+    if taxo:
+        from .loss import _checked_gamma
+        if in_batch:
+            raise ValueError("train_epoch: taxo_margin cannot be combined with in_batch=True (margins inside the in-batch loss are out of scope)")
+        if loss_fn is not None:
+            raise ValueError("train_epoch: taxo_margin brings its own loss (loss.taxo_info_nce); loss_fn cannot be given with it")
+        if getattr(loader, "attach_anchors", True) is False:
+            raise ValueError("train_epoch: taxo_margin needs a loader that attaches g.anchors (DeviceBatchLoader(sampler='device', "
+                             "attach_anchors=True))")
+        taxo_margin = _checked_gamma(taxo_margin, "train_epoch: taxo_margin")
+        n_data = getattr(getattr(getattr(loader, "dataset", None), "node_features", None), "shape", (None,))[0]
+        if taxonomy_index is not None and n_data is not None and int(taxonomy_index.n_nodes) != int(n_data):
+            raise ValueError(f"train_epoch: taxonomy_index has {taxonomy_index.n_nodes} nodes, the loader's dataset {n_data}")
+    elif taxonomy_index is not None:
+        raise ValueError("train_epoch: taxonomy_index is the index of taxo_margin; it cannot be given without it")
     if in_batch:
         if loss_fn is not None:
             raise ValueError("train_epoch: in_batch=True brings its own loss (loss.in_batch_info_nce); loss_fn cannot be given with it")
@@ -230,6 +256,16 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         from .loss import in_batch_info_nce
         from .model import encode_graph
         valid_total, n_queries = log.counter, 0                        # (cleared with the log, read back with it)
+    if taxo:
+        from .loss import DIST_SCALE, taxo_info_nce
+        from .taxometric import DeviceTaxonomyIndex, TaxonomyIndex
+        if taxonomy_index is None:
+            if getattr(loader, "dataset", None) is None:
+                raise ValueError("train_epoch: taxo_margin needs taxonomy_index (the loader has no dataset to build it from)")
+            taxonomy_index = TaxonomyIndex.from_dataset(loader.dataset)
+        if not isinstance(taxonomy_index, DeviceTaxonomyIndex):
+            taxonomy_index = taxonomy_index.to(dev)
+        n_negatives = 0
     model.train()                                                      # trainer.py:42
     n_batches = 0
     for batch in loader:
@@ -260,7 +296,15 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
             if info_nce:
                 if prediction.numel() % group_size:
                     raise ValueError(f"a batch of {prediction.numel()} scores is no multiple of group_size {group_size}")
-                loss = loss_fn(prediction.reshape(-1, group_size), None)
+                if taxo:
+                    anchors = getattr(g, "anchors", None)
+                    if anchors is None:
+                        raise ValueError("train_epoch: taxo_margin, but a batch has no g.anchors (DeviceBatchLoader(sampler='device', "
+                                         "attach_anchors=True))")
+                    loss = taxo_info_nce(prediction.reshape(-1, group_size), anchors, taxonomy_index, taxo_margin, dist_total=log.counter)
+                    n_negatives += (prediction.numel() // group_size) * (group_size - 1)
+                else:
+                    loss = loss_fn(prediction.reshape(-1, group_size), None)
             else:
                 loss = loss_fn(prediction, label)
         loss.backward()                                                # trainer.py:60
@@ -284,6 +328,8 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
                grad_norms=rec["grad_norm"], first_nonfinite=rec["first_nonfinite"])
     if in_batch:                                                       # (valid pairs - the positives) per query
         out["mean_negatives"] = (rec["counter"] - n_queries) / n_queries if n_queries else float("nan")
+    if taxo:
+        out["mean_taxo_distance"] = rec["counter"] / DIST_SCALE / n_negatives if n_negatives else float("nan")
     return out
 
 
@@ -360,7 +406,7 @@ def _checked_hard_negatives(cfg, train_loader):
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
         loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False,
-        hard_negatives=None, averaged=False, in_batch=False, feature_table=None):
+        hard_negatives=None, averaged=False, in_batch=False, feature_table=None, taxo_margin=None, taxonomy_index=None):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -408,7 +454,11 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     anything that reads host features afterwards -- scores with the trained vectors.  Every checkpoint (checkpoint-epochN.pth,
     model_best.pth, last_finite.pth) gains "feature_table" = its state_dict(), and `resume=` restores it (a checkpoint without the key
     is a ValueError).  Averaged weights do not cover the table: with averaged=True the val_* metrics use the averaged model over the
-    raw table."""
+    raw table.
+    taxo_margin / taxonomy_index (an addition; None: nothing changes) go to train_epoch (see there; passed only when taxo_margin is set):
+    the epochs train with loss.taxo_info_nce and their logs gain mean_taxo_distance.  The index is built ONCE here, before the first
+    epoch (TaxonomyIndex.from_dataset(train_loader.dataset).to(the model's device)), when none is given.  Validation and checkpoints
+    are unchanged: a run without the keyword loads them."""
     if averaged and not (hasattr(optimizer, "averaged_parameters") and any(g.get("ema_decay") is not None for g in optimizer.param_groups)):
         raise ValueError("fit(averaged=True) needs an optimizer with averaged_parameters() and an ema_decay in at least one parameter "
                          f"group (taxoexpan_amd.optim.Adam(ema_decay=...)); got {type(optimizer).__name__}")
@@ -455,6 +505,16 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
         guard_args["in_batch"] = True
     if feature_table is not None:
         guard_args["feature_table"] = feature_table
+    if taxo_margin is not None:
+        from .loss import _checked_gamma
+        _checked_gamma(taxo_margin, "fit: taxo_margin")
+        if (taxonomy_index is None and not in_batch and loss_fn is None and getattr(train_loader, "attach_anchors", True) is not False
+                and hasattr(train_loader, "dataset")):                # (a combination train_epoch refuses is left for it to refuse)
+            from .taxometric import TaxonomyIndex
+            taxonomy_index = TaxonomyIndex.from_dataset(train_loader.dataset).to(next(model.parameters()).device)
+        guard_args["taxo_margin"] = taxo_margin
+        if taxonomy_index is not None:
+            guard_args["taxonomy_index"] = taxonomy_index
     for epoch in range(start_epoch, epochs + 1):
         mined = None
         if hard is not None and epoch >= hard["start"] and (epoch - hard["start"]) % hard["every"] == 0:
