@@ -389,6 +389,42 @@ int txe_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, 
                         const void* u_packed, void* stream);
 int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long long cnt, float* lse, void* stream);
 
+/* ---- moments of the predictive distribution (calibration): the lse mode above under a score scale beta = 1 / temperature, with the first
+ * two moments of the scaled score.  For a query row with candidates g < G:
+ *     s = the score kernel's own value (bit-identical to txe_*_score_block, exp applied where apply_exp is set),
+ *     z = s when larger_is_better, else -s,
+ *     t = fl32(beta * z): ONE fp32 multiply, rounded before anything else uses it (never contracted into the subtraction of the maximum);
+ * beta is fp32, finite and > 0.  A set of candidates (one tile's columns of a row, or the whole row) is carried as the quadruple
+ *     m = max t (NaN kept),   s0 = sum exp(d),   s1 = sum d exp(d),   s2 = sum d^2 exp(d),      d = t - m <= 0
+ * -- sums centred at the set's own maximum: nothing overflows and E[t^2] - E[t]^2 is never formed from large numbers.  A candidate with
+ * t = -Inf adds nothing to any sum (no -Inf * 0); s0 / s1 / s2 count only while m is finite.  A row's quadruples merge in float64, parts in
+ * a fixed order, no atomics: with M = max m_i, delta_i = m_i - M, w_i = exp(delta_i)
+ *     S0 = sum w s0,   S1 = sum w (s1 + delta s0),   S2 = sum w (s2 + 2 delta s1 + delta^2 s0)
+ *     lse = M + log S0,   mean = M + S1 / S0,   var = max(S2 / S0 - (S1 / S0)^2, 0),   entropy = max(log S0 - S1 / S0, 0)
+ * (a part more than 104 below M -- where fp32's exp is exactly 0 -- adds nothing to S1 and S2, as a candidate that far behind adds nothing
+ * inside a tile).  mean = E_p[t], var = Var_p[t], entropy = H(p), p = softmax(t); d lse / d beta = mean / beta, d^2 lse / d beta^2 =
+ * var / beta^2.  entropy comes from S0 and S1, not from lse - mean, which cancels for a peaked row.  out: float64 [nq][4] in that order.
+ * lse follows txe_score_lse_block's rules exactly (NaN in the row: NaN; else a +Inf: +Inf; else all -Inf: -Inf), and at beta = 1
+ * (float)lse has txe_*_score_lse_block's bits; wherever lse is not finite, mean, var and entropy are NaN.  G = 1: entropy = var = 0 and
+ * mean = (double)t; a leader more than 110 ahead of the rest after scaling: entropy = 0 and mean = M.  A row's four values depend on the
+ * row's scores and beta alone: not on the block size, the row's place in the block, the route, or the run.
+ * part_max / part_s0 / part_s1 / part_s2: [nq][txe_score_topk_tiles(G)] caller-provided scratch, rewritten by every call.
+ * TXE_ERR_ARG / TXE_ERR_WORKSPACE before any launch: txe_score_lse_block's rules, beta not finite or <= 0, a NULL scratch or output.
+ * nq == 0: TXE_OK, nothing launched.  The MLP and NTN forms mirror their lse entry points.
+ * txe_moments_merge alone: out [nq][4] from `cnt` quadruples per row ([nq][cnt] each) -- also the merge of the per-rank quadruples of a
+ * candidate-sharded loop.  cnt == 0: lse = -Inf, the other three NaN.  TXE_ERR_ARG: nq < 0, cnt < 0, a NULL pointer. */
+int txe_score_moments_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
+                            int larger_is_better, float beta, float* part_max, float* part_s0, float* part_s1, float* part_s2, double* out,
+                            void* sws, size_t sws_bytes, const void* u_packed, void* stream);
+int txe_mlp_score_moments_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                                const float* mw, int larger_is_better, float beta, float* part_max, float* part_s0, float* part_s1,
+                                float* part_s2, double* out, void* stream);
+int txe_ntn_score_moments_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                                const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
+                                float beta, float* part_max, float* part_s0, float* part_s1, float* part_s2, double* out, void* stream);
+int txe_moments_merge(const float* part_max, const float* part_s0, const float* part_s1, const float* part_s2, int nq, long long cnt,
+                      double* out, void* stream);
+
 /* ---- retrieval stage of the two-stage test protocol (data_loader/dataset.py:316-330; csrc/txe_retrieve.hip) -------------------------
  * txe_row_normalize: y[i] = x[i] / ||x[i]||_2 (fp32, any pitch, y apart from x): cosine similarity then is a plain dot product, formed by
  * txe_score_block with apply_exp = 0.  A zero-norm or non-finite row becomes NaN and gives NaN similarities.

@@ -6,5 +6,6 @@ The compute lives in taxoexpan_amd/csrc/libtxe.so (C ABI: include/txe.h).  There
 """
 from . import graph, model_zoo, ops  # noqa: F401
 from .model import TaxoExpan, encode_graph  # noqa: F401
+from . import calibrate  # noqa: F401  (temperature fit + calibration metrics over the all-candidate moments)
 
-__all__ = ["graph", "model_zoo", "ops", "TaxoExpan", "encode_graph"]
+__all__ = ["graph", "model_zoo", "ops", "calibrate", "TaxoExpan", "encode_graph"]

@@ -84,6 +84,8 @@ SIGNATURES = {
     "txe_topk_merge_wide": (I, [P, P, I, L, I, I, P, P, P, P]),
     "txe_score_lse_block": (I, [P, L, I, P, L, I, I, I, I, P, P, P, P, SZ, P, P]),
     "txe_lse_merge": (I, [P, P, I, L, P, P]),
+    "txe_score_moments_block": (I, [P, L, I, P, L, I, I, I, I, F, P, P, P, P, P, P, SZ, P, P]),
+    "txe_moments_merge": (I, [P, P, P, P, I, L, P, P]),
     "txe_bilinear_stacked_fwd": (I, [P, L, P, L, P, P, I, I, I, P, I, P, P, P]),
     "txe_bilinear_stacked_bwd_ws_bytes": (SZ, [I, I, I]),
     "txe_bilinear_stacked_bwd": (I, [P, L, P, L, P, P, I, I, I, I, P, P, P, P, L, P, P, SZ, P]),
@@ -102,6 +104,7 @@ SIGNATURES = {
     "txe_mlp_score_topk_block": (I, [P, P, I, P, P, P, I, I, P, I, I, I, P, P, P, P, P, P]),
     "txe_mlp_score_topk_wide_block": (I, [P, P, I, P, P, P, I, I, P, I, I, I, P, P, P, P, P, P, P]),
     "txe_mlp_score_lse_block": (I, [P, P, I, P, P, P, I, I, P, I, P, P, P, P]),
+    "txe_mlp_score_moments_block": (I, [P, P, I, P, P, P, I, I, P, I, F, P, P, P, P, P, P]),
     "txe_ntn_project": (I, [P, L, I, I, P, L, P, I, P, L, P]),
     "txe_ntn_query_project": (I, [P, L, I, I, P, L, I, P, L, P]),
     "txe_ntn_score_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, P, L, P]),
@@ -110,6 +113,7 @@ SIGNATURES = {
     "txe_ntn_score_topk_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, I, I, P, P, P, P, P, P]),
     "txe_ntn_score_topk_wide_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, I, I, P, P, P, P, P, P, P]),
     "txe_ntn_score_lse_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, P, P, P, P]),
+    "txe_ntn_score_moments_block": (I, [P, L, I, P, L, L, I, I, P, L, P, L, P, I, I, F, P, P, P, P, P, P]),
     "txe_score_split_ws_bytes": (SZ, [I, I, I]),
     "txe_score_count_block": (I, [P, L, I, P, L, I, I, I, P, P, I, P, P, SZ, P, P]),
     "txe_score_positives": (I, [P, L, I, P, L, I, I, I, P, P, P, SZ, P]),

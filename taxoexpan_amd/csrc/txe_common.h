@@ -215,5 +215,19 @@ static inline int lse_one_pass(int nq, long long tiles, float* part_max, float* 
     const int rc = pass();
     return rc ? rc : txe_lse_merge(part_max, part_sum, nq, tiles, lse, s);
 }
+// moments: a moments entry point's scratch and output (txe.h: txe_score_moments_block); what the three families check alike
+struct MomentParts {
+    float* part_max; float* part_s0; float* part_s1; float* part_s2; double* out;
+};
+static inline bool moments_args_ok(float beta, const float* part_max, const float* part_s0, const float* part_s1, const float* part_s2,
+                                   const double* out) {
+    return beta > 0.f && beta < INFINITY && part_max && part_s0 && part_s1 && part_s2 && out;      // (a NaN beta fails both comparisons)
+}
+// one pass leaving the tiles' (max, s0, s1, s2) quadruples, the merge
+template <class Pass>
+static inline int moments_one_pass(int nq, long long tiles, const MomentParts& p, hipStream_t s, Pass pass) {
+    const int rc = pass();
+    return rc ? rc : txe_moments_merge(p.part_max, p.part_s0, p.part_s1, p.part_s2, nq, tiles, p.out, s);
+}
 
 }  // namespace txe

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "txe_common.h"
+#include "txe_moments.h"
 
 namespace txe {
 
@@ -75,10 +76,15 @@ enum EpiMode : int {
     EPI_COUNT_GT = 1, EPI_COUNT_LT = 2,         // count mode: larger / smaller is better
     EPI_PICK = 3,                               // pick mode
     EPI_TOPK_MAX = 4, EPI_TOPK_MIN = 5,         // top-k mode: larger / smaller is better
-    EPI_LSE_MAX = 6, EPI_LSE_MIN = 7            // lse mode: larger / smaller is better
+    EPI_LSE_MAX = 6, EPI_LSE_MIN = 7,           // lse mode: larger / smaller is better
+    EPI_MOM_MAX = 8, EPI_MOM_MIN = 9            // moments mode: larger / smaller is better
 };
 // (for the launchers, which pick the lse mode's own instantiations by it; the kernels compare the field with the names in place)
 static inline bool epi_is_lse(int mode) { return mode == EPI_LSE_MAX || mode == EPI_LSE_MIN; }
+static inline bool epi_is_mom(int mode) { return mode == EPI_MOM_MAX || mode == EPI_MOM_MIN; }
+// the reducing epilogues that are instantiations of their own (gemm_tile_epilogue's RED): none / lse / moments
+enum EpiRed : int { RED_NONE = 0, RED_LSE = 1, RED_MOM = 2 };
+static inline int epi_red(int mode) { return epi_is_lse(mode) ? RED_LSE : (epi_is_mom(mode) ? RED_MOM : RED_NONE); }
 struct Epi {
     float* c;
     long long ldc;
@@ -87,7 +93,7 @@ struct Epi {
     long long ldc2;
     const float* act_src;      // act_src / mask: always readable addresses; act_on / mask_on say whether they apply
     long long ld_act;
-    float act_slope;
+    union { float act_slope; float mom_beta; };      // (moments mode applies no activation: the score scale beta rides in its slot)
     int act_on;
     const unsigned* mask;
     long long mask_ld;
@@ -109,18 +115,22 @@ struct Epi {
     int topk_k;
     union { float* topk_key; float* lse_m; };        // (one mode per launch: the lse mode's outputs share the best-k lists' slots)
     union { int* topk_idx; float* lse_s; };
-    int* topk_floor;           // [M] ordered-int keys (topk_ord): a lower bound of each row's final k-th best key, raised by every tile
+    // [M] ordered-int keys (topk_ord): a lower bound of each row's final k-th best key, raised by every tile
+    union { int* topk_floor; float* mom_s1; };       // (moments mode: s1 / s2 beside lse_m / lse_s -- slots no reducing mode reads)
     int force_bn128;           // 1: 128-wide column tiles whatever the shape (the top-k and lse scratch is laid out by them)
     // lse mode (EPI_LSE_MAX: larger is better, z = value; EPI_LSE_MIN: smaller is better, z = -value; the scoring loop's log-partition, the exact
     //   form of loss.py:52-57 over test_fast.py:121-123): nothing of the product is stored; every tile leaves, per row, the pair
     //   (max z, sum exp(z - max)) over its columns < N at lse_m / lse_s [M][column tiles] (txe_common.h: lse_max / lse_term name the
     //   special values); a merge kernel (txe_lse_merge) combines a row's pairs in tile order
+    // moments mode (EPI_MOM_MAX / EPI_MOM_MIN; the calibrated predictive distribution, txe.h: txe_score_moments_block): the lse mode over
+    //   t = fl32(mom_beta * z) with two more sums -- every tile leaves, per row, (max t, sum e, sum d e, sum d^2 e), d = t - max, e = exp(d)
+    //   (txe_moments.h) at lse_m / lse_s / mom_s1 / mom_s2 [M][column tiles]; txe_moments_merge combines a row's quadruples in tile order
     // the top-k mode's optional ceiling (the rounds of a best-k wider than TOPK_MAX; both NULL: none) shares the slots of the count
     //   mode's fields, which top-k mode never reads: column n of row m is eligible only if topk_better(topk_ceil_key[m],
     //   topk_ceil_idx[m], key, n) -- strictly worse, in the total (key, column) order, than the last entry an earlier round chose
     union { const int* cnt_off; const int* topk_ceil_idx; };
     union { const float* cnt_thr; const float* topk_ceil_key; };
-    int* cnt_out;
+    union { int* cnt_out; float* mom_s2; };
     // profiling only: the product's ALGORITHMIC flops when the operands carry tile padding (0: 2*M*N*K as launched)
     double alg_flops;
     // 1: every element is accumulated in plain k order whatever the tile count (no k-split of a last partial round): the scoring
@@ -137,6 +147,11 @@ constexpr int GEMM_ROUTE_NO_PERSIST = 1;     // whole rounds stay on gemm_kernel
 constexpr int GEMM_ROUTE_NO_TN_LDS = 2;      // split-K TN products on gemm_kernel<false,false,4,4,160> (same k order per element)
 constexpr int GEMM_ROUTE_FORCE_BN160 = 4;    // every eligible split-K product on 128 x 160 tiles, whatever its size
 
+// The moments mode's fields (mom_beta, mom_s1, mom_s2) share slots with act_slope, topk_floor and cnt_out so that Epi -- a kernel
+// argument of every GEMM -- stays the size it was; this holds as long as no path reads those three in moments mode (act_on is 0
+// there and the reducing branches of gemm_tile_epilogue return before the other modes' code)
+static_assert(sizeof(Epi) == 192, "Epi grew: the moments mode's fields are meant to ride in slots of modes that never run with it");
+// (epi_plain writes act_slope = 1: a moments entry point sets mom_beta AFTER it)
 static inline Epi epi_plain(float* c, long long ldc, int cols) {
     Epi e;
     e.c = c; e.ldc = ldc; e.cols_main = cols; e.c2 = nullptr; e.ldc2 = 0;
@@ -479,9 +494,10 @@ __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(const Epi E, const
 // for the count mode) -- plain / exp / mask / activation stores, the pick, count and best-k modes.  Shared by gemm_kernel and the
 // bf16-pipe product of txe_gemm_split.hip (the scoring loop's four entry points must produce bit-identical scores: ONE epilogue).
 // cnt_pb / cnt_np / cnt_th: the count mode's per-row positive range and first thresholds, fetched by the caller before its k-loop.
-// LSE: the lse mode (EPI_LSE_MAX / EPI_LSE_MIN) and nothing else -- its own instantiation of every kernel that ends here, so that the code of the
-// other modes (the training GEMMs among them) is what it was without it.
-template <int BN, int SMEM, bool LSE = false>
+// RED (EpiRed): RED_LSE = the lse mode (EPI_LSE_MAX / EPI_LSE_MIN) and nothing else, RED_MOM = the moments mode (EPI_MOM_MAX / EPI_MOM_MIN)
+// and nothing else -- each its own instantiation of every kernel that ends here, so that the code of the other modes (the training GEMMs
+// among them) is what it was without them.
+template <int BN, int SMEM, int RED = RED_NONE>
 __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, const int m0, const int n0, const int M, const int N, const int tn,
                                                    const int nbn, const int zslice, const int cnt_pb, const int cnt_np, const float (&cnt_th)[8]) {
     constexpr int CLD = BN + 4;
@@ -574,7 +590,51 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
         }
         return;
     }
-    if constexpr (LSE) {
+    if constexpr (RED == RED_MOM) {
+        // moments: the lse walk below over t = fl32(beta * z) -- two threads per row, each walks its half row twice (ascending columns):
+        // the maximum of t over the columns < N, shared by the pair (NaN kept), then s0 / s1 / s2 in four interleaved chains each; the
+        // even thread adds the pair's sums (its own first) and writes the row's quadruple of this column tile.  At beta = 1 (max, s0) are
+        // the lse mode's pair, bit for bit.
+        static_assert(GEMM_THREADS == 2 * GEMM_BM, "two threads per tile row");
+        constexpr int HW = BN / 2;
+        const int row = threadIdx.x >> 1, half = threadIdx.x & 1;
+        const int m = m0 + row, nb = n0 + half * HW;
+        const bool larger = E.cnt_mode == EPI_MOM_MAX;
+        const float beta = E.mom_beta;
+        const float* src = Cs + row * CLD + half * HW;
+        float mx = -INFINITY;
+        bool bad = false;
+#pragma unroll 4
+        for (int j = 0; j < HW / 4; ++j) {
+            const float4 t4 = *reinterpret_cast<const float4*>(src + 4 * j);
+            const float v4[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                mom_max_step(mom_scaled(E.apply_exp ? __expf(v4[q]) : v4[q], larger, beta), nb + 4 * j + q < N, mx, bad);
+        }
+        mx = bad ? __builtin_nanf("") : mx;
+        mx = lse_max(mx, __shfl_xor(mx, 1, 64));
+        float p0[4] = {0.f, 0.f, 0.f, 0.f}, p1[4] = {0.f, 0.f, 0.f, 0.f}, p2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int j = 0; j < HW / 4; ++j) {
+            const float4 t4 = *reinterpret_cast<const float4*>(src + 4 * j);
+            const float v4[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                mom_sum_step(mom_scaled(E.apply_exp ? __expf(v4[q]) : v4[q], larger, beta), nb + 4 * j + q < N, mx, p0[q], p1[q], p2[q]);
+        }
+        const float s0 = (p0[0] + p0[1]) + (p0[2] + p0[3]), s1 = (p1[0] + p1[1]) + (p1[2] + p1[3]), s2 = (p2[0] + p2[1]) + (p2[2] + p2[3]);
+        const float o0 = __shfl_xor(s0, 1, 64), o1 = __shfl_xor(s1, 1, 64), o2 = __shfl_xor(s2, 1, 64);
+        if (half == 0 && m < M) {
+            const long long o = (long long)m * nbn + tn;
+            E.lse_m[o] = mx;
+            E.lse_s[o] = s0 + o0;
+            E.mom_s1[o] = s1 + o1;
+            E.mom_s2[o] = s2 + o2;
+        }
+        return;
+    }
+    if constexpr (RED == RED_LSE) {
         // log-partition: two threads per row, each walks its half row twice (ascending columns): the maximum of z over the columns < N
         // -- the pair then shares the larger one, NaN kept -- and the sum of exp(z - max) in four interleaved chains; the even thread
         // adds the pair's sums (its own first) and writes the row's (max, sum) of this column tile.  A row's pair depends on the row's
@@ -747,14 +807,15 @@ __device__ __forceinline__ void gemm_tile_epilogue(const Epi& E, float* smem, co
     }
 }
 
-// BNX: the tile width BN, or GEMM_BN_LSE -- 128-wide tiles that end in the epilogue's lse mode (an instantiation of its own; a further
-// template parameter would rename every kernel the profiles know)
+// BNX: the tile width BN, or GEMM_BN_LSE / GEMM_BN_MOM -- 128-wide tiles that end in the epilogue's lse / moments mode (instantiations of
+// their own; a further template parameter would rename every kernel the profiles know)
 constexpr int GEMM_BN_LSE = -128;
+constexpr int GEMM_BN_MOM = -129;
 template <bool AK, bool BKC, int VA, int VB, int BNX>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(VMat A, VMat B, const Epi E, const int M, const int N,
                                                                 const int K, const int ksplit, const Tail T) {
-    constexpr int BN = BNX < 0 ? -BNX : BNX;
-    constexpr bool LSE = BNX < 0;
+    constexpr int BN = BNX < 0 ? 128 : BNX;
+    constexpr int RED = BNX == GEMM_BN_LSE ? RED_LSE : (BNX == GEMM_BN_MOM ? RED_MOM : RED_NONE);
     using GA = StageGeom<AK, VA, GEMM_BM>;
     using GB = StageGeom<BKC, VB, BN>;
     constexpr int ASZ = GA::LDS, BSZ = GB::LDS;
@@ -950,7 +1011,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(VMat A, VMat B, c
         }
         return;
     }
-    gemm_tile_epilogue<BN, SMEM, LSE>(E, smem, m0, n0, M, N, tn, nbn, zslice, cnt_pb, cnt_np, cnt_th);
+    gemm_tile_epilogue<BN, SMEM, RED>(E, smem, m0, n0, M, N, tn, nbn, zslice, cnt_pb, cnt_np, cnt_th);
 }
 
 // ---- whole rounds of a plain product: persistent workgroups, the C tile drained under the NEXT tile's k-loop ---------------------
@@ -1241,6 +1302,13 @@ static inline void gemm_launch_v(int bn, dim3 grid, hipStream_t stream, const VM
             hipLaunchKernelGGL((gemm_kernel<AK, BKC, VA, VB, GEMM_BN_LSE>), grid, dim3(GEMM_THREADS), 0, stream, A, B, E, M, N, K, ksplit, T);
             return;
         }
+        if (epi_is_mom(E.cnt_mode)) {                    // (the moments mode: the same restriction, its own instantiation)
+            static char mom_name[48];
+            if (!mom_name[0]) snprintf(mom_name, sizeof(mom_name), "gemm_kernel<true, true, %d, %d, %d>", VA, VB, GEMM_BN_MOM);
+            ProfScope prof(mom_name, stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
+            hipLaunchKernelGGL((gemm_kernel<AK, BKC, VA, VB, GEMM_BN_MOM>), grid, dim3(GEMM_THREADS), 0, stream, A, B, E, M, N, K, ksplit, T);
+            return;
+        }
     }
     ProfScope prof(name, stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
     if constexpr (!BKC && VA == 4 && VB == 4) {      // (160-wide tiles: B row-contiguous -- weight gradients (TN), dZ = d_hg W (NN))
@@ -1269,8 +1337,8 @@ template <bool AK, bool BKC>
 static inline int gemm_launch_layout(const VMat& A, const VMat& B, const Epi& E_in, int M, int N, int K, int splits,
                                      hipStream_t stream, void* tail_ws = nullptr, size_t tail_ws_bytes = 0) {
     if (M <= 0 || N <= 0) return TXE_OK;
-    // the lse mode exists for NT products on 128-wide tiles only (gemm_launch_v); no other instance has its epilogue
-    if (epi_is_lse(E_in.cnt_mode) && !(AK && BKC && E_in.force_bn128 && splits <= 1)) return TXE_ERR_ARG;
+    // the lse and moments modes exist for NT products on 128-wide tiles only (gemm_launch_v); no other instance has their epilogues
+    if (epi_red(E_in.cnt_mode) != RED_NONE && !(AK && BKC && E_in.force_bn128 && splits <= 1)) return TXE_ERR_ARG;
     Epi E = E_in;
     {   // the epilogue loads its extras unconditionally: give the unused ones a readable dummy address
         const void* valid = E.c ? (const void*)E.c : (const void*)E.c2;

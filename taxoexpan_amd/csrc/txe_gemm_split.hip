@@ -158,7 +158,8 @@ __device__ __forceinline__ void gemm_nt_split_slow_tile(const char* __restrict__
 }
 
 // EPI: 0 = plain stores from the accumulators; 1 = the same with the dropout-mask / activation factors; 2 = the tile goes through LDS into
-// gemm_kernel's own epilogue (txe_gemm.h gemm_tile_epilogue: exp, pick, count and best-k modes -- the scoring loop), E = its arguments; 3 = as 2, into that epilogue's lse mode
+// gemm_kernel's own epilogue (txe_gemm.h gemm_tile_epilogue: exp, pick, count and best-k modes -- the scoring loop), E = its arguments; 3 = as 2, into that epilogue's lse mode;
+// 4 = as 2, into its moments mode
 template <int MI, int NST, int MINB, int EPI = 0>
 __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGemm p, const Epi E) {
     constexpr int NA = 2 * MI, NB = 4;                      // A / B fragment blocks per tile
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(256, MINB) void gemm_nt_split_kernel(const SplitGem
                     Cs[row * 132 + 64 * wn + 2 * (l & 31) + j] = acc[i][j][e];
                 }
         __syncthreads();
-        gemm_tile_epilogue<128, NST * STAGE_U4 * 4, EPI == 3>(E, Cs, tm * 128, tn * SPL_BN, p.M, p.N, tn, p.nbn, 0, cnt_pb, cnt_np, cnt_th);
+        gemm_tile_epilogue<128, NST * STAGE_U4 * 4, EPI == 3 ? RED_LSE : (EPI == 4 ? RED_MOM : RED_NONE)>(E, Cs, tm * 128, tn * SPL_BN, p.M, p.N, tn, p.nbn, 0, cnt_pb, cnt_np, cnt_th);
         return;
     }
     // accumulator register e of block (i, j): row 32 i + (e & 3) + 8 (e >> 2) + 4 (lane >> 5), slot lane & 31 of B fragment 2 wn + j =
@@ -720,6 +721,12 @@ int gemm_nt_split_epi_launch(const void* Ap, const void* Bp, const Epi& E, int M
     if (epi_is_lse(E.cnt_mode)) {                       // the lse mode: its own instantiation (gemm_tile_epilogue's LSE)
         ProfScope prof("gemm_nt_split_kernel<2, 3, 2, 3>", stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
         hipLaunchKernelGGL((gemm_nt_split_kernel<2, 3, 2, 3>), dim3(p.nbm * p.nbn), dim3(256), 0, stream, p, E2);
+        TXE_CHECK_LAUNCH();
+        return TXE_OK;
+    }
+    if (epi_is_mom(E.cnt_mode)) {                       // the moments mode: its own instantiation too
+        ProfScope prof("gemm_nt_split_kernel<2, 3, 2, 4>", stream, E.alg_flops > 0.0 ? E.alg_flops : 2.0 * M * (double)N * K, 0);
+        hipLaunchKernelGGL((gemm_nt_split_kernel<2, 3, 2, 4>), dim3(p.nbm * p.nbn), dim3(256), 0, stream, p, E2);
         TXE_CHECK_LAUNCH();
         return TXE_OK;
     }

@@ -949,4 +949,29 @@ int txe_score_lse_block(const float* Q, long long ld_q, int nq, const float* U, 
     });
 }
 
+// Fused scoring + moments of one block of the loop (txe.h): txe_score_lse_block over t = fl32(beta * z) with the first two moments of t
+// under softmax(t) -- every 128 x 128 tile leaves each row's quadruple (max t, s0, s1, s2) at part_max / part_s0 / part_s1 / part_s2
+// [nq][txe_score_topk_tiles(G)] (scratch), txe_moments_merge combines them in tile order into out [nq][4] = (lse, mean, var, entropy).
+// The same MFMA kernel and k order as txe_score_block: the scores behind the sums are bit-identical to the materialised ones.  G >= 1.
+int txe_score_moments_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, int G, int r, int apply_exp,
+                            int larger_is_better, float beta, float* part_max, float* part_s0, float* part_s1, float* part_s2, double* out,
+                            void* sws, size_t sws_bytes, const void* u_packed, void* stream) {
+    if (nq < 0 || G < 1 || r < 1 || ld_u < r || (nq > 1 && ld_q < r) || !Q || !U || !moments_args_ok(beta, part_max, part_s0, part_s1, part_s2, out))
+        return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    if (sws && sws_bytes < score_split_need(nq, G, r, u_packed != nullptr)) return TXE_ERR_WORKSPACE;      // before the first launch
+    hipStream_t s = (hipStream_t)stream;
+    VMat A = vmat_plain(Q, ld_q, nq, r);
+    VMat B = vmat_plain(U, ld_u, G, r);
+    Epi E = epi_plain(part_max, 0, G);                              // c is never written in moments mode
+    E.apply_exp = apply_exp;
+    E.cnt_mode = larger_is_better ? EPI_MOM_MAX : EPI_MOM_MIN;
+    E.mom_beta = beta; E.lse_m = part_max; E.lse_s = part_s0; E.mom_s1 = part_s1; E.mom_s2 = part_s2;
+    E.force_bn128 = 1;                                              // (the scratch layout counts 128-wide column tiles)
+    return moments_one_pass(nq, txe_score_topk_tiles(G), {part_max, part_s0, part_s1, part_s2, out}, s, [&] {
+        const int sr = score_split(Q, ld_q, nq, U, ld_u, G, r, E, sws, sws_bytes, u_packed, s);
+        return sr == 0 ? gemm_nt(A, B, E, nq, G, r, 1, s) : (sr < 0 ? sr : TXE_OK);
+    });
+}
+
 }  // extern "C"

@@ -14,6 +14,7 @@
 // no partial sum of either form comes near FLT_MAX (|w2| * |a + b| summed over h stays under 2^121), so the two forms then produce the
 // same non-finite pattern: none.
 #include "txe_common.h"
+#include "txe_moments.h"
 
 namespace txe {
 
@@ -160,14 +161,17 @@ struct MlpArgs {
     const float* mw; int Hp;                        // w2 (padded), b2, lim
     float* S; long long ld_s;                       // store
     const int* pos_off; const float* thr; int* counts; int larger;   // count
-    int k; float* part_key; int* part_idx; int* floor_ws;            // top-k
-    const float* ceil_key; const int* ceil_idx;                      // top-k: the rows' ceilings of a wide best-k's later rounds (NULL: none)
-    float* part_max; float* part_sum;                                // lse
+    // (moments: the score scale and the two further sums ride in top-k's slots, which a moments launch never reads)
+    union { int k; float beta; }; union { float* part_key; float* part_s1; }; int* part_idx; int* floor_ws;   // top-k
+    union { const float* ceil_key; float* part_s2; }; const int* ceil_idx;   // top-k: the rows' ceilings of a wide best-k's later rounds (NULL: none)
+    float* part_max; float* part_sum;                                // lse; moments: (max, s0)
 };
+
+static_assert(sizeof(MlpArgs) == 176, "MlpArgs grew: the moments mode's fields are meant to ride in top-k's slots");
 
 // (MLP_TOPK_CEIL: MLP_TOPK under the rows' ceilings, a later round of a wide best-k -- an instantiation of its own, so that the k <= 8
 //  path's kernel keeps its registers and its occupancy)
-enum { MLP_STORE = 0, MLP_COUNT = 1, MLP_TOPK = 2, MLP_LSE = 3, MLP_TOPK_CEIL = 4 };
+enum { MLP_STORE = 0, MLP_COUNT = 1, MLP_TOPK = 2, MLP_LSE = 3, MLP_TOPK_CEIL = 4, MLP_MOM = 5 };
 
 // One 128-candidate x 64-query tile per workgroup of 256 threads; thread (tg, tq) = (tid & 15, tid >> 4) owns candidates
 // g0 + {tg*4 .. tg*4+3, 64 + tg*4 .. 64 + tg*4+3} and queries q0 + tq*4 .. tq*4+3: 32 pairs.  A and -B go through LDS in 16-step
@@ -318,6 +322,39 @@ __global__ __launch_bounds__(256) void mlp_pair_kernel(const MlpArgs a) {
                 const long long o = (long long)q * nbn + blockIdx.x;
                 a.part_max[o] = mx;
                 a.part_sum[o] = s;
+            }
+        }
+    } else if constexpr (MODE == MLP_MOM) {
+        // moments: the lse mode above over t = fl32(beta * z) (txe_moments.h) -- each thread's 8 columns, then a butterfly over the 16
+        // threads of the row, once for the maximum (NaN kept) and once for the three sums: a fixed order
+        const int nbn = (a.G + MLP_BG - 1) / MLP_BG;
+        const bool larger = a.larger != 0;
+        const float beta = a.beta;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = q0 + tq * 4 + i;
+            float mx = -INFINITY;
+            bool bad = false;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mom_max_step(mom_scaled(acc[i][j], larger, beta), gcol[j] < a.G, mx, bad);
+            mx = bad ? __builtin_nanf("") : mx;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) mx = lse_max(mx, __shfl_xor(mx, o, 64));
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mom_sum_step(mom_scaled(acc[i][j], larger, beta), gcol[j] < a.G, mx, s0, s1, s2);
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                s0 += __shfl_xor(s0, o, 64);
+                s1 += __shfl_xor(s1, o, 64);
+                s2 += __shfl_xor(s2, o, 64);
+            }
+            if (tg == 0 && q < a.nq) {
+                const long long o = (long long)q * nbn + blockIdx.x;
+                a.part_max[o] = mx;
+                a.part_sum[o] = s0;
+                a.part_s1[o] = s1;
+                a.part_s2[o] = s2;
             }
         }
     } else {
@@ -511,6 +548,20 @@ int txe_mlp_score_lse_block(const float* Ap, const int* flag_a, int G, const flo
     MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
     a.larger = larger_is_better ? 1 : 0; a.part_max = part_max; a.part_sum = part_sum;
     return lse_one_pass(nq, (G + MLP_BG - 1) / MLP_BG, part_max, part_sum, lse, s, [&] { return mlp_launch<MLP_LSE>(a, s, "mlp_pair_kernel[lse]"); });
+}
+
+// model_zoo.py:285-298 under a score scale -- the moments of every query's predictive distribution over all candidates,
+// txe_score_moments_block's definition, scratch and merge (the pair kernel's tiles are 128 candidates wide too)
+int txe_mlp_score_moments_block(const float* Ap, const int* flag_a, int G, const float* nB, const float* c, const int* flag_b, int nq, int H,
+                                const float* mw, int larger_is_better, float beta, float* part_max, float* part_s0, float* part_s1,
+                                float* part_s2, double* out, void* stream) {
+    if (!TXE_MLP_ARGS_OK || G < 1 || !moments_args_ok(beta, part_max, part_s0, part_s1, part_s2, out)) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    MlpArgs a = mlp_args(Ap, flag_a, G, nB, c, flag_b, nq, H, mw);
+    a.larger = larger_is_better ? 1 : 0; a.beta = beta; a.part_max = part_max; a.part_sum = part_s0; a.part_s1 = part_s1; a.part_s2 = part_s2;
+    return moments_one_pass(nq, (G + MLP_BG - 1) / MLP_BG, {part_max, part_s0, part_s1, part_s2, out}, s,
+                            [&] { return mlp_launch<MLP_MOM>(a, s, "mlp_pair_kernel[moments]"); });
 }
 
 }  // extern "C"

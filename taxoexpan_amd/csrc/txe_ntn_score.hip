@@ -51,9 +51,13 @@ struct NtnArgs {
 // j + 1 is fetched under the last MFMA block of slice j.  A k-tile that lies wholly inside K takes the 16-byte row loader, a ragged
 // last one the element loader (both zero what lies past M / N / K).  V: the operands' common vector width (4, or 1 on odd pitches).
 // LSE: the tile ends in the epilogue's lse mode (Epi: EPI_LSE_MAX / EPI_LSE_MIN) -- an instantiation of its own
-template <int V, bool LSE = false>
+// VX: the vector width V, or -V -- the tile ends in the epilogue's moments mode (EPI_MOM_MAX / EPI_MOM_MIN), an instantiation of its own
+// (gemm_kernel's BNX pattern: the existing instantiations keep their names)
+template <int VX, bool LSE = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void ntn_score_kernel(const VMat A, VMat B, const NtnArgs P, const Epi E, const int M, const int N,
                                                                     const int K) {
+    constexpr int V = VX < 0 ? -VX : VX;
+    constexpr int RED = VX < 0 ? RED_MOM : (LSE ? RED_LSE : RED_NONE);
     constexpr int BN = 128, MI = 2, NJ = 2, CLD = BN + 4;
     using GA = StageGeom<true, V, GEMM_BM>;
     using GB = StageGeom<true, V, BN>;
@@ -200,7 +204,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void ntn_score_kernel(const VMat A
                 Cs[row * CLD + wn0 + j * 32 + (l & 31)] = sc[i][j][e];
             }
     __syncthreads();
-    gemm_tile_epilogue<BN, SMEM, LSE>(E, smem, m0, n0, M, N, tn, nbn, 0, cnt_pb, cnt_np, cnt_th);
+    gemm_tile_epilogue<BN, SMEM, RED>(E, smem, m0, n0, M, N, tn, nbn, 0, cnt_pb, cnt_np, cnt_th);
 }
 
 // out[j][i] = <Wv[j], X[i]> (+ bias[j]) for i < n, j < k: the candidate side's a (X = hg, Wv = V1, bias = W.bias) and the query side's c
@@ -264,6 +268,9 @@ static int ntn_launch(const NtnCall& n, int N, Epi E, hipStream_t s, const char*
     if (epi_is_lse(E.cnt_mode)) {
         if (v4) hipLaunchKernelGGL((ntn_score_kernel<4, true>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
         else hipLaunchKernelGGL((ntn_score_kernel<1, true>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
+    } else if (epi_is_mom(E.cnt_mode)) {
+        if (v4) hipLaunchKernelGGL((ntn_score_kernel<-4>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
+        else hipLaunchKernelGGL((ntn_score_kernel<-1>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
     } else if (v4) hipLaunchKernelGGL((ntn_score_kernel<4>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
     else hipLaunchKernelGGL((ntn_score_kernel<1>), dim3(tiles), dim3(GEMM_THREADS), 0, s, A, B, P, E, n.nq, N, n.r);
     TXE_CHECK_LAUNCH();
@@ -375,6 +382,22 @@ int txe_ntn_score_lse_block(const float* Q, long long ld_q, int nq, const float*
     E.lse_m = part_max; E.lse_s = part_sum;
     hipStream_t s = (hipStream_t)stream;
     return lse_one_pass(nq, txe_score_topk_tiles(G), part_max, part_sum, lse, s, [&] { return ntn_launch(n, G, E, s, "ntn_score_kernel[lse]"); });
+}
+
+// model_zoo.py:331-346 under a score scale -- the moments of every query's predictive distribution over all candidates,
+// txe_score_moments_block's definition, scratch and merge
+int txe_ntn_score_moments_block(const float* Q, long long ld_q, int nq, const float* U, long long ld_u, long long slice_u, int G, int r,
+                                const float* a, long long ld_a, const float* c, long long ld_c, const float* u, int k, int larger_is_better,
+                                float beta, float* part_max, float* part_s0, float* part_s1, float* part_s2, double* out, void* stream) {
+    TXE_NTN_CALL;
+    if (!ntn_call_ok(n) || G < 1 || !moments_args_ok(beta, part_max, part_s0, part_s1, part_s2, out)) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    Epi E = epi_plain(part_max, 0, G);                              // c is never written in moments mode
+    E.cnt_mode = larger_is_better ? EPI_MOM_MAX : EPI_MOM_MIN;
+    E.mom_beta = beta; E.lse_m = part_max; E.lse_s = part_s0; E.mom_s1 = part_s1; E.mom_s2 = part_s2;
+    hipStream_t s = (hipStream_t)stream;
+    return moments_one_pass(nq, txe_score_topk_tiles(G), {part_max, part_s0, part_s1, part_s2, out}, s,
+                            [&] { return ntn_launch(n, G, E, s, "ntn_score_kernel[moments]"); });
 }
 
 #undef TXE_NTN_CALL

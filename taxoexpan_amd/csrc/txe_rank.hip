@@ -6,6 +6,7 @@
 // One workgroup per query streams the G scores of its row once (coalesced), compares against the query's
 // few positives held in LDS, and reduces integer counts -- exact, no floating point accumulation.
 #include "txe_common.h"
+#include "txe_moments.h"
 
 namespace txe {
 
@@ -277,6 +278,46 @@ __global__ __launch_bounds__(256) void lse_merge_kernel(const float* __restrict_
     if (l == 0) lse[q] = (fabsf(M) < INFINITY && S != 1.0) ? (float)((double)M + log(S)) : M;
 }
 
+// (lse, mean, var, entropy)[q] of row q from its `cnt` quadruples (txe_moments.h: m = max t, s0 / s1 / s2 = sum of exp(d), d exp(d),
+// d^2 exp(d), d = t - m, over a part of the row) -- lse_merge_kernel's frame: one wave per row, in float64, M = the largest m (NaN kept),
+// then with delta = m - M and w = exp(delta) the lanes' strided shares of
+//   S0 = sum w s0,  S1 = sum w (s1 + delta s0),  S2 = sum w (s2 + 2 delta s1 + delta^2 s0)
+// in ascending order and a fixed butterfly -- no atomics, no dependence on the order of arrival.  S0 is lse_merge_kernel's sum,
+// expression for expression.  A part more than MOM_FAR below M adds nothing to S1 and S2: fp32's exp(-104) is exactly 0, so a candidate
+// that far behind the leader inside the leader's own tile adds nothing either -- a row is treated alike wherever its tile edges fall, and
+// what is dropped is below e^-104 of the sums.
+constexpr double MOM_FAR = 104.0;
+__global__ __launch_bounds__(256) void moments_merge_kernel(const float* __restrict__ pm, const float* __restrict__ p0, const float* __restrict__ p1,
+                                                            const float* __restrict__ p2, int nq, long long cnt, double* __restrict__ out) {
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (q >= nq) return;                             // (whole waves leave: the shuffles below stay uniform)
+    const long long base = (long long)q * cnt;
+    float M = -INFINITY;
+    for (long long e = l; e < cnt; e += 64) M = lse_max(M, pm[base + e]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = lse_max(M, __shfl_xor(M, o, 64));
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0;
+    if (fabsf(M) < INFINITY)
+        for (long long e = l; e < cnt; e += 64) {
+            const float m = pm[base + e];
+            if (m == -INFINITY) continue;
+            const double delta = (double)m - (double)M, w = exp(delta), s0 = (double)p0[base + e];
+            S0 += s0 * w;
+            if (delta >= -MOM_FAR) {
+                const double s1 = (double)p1[base + e], s2 = (double)p2[base + e];
+                S1 += w * (s1 + delta * s0);
+                S2 += w * (s2 + 2.0 * delta * s1 + delta * delta * s0);
+            }
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        S0 += __shfl_xor(S0, o, 64);
+        S1 += __shfl_xor(S1, o, 64);
+        S2 += __shfl_xor(S2, o, 64);
+    }
+    if (l == 0) mom_finish(M, S0, S1, S2, out + 4LL * q);
+}
+
 }  // namespace txe
 
 using namespace txe;
@@ -321,6 +362,18 @@ int txe_lse_merge(const float* part_max, const float* part_sum, int nq, long lon
     if (nq == 0) return TXE_OK;
     ProfScope prof("lse_merge_kernel", (hipStream_t)stream, 8.0 * nq * (double)cnt, 1);
     hipLaunchKernelGGL(lse_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, part_max, part_sum, nq, cnt, lse);
+    TXE_CHECK_LAUNCH();
+    return TXE_OK;
+}
+
+// part_max / part_s0 / part_s1 / part_s2 [nq][cnt] -> out [nq][4] float64 = (lse, mean, var, entropy) (txe.h).  cnt == 0 runs the same
+// kernel (no quadruple is read): lse = -Inf, the other three NaN.
+int txe_moments_merge(const float* part_max, const float* part_s0, const float* part_s1, const float* part_s2, int nq, long long cnt,
+                      double* out, void* stream) {
+    if (nq < 0 || cnt < 0 || !part_max || !part_s0 || !part_s1 || !part_s2 || !out) return TXE_ERR_ARG;
+    if (nq == 0) return TXE_OK;
+    ProfScope prof("moments_merge_kernel", (hipStream_t)stream, 16.0 * nq * (double)cnt, 1);
+    hipLaunchKernelGGL(moments_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, (hipStream_t)stream, part_max, part_s0, part_s1, part_s2, nq, cnt, out);
     TXE_CHECK_LAUNCH();
     return TXE_OK;
 }

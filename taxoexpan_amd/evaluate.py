@@ -119,6 +119,30 @@ def _nll_of(lse, thr, pos_off, larger_is_better):
     return _per_query_means(lse.to(torch.float64)[qid] - (z if larger_is_better else -z), pos_off)
 
 
+def _scaled(s, beta, larger_is_better):
+    """t = fl32(beta * z) of fp32 scores s as the moments kernels form it (one fp32 product; z = s or its negative), in float64"""
+    z = s.float() if larger_is_better else -s.float()
+    return (z * torch.tensor(beta, dtype=torch.float32, device=s.device)).to(torch.float64)
+
+
+def _predictive(model, hg, qf, mom, ranks, pos_off, beta, larger_is_better, qblock):
+    """evaluate's `predictive` metrics from the moments of every query's distribution and its first predicted parent: (entropy /
+    confidence / ece floats, the per-query device tensors)"""
+    from .calibrate import _ece_device
+    dev = hg.device
+    cols = torch.arange(hg.shape[0], device=dev)
+    _ids, top = _best_parents(model, hg, qf, cols, 1, larger_is_better, qblock, with_scores=True)
+    top1_prob = torch.exp(_scaled(top[:, 0], beta, larger_is_better) - mom.lse)
+    off = torch.as_tensor(pos_off).to(device=dev, dtype=torch.int64)
+    Q = off.numel() - 1
+    qid = torch.repeat_interleave(torch.arange(Q, device=dev), off[1:] - off[:-1])
+    best = torch.full((Q,), 2 ** 31 - 1, dtype=torch.int32, device=dev).scatter_reduce_(0, qid, ranks.to(torch.int32), "amin")
+    correct = best == 1
+    vals = torch.stack([mom.entropy.mean(), top1_prob.mean(), _ece_device(top1_prob, correct)]).cpu().tolist()
+    return dict(entropy=vals[0], confidence=vals[1], ece=vals[2]), \
+        dict(lse=mom.lse, mean=mom.mean, var=mom.var, entropy=mom.entropy, top1_prob=top1_prob, correct=correct)
+
+
 def _retrieval_masks(dataset, queries, index):
     """node2masks[q] (descendants, parents, q itself, roots: dataset.py:262-268) as candidate rows, CSR over the queries"""
     off, idx = [0], []
@@ -230,7 +254,7 @@ def _taxonomic(index_dev, best, pos_off, gold_idx, Q):
 
 
 def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0, batch_size=-1, case=None, metric_names=CASE_METRICS,
-             topk=5, retrieve=None, nll=False, taxonomic=False, taxonomy_index=None):
+             topk=5, retrieve=None, nll=False, taxonomic=False, taxonomy_index=None, temperature=None, predictive=False):
     """dataset: taxoexpan_amd.dataset.MaskedGraphDataset in 'validation' or 'test' mode.  Returns (metrics dict, ranks int32
     [n_positives], pos_off [Q+1], queries list).  Queries whose true parents are not candidate positions are skipped, like the
     reference's rearrange() would fail on them.
@@ -265,12 +289,29 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     taxometric.TaxonomyIndex of that taxonomy (or its .to(device)) to reuse; default TaxonomyIndex.from_dataset(dataset).  "wu_palmer"
     in `metric_names` adds the first prediction's value as a per-query column of the case study (ValueError before any launch without
     `taxonomic`).  Every other metric, the ranks and the offsets are bit-equal to a call without it.
+    temperature=T (finite and > 0, else ValueError before any launch; calibrate.fit_temperature finds it on the validation split): the
+    predictive distribution is p = softmax(t) over ALL candidates, t = fl32(z / T) (scoring.score_moments_fused: one pass
+    over the candidates, no score matrix), and nll=True reports the NLL under it -- calibrate's f(1 / T), the true parents' terms taken
+    as their own t.  predictive: truthy (True, or a dict -- an empty one too) = three more metrics of that distribution (at T = 1 without
+    `temperature`): entropy = the mean over queries of H(p); confidence = the mean probability of the first predicted parent,
+    exp(t_top - lse); ece = the expected calibration error of that probability over 10 equal-width bins (the sum of share x |accuracy -
+    mean confidence|; accurate = the query's best rank is 1).  A dict is also filled with the per-query device tensors lse, mean, var,
+    entropy, top1_prob (float64 [Q]) and correct (bool [Q]).  Neither goes with retrieve=k (ValueError before any launch).  Ranks,
+    offsets and every other metric are bit-equal to a call without the two keywords -- nll too while `temperature` is None (it stays on
+    log_partition_fused's fp32 lse then) --; without both the code path is what it was.
     Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): evaluate(model, ...)` evaluates the averaged
     model -- the parameters are the averages inside the context; or load a checkpoint's with trainer.load_averaged."""
     device = torch.device(device)
+    want_pred = isinstance(predictive, dict) or bool(predictive)
+    calibrated = temperature is not None or want_pred
+    if calibrated:
+        beta = scoring._beta_of(1.0 if temperature is None else temperature)
     if retrieve is not None:
         if nll:
             raise ValueError("evaluate: nll=True scores every candidate; with retrieve=k the partition over a retrieved subset is not the likelihood")
+        if calibrated:
+            raise ValueError("evaluate: temperature / predictive describe the distribution over every candidate; with retrieve=k the partition "
+                             "over a retrieved subset is not the likelihood")
         retrieve = _retrieve_args(retrieve, None, None)[0]
     want_taxo = isinstance(taxonomic, dict) or bool(taxonomic)
     if case is not None and "wu_palmer" in metric_names and not want_taxo:
@@ -295,7 +336,24 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     pos_idx = np.concatenate(pos_lists).astype(np.int64) if pos_lists else np.zeros(0, dtype=np.int64)
     qf = dataset.node_features[torch.as_tensor(queries, dtype=torch.long)].to(device)
     with torch.no_grad():
-        if retrieve is None:
+        if retrieve is None and calibrated:
+            ranks, thr = _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock, with_thr=True) if nll else \
+                (_ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock), None)
+            if queries:
+                if want_pred or nll and temperature is not None:          # (a temperature alone asks for nothing that needs the pass)
+                    mom = scoring.score_moments_fused(model.match, hg, qf, larger_is_better, 1.0 / beta, block=qblock)
+                if nll and temperature is not None:
+                    nll_value = _nll_of(mom.lse, _scaled(thr, beta, larger_is_better), pos_off, True)
+                elif nll:                                                 # no temperature: the value a call without `predictive` reports
+                    nll_value = _nll_of(log_partition_fused(model.match, hg, qf, larger_is_better, block=qblock), thr, pos_off, larger_is_better)
+                if want_pred:
+                    pred_metrics, pred_tensors = _predictive(model, hg, qf, mom, ranks, pos_off, beta, larger_is_better, qblock)
+            else:
+                nll_value = float("nan")
+                pred_metrics, pred_tensors = dict(entropy=float("nan"), confidence=float("nan"), ece=float("nan")), {}
+            if isinstance(predictive, dict):
+                predictive.update(pred_tensors)
+        elif retrieve is None:
             if nll:
                 ranks, thr = _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock, with_thr=True)
                 nll_value = _nll_of(log_partition_fused(model.match, hg, qf, larger_is_better, block=qblock), thr, pos_off, larger_is_better) \
@@ -353,11 +411,13 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
         metrics["nll"] = nll_value
     if want_taxo:
         metrics.update(taxo_metrics)
+    if want_pred:
+        metrics.update(pred_metrics)
     return metrics, ranks, pos_off, queries
 
 
 def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-1, save=None, topk=5, normalize=False, qblock=1024,
-          seed=0, retrieve=None, with_scores=False):
+          seed=0, retrieve=None, with_scores=False, temperature=None):
     """infer.py:77-159: the `topk` best parents of every NEW term.  dataset: MaskedGraphDataset in 'test' mode (infer.py:43-57);
     new_taxons: path of the `<name>\t<v0 v1 ...>` file (infer.py:23-38) or an already loaded (vocab, array) pair.  Candidates are ALL
     nodes of the dataset's graph (infer.py:80-82 iterates `test_dataset.graph.nodes()`, not `all_positions`), in node order; best =
@@ -373,10 +433,17 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     of exp(z') (scoring.log_partition_fused; z = the score for the info_nce losses, its negative otherwise), formed in float64; `save`
     then writes two more tab-separated columns, `Scores` and `Log-probabilities` (%.6g, comma separated like the parents).  Not with
     retrieve=k (ValueError before any launch): a partition over a retrieved subset is not the likelihood.
+    temperature=T (with with_scores=True only; finite and > 0; both ValueError before any launch): the calibrated form, log_probs =
+    t - lse_T[q] with t = fl32(z / T) and lse_T over the scaled scores of all candidates (scoring.score_moments_fused) -- T from
+    calibrate.fit_temperature on the validation split.  temperature=None: what it was.
     Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): infer(model, ...)` infers with the averaged
     model; or load a checkpoint's with trainer.load_averaged."""
     from .dataset import load_new_taxons
     device = torch.device(device)
+    if temperature is not None:
+        if not with_scores:
+            raise ValueError("infer: temperature scales the probabilities that with_scores=True reports; without it there is nothing to calibrate")
+        beta = scoring._beta_of(temperature)
     if retrieve is not None:
         if with_scores:
             raise ValueError("infer: with_scores=True normalises over every candidate; with retrieve=k the partition over a retrieved subset is not "
@@ -395,9 +462,13 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     with torch.no_grad():
         if retrieve is None and with_scores:
             ids, sc = _best_parents(model, hg, qf, cand_ids, topk, larger, qblock, with_scores=True)
-            lse = log_partition_fused(model.match, hg, qf, larger, block=qblock).to(torch.float64)
-            z = sc.to(torch.float64)
-            logp = ((z if larger else -z) - lse[:, None]).cpu().tolist()
+            if temperature is None:
+                lse = log_partition_fused(model.match, hg, qf, larger, block=qblock).to(torch.float64)
+                z = sc.to(torch.float64)
+                logp = ((z if larger else -z) - lse[:, None]).cpu().tolist()
+            else:
+                lse = scoring.score_moments_fused(model.match, hg, qf, larger, 1.0 / beta, block=qblock).lse
+                logp = (_scaled(sc, beta, larger) - lse[:, None]).cpu().tolist()
             picks, sc = ids.cpu().tolist(), sc.cpu().tolist()
         elif retrieve is None:
             picks = _best_parents(model, hg, qf, cand_ids, topk, larger, qblock).cpu().tolist()

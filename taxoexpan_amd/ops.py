@@ -6,6 +6,7 @@ every number is produced by the hand-written HIP kernels.  There is no CPU path 
 import collections
 import ctypes
 import functools
+import math
 import typing
 import weakref
 
@@ -1989,7 +1990,8 @@ def _score_sws(nq, G, r, ref, u_packed=False):
 # ----------------------------------------------------------------------------------------------------------------
 class _Family:
     """what the mode functions below (and scoring.prepare_matcher's loop over blocks) take from a matcher family:
-    prefix: of its C entry points -- prefix + "_block" / "_count_block" / "_topk_block" / "_topk_wide_block" / "_lse_block";
+    prefix: of its C entry points -- prefix + "_block" / "_count_block" / "_topk_block" / "_topk_wide_block" / "_lse_block" /
+    "_moments_block";
     queries(Q, prep, q_padded=False): one block's prepared query side, its row count in .n;
     head(qp, prep) / tail(qp, prep, store=False): the C arguments in front of / behind a mode's own (store: for prefix_block);
     ref(qp, prep): the tensor whose device the outputs and the scratch follow;
@@ -2138,6 +2140,43 @@ def _lse_block(fam, Q, prep, larger_is_better, scratch, q_padded=False):
     return lse
 
 
+def _check_beta(beta, what="beta"):
+    """the score scale of the moments mode as the fp32 the kernels take: finite and > 0 (ValueError before any launch)"""
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a finite number > 0, got {beta!r}") from None
+    b32 = float(torch.tensor(b, dtype=torch.float32).item()) if math.isfinite(b) else b
+    if isinstance(beta, bool) or not (math.isfinite(b32) and b32 > 0.0):
+        raise ValueError(f"{what} must be finite and > 0 (in fp32), got {beta!r}")
+    return b32
+
+
+def _moments_scratch(sc, need, ref):
+    """the moments entry points' per-tile quadruples (four fp32 [need]) in the dict a loop over blocks passes along (None: for this call
+    only), grown when a block needs more or the device changed"""
+    sc = sc if sc is not None else {}
+    if sc.get("mom_n", 0) < need or sc["mom"][0].device != ref.device:
+        sc["mom"], sc["mom_n"] = tuple(_empty((need,), ref) for _ in range(4)), need
+    return sc
+
+
+def _moments_block(fam, Q, prep, larger_is_better, beta, scratch, q_padded=False):
+    """(lse, mean, var, entropy) float64 [nq, 4] of one query block at the score scale beta: one pass of prefix_moments_block"""
+    beta = _check_beta(beta)
+    qp = fam.queries(Q, prep, q_padded)
+    nq, G, ref = qp.n, prep.G, fam.ref(qp, prep)
+    assert G >= 1, fam.prefix[4:] + "_moments_block: at least one candidate"
+    out = torch.empty((nq, 4), dtype=torch.float64, device=ref.device)
+    if nq == 0:
+        return out
+    with _lib.on_device(ref.device):
+        sc = _moments_scratch(scratch, nq * pure("txe_score_topk_tiles", G), ref)
+        call(fam.prefix + "_moments_block", *fam.head(qp, prep), int(larger_is_better), beta, *(ptr(t) for t in sc["mom"]), ptr(out),
+             *fam.tail(qp, prep), _lib.stream_ptr())
+    return out
+
+
 def score_block(Q, U, apply_exp, out=None):
     """S[q][g] = match(hg[g], Q[q]) for a block of queries against every candidate (test_fast.py:116-123).  U: a [G, r] tensor (that of
     bilinear_project brings its padding and planes along) or a BilinearPrepared, here and in the score_* functions below."""
@@ -2251,6 +2290,28 @@ def lse_merge(part_max, part_sum):
         with _lib.on_device(part_max.device):
             call("txe_lse_merge", ptr(part_max), ptr(part_sum), nq, cnt, ptr(lse), _lib.stream_ptr())
     return lse
+
+
+def score_moments_block(Q, U, apply_exp, larger_is_better=True, beta=1.0, q_padded=False, scratch=None):
+    """fused scoring + moments of one query block against a candidate matrix U (txe_score_moments_block): float64 [nq, 4] =
+    (lse, mean, var, entropy) of p = softmax(t), t = fl32(beta * z), z the score (larger is better) or its negative; include/txe.h states
+    the definitions and the special values.  No [nq x G] block is materialised.  G >= 1; beta finite and > 0 (ValueError).
+    q_padded / scratch: as in score_lse_block."""
+    return _moments_block(_BilinearFamily(apply_exp), Q, _as_prepared(U), larger_is_better, beta, scratch, q_padded)
+
+
+def moments_merge(part_max, part_s0, part_s1, part_s2):
+    """(lse, mean, var, entropy) float64 [nq, 4] of rows given as quadruples (txe_moments_merge; four fp32 [nq, cnt]; (-inf, 0, 0, 0) is
+    an empty slot): the merge of the per-tile quadruples of the score kernels, or of the per-rank ones of a candidate-sharded loop"""
+    _need_cuda(part_max, part_s0, part_s1, part_s2)
+    parts = [_f32(t) for t in (part_max, part_s0, part_s1, part_s2)]
+    assert parts[0].dim() == 2 and all(t.shape == parts[0].shape for t in parts)
+    nq, cnt = parts[0].shape
+    out = torch.empty((nq, 4), dtype=torch.float64, device=parts[0].device)
+    if nq > 0:
+        with _lib.on_device(parts[0].device):
+            call("txe_moments_merge", *(ptr(t) for t in parts), nq, cnt, ptr(out), _lib.stream_ptr())
+    return out
 
 
 SELECT_K_MAX = 4096     # txe_select_k keeps its survivors in LDS
@@ -2467,6 +2528,11 @@ def mlp_score_lse_block(Q, prep, larger_is_better=True, scratch=None):
     return _lse_block(_MLP, Q, prep, larger_is_better, scratch)
 
 
+def mlp_score_moments_block(Q, prep, larger_is_better=True, beta=1.0, scratch=None):
+    """fused scoring + moments of one query block (txe_mlp_score_moments_block): float64 [nq, 4] in score_moments_block's definition"""
+    return _moments_block(_MLP, Q, prep, larger_is_better, beta, scratch)
+
+
 _MLP = _Family("txe_mlp_score", project=mlp_project, loop_queries=mlp_prepare_queries, positives=mlp_positive_scores, head=_mlp_args,
                queries=lambda Q, prep, q_padded=False: mlp_prepare_queries(Q, prep), ref=lambda qp, prep: prep.Ap)
 
@@ -2619,6 +2685,11 @@ def ntn_score_lse_block(Q, prep, larger_is_better=True, scratch=None):
     """fused scoring + log-partition of one query block (txe_ntn_score_lse_block): fp32 [nq] in score_lse_block's definition and
     conventions.  G >= 1.  scratch: dict reused across blocks."""
     return _lse_block(_NTN, Q, prep, larger_is_better, scratch)
+
+
+def ntn_score_moments_block(Q, prep, larger_is_better=True, beta=1.0, scratch=None):
+    """fused scoring + moments of one query block (txe_ntn_score_moments_block): float64 [nq, 4] in score_moments_block's definition"""
+    return _moments_block(_NTN, Q, prep, larger_is_better, beta, scratch)
 
 
 # (positives: the loop hands over the positives' local rows, those of another shard clamped to 0, and masks their scores itself, as for BIM / LBM)

@@ -7,6 +7,7 @@ Here:  U = HG W is formed once (txe_bilinear_project); a block of queries is ONE
 the ranks of one node; each rank scores its shard and the score blocks are all-gathered over xGMI (RCCL) so that every
 rank holds the full [queries x candidates] block, as the north star asks.
 """
+import collections
 import math
 
 import torch
@@ -18,8 +19,8 @@ from . import ops
 class _PreparedMatcher:
     """a matcher over a candidate set: the family's candidate side once (ops._BilinearFamily: U = hg W; ops._MLP: A = hg W1a^T + b1;
     ops._NTN: the k slices U_j = hg W_j and a = V1 hg^T + b), then every query block through ONE function per mode whatever the family
-    (ops._store_block / _count_block / _topk_block / _lse_block) -- the same scratch and count conventions for all.  The blocks of
-    positives / count / topk / lse are row blocks of .queries(all queries); score takes raw query rows."""
+    (ops._store_block / _count_block / _topk_block / _lse_block / _moments_block) -- the same scratch and count conventions for all.  The
+    blocks of positives / count / topk / lse / moments are row blocks of .queries(all queries); score takes raw query rows."""
 
     def __init__(self, fam, match, hg):
         self.fam, self.prep = fam, fam.project(hg, match)
@@ -41,6 +42,9 @@ class _PreparedMatcher:
 
     def lse(self, qb, larger_is_better, scratch):
         return ops._lse_block(self.fam, qb, self.prep, larger_is_better, scratch, q_padded=True)
+
+    def moments(self, qb, larger_is_better, beta, scratch):
+        return ops._moments_block(self.fam, qb, self.prep, larger_is_better, beta, scratch, q_padded=True)
 
 
 def _ntn_fused_ok(match):
@@ -166,6 +170,102 @@ def log_partition_fused(match, hg, queries, larger_is_better=True, block=None):
     for _q0, S in _score_blocks(types.SimpleNamespace(match=match), hg, queries, block):
         out.append(torch.logsumexp(S.float() if larger_is_better else -S.float(), dim=1))
     return torch.cat(out)
+
+
+# (lse, mean, var, entropy) of every query's predictive distribution p = softmax(t) over all candidates: float64 [Q] each
+ScoreMoments = collections.namedtuple("ScoreMoments", "lse mean var entropy")
+
+
+def _beta_of(temperature):
+    """beta = 1 / temperature as the fp32 the kernels scale by; ValueError unless the temperature and its reciprocal are finite and > 0"""
+    try:
+        T = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}") from None
+    if isinstance(temperature, bool) or not (math.isfinite(T) and T > 0.0):
+        raise ValueError(f"temperature must be finite and > 0, got {temperature!r}")
+    return ops._check_beta(1.0 / T, "1 / temperature")
+
+
+def host_score_moments(S, temperature=1.0, larger_is_better=True):
+    """score_moments_fused on the host (the host_log_partition pattern: the tests' reference and any CPU caller's route): per row of the
+    score array S [Q, G], with z = S (larger is better) or -S and t = fl32(beta * z) -- the product formed in fp32, beta = fl32(1 /
+    temperature) -- the float64 values
+        lse = M + log S0,  mean = M + S1 / S0 = E_p[t],  var = max(S2 / S0 - (S1 / S0)^2, 0) = Var_p[t],  entropy = max(log S0 - S1 / S0, 0)
+    where M = max t, d = t - M, S0 / S1 / S2 = sum of exp(d), d exp(d), d^2 exp(d) over the candidates with t > -Inf, p = softmax(t).
+    lse: a NaN in the row gives NaN; otherwise a t = +Inf gives +Inf; otherwise all t = -Inf (or G = 0) gives -Inf; wherever lse is not
+    finite the other three are NaN.  Returns a ScoreMoments of float64 numpy arrays [Q]."""
+    import numpy as np
+    beta = np.float32(_beta_of(temperature))
+    z = np.asarray(torch.as_tensor(S).detach().cpu(), dtype=np.float32)
+    z = z if larger_is_better else -z
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (beta * z).astype(np.float32).astype(np.float64)       # one fp32 product, rounded on its own
+    Q = t.shape[0]
+    out = np.full((4, Q), np.nan, dtype=np.float64)
+    out[0] = -np.inf
+    for q in range(Q):
+        row = t[q]
+        if row.size == 0:
+            continue
+        M = row.max()                                             # (numpy's max keeps a NaN)
+        if np.isnan(M) or np.isinf(M):
+            out[0, q] = M
+            continue
+        d = row[row > -np.inf] - M
+        e = np.exp(d)
+        S0, S1, S2 = e.sum(), (d * e).sum(), (d * d * e).sum()
+        r1 = S1 / S0
+        out[:, q] = (M + np.log(S0), M + r1, max(S2 / S0 - r1 * r1, 0.0), max(np.log(S0) - r1, 0.0))
+    return ScoreMoments(*out)
+
+
+def _moments_of_block(S, beta, larger_is_better):
+    """float64 [nq, 4] of a materialised score block: host_score_moments' formulas in float64 torch ops (t is the fp32 product)"""
+    z = S.float() if larger_is_better else -S.float()
+    t = (z * torch.tensor(beta, dtype=torch.float32, device=S.device)).to(torch.float64)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=S.device)
+    M = torch.where(torch.isnan(t).any(dim=1), nan, t.max(dim=1).values)
+    fin = torch.isfinite(M)
+    d = t - torch.where(fin, M, torch.zeros_like(M))[:, None]
+    e = torch.exp(d)
+    dz = torch.where(torch.isinf(d), torch.zeros_like(d), d)
+    S0, S1, S2 = e.sum(1), (dz * e).sum(1), (dz * dz * e).sum(1)
+    r1 = S1 / S0
+    ls = torch.log(S0)
+    vals = torch.stack([M + ls, M + r1, (S2 / S0 - r1 * r1).clamp(min=0.0), (ls - r1).clamp(min=0.0)], dim=1)
+    special = torch.stack([M, nan.expand_as(M), nan.expand_as(M), nan.expand_as(M)], dim=1)
+    return torch.where(fin[:, None], vals, special)
+
+
+def score_moments_fused(match, hg, queries, larger_is_better=True, temperature=1.0, block=None):
+    """The first two moments of the scaled score under the predictive distribution over ALL candidates, per query: with z = the
+    matcher's score (larger is better) or its negative, beta = 1 / temperature and t = fl32(beta * z), a ScoreMoments of float64 [Q]
+    tensors on hg's device -- lse = log sum_g exp(t), mean = E_p[t], var = Var_p[t], entropy = H(p), p = softmax(t).  They are the
+    derivatives a temperature fit needs (d lse / d beta = mean / beta, d^2 lse / d beta^2 = var / beta^2; calibrate.py) and the query's
+    predictive entropy.  BIM / LBM / MLP / NTN: per query block ONE launch of the score kernel whose epilogue reduces every tile row to
+    a quadruple + a merge launch (txe_*_score_moments_block; include/txe.h states the definitions) -- no [Q, G] scores.  Any other
+    matcher is scored block by block (evaluate._score_blocks) and reduced with the same formulas in float64 torch ops.  Special values
+    as host_score_moments (no candidate at all: lse -inf, the rest NaN).  block: queries per launch, rank_all_fused's default."""
+    beta = _beta_of(temperature)
+    dev = hg.device
+    Q, G = queries.shape[0], hg.shape[0]
+    if block is None:
+        block = _default_block(Q)
+    if Q == 0 or G == 0:
+        out = torch.full((Q, 4), float("nan"), dtype=torch.float64, device=dev)
+        out[:, 0] = -float("inf")
+    elif fused_matcher_ok(match):
+        pm = prepare_matcher(match, hg)
+        Qp = pm.queries(queries)
+        scratch = {}
+        out = torch.cat([pm.moments(Qp[q0:q0 + block], larger_is_better, beta, scratch) for q0 in range(0, Q, block)])
+    else:
+        import types
+        from .evaluate import _score_blocks
+        out = torch.cat([_moments_of_block(S, beta, larger_is_better)
+                         for _q0, S in _score_blocks(types.SimpleNamespace(match=match), hg, queries, block)])
+    return ScoreMoments(*out.t().contiguous().unbind(0))
 
 
 def encode_candidates(model, graph, chunk=None, device=None):
