@@ -748,6 +748,45 @@ int txe_taxo_slots(const int* anc_ptr, const int* anc_idx, const int* depth, con
                    const int* pred, int Q, int K, const int* gold_off, const int* gold_idx, int n_gold, int* lca_depth, int* best_gold,
                    int* relation, void* stream);
 
+/* ---- hedged placement (taxoexpan_amd/hedge.py, csrc/txe_hedge.hip): the probability mass of every candidate's subtree
+ * and the deepest candidate whose subtree mass reaches a threshold.  Everything is in candidate-column space: G candidates, column a.
+ * The index, built and validated on the host (HedgeIndex.build): sub_ptr [G + 1] / sub_idx [nnz] = per column a the columns of a and
+ * of all its descendants on the taxonomy, ascending, a included, each once; depth [G] = the longest-chain depth of the column's node
+ * (>= 1).  The work list: item i < n_items is (item_row[i], item_slice[i], item_part[i]) -- slice s of row a covers the entries
+ * sub_ptr[a] + s TXE_HEDGE_SLICE .. + TXE_HEDGE_SLICE (cut at the row's end); item_part = -1 for a row of at most TXE_HEDGE_SLICE
+ * entries (one item, finished where it is summed), else the slice's position in the partial-sum workspace; long_row [n_long] = the
+ * longer rows and long_ptr [n_long + 1] their ranges of workspace positions (n_part in all), in slice order.
+ *
+ * txe_hedge_probs: S [nq][ldS] fp32 scores, lse [nq] float64 (txe_*_score_moments_block's value at this beta), z = S or -S (negate != 0),
+ * t = fl32(beta z), p = fl32(exp(float64(t) - lse[q])), and p = 0 on every row whose lse is not finite.  Written candidate-major:
+ * PT[g ldq + q], ldq >= nq; the columns nq .. ldq of every row are written as zeros.  One launch; the transposition goes through a
+ * padded LDS tile.  TXE_ERR_ARG before any launch: nq < 0, G < 0, beta not finite or <= 0, and (with nq > 0 and G > 0) a NULL pointer,
+ * ldS < G, ldq < nq, more than 65,535 x 64 query columns.  nq == 0 or G == 0: TXE_OK, no device call.
+ *
+ * txe_hedge_sweep: mass[a][q] = the sum of PT[d ldq + q] over the entries d of row a, in float64, in an order fixed by the list alone:
+ * every slice is summed left to right from 0.0, the slice sums are added left to right.  No atomics: equal inputs give equal bytes,
+ * and a query's values do not depend on nq or on where the query sits.  n_thr == 0 (store mode): mass [G][ldm] is written, ldm >= nq.
+ * 1 <= n_thr <= TXE_HEDGE_MAX_THRESHOLDS (hedge mode; thresholds: n_thr doubles in HOST memory, each in (0, 1]): per query q and
+ * threshold t the column a with mass[a][q] >= thresholds[t] of the largest depth -- ties: the larger mass, then the smaller column --
+ * to out_col[q n_thr + t] (int, -1 when none qualifies), with its mass to out_mass (float64, NaN for -1) and its depth to out_depth
+ * (int, 0 for -1); no mass matrix is written and `mass` may be NULL.  The result for a threshold does not depend on the others.
+ * Launches: the sweep (a wave per work item and tile of 64 queries), the long rows' slice sums if n_long > 0, and in hedge mode the
+ * per-query merge of the workgroups' partial keys.  Every row, entry, workspace position and offset is range-checked before it
+ * addresses anything; an entry outside [0, G) contributes nothing.
+ * ws: txe_hedge_sweep_ws_bytes(n_items, n_long, n_part, nq, n_thr) bytes, else TXE_ERR_WORKSPACE (before any launch).
+ * TXE_ERR_ARG before any launch: a negative count, n_thr > TXE_HEDGE_MAX_THRESHOLDS, a NULL thresholds with n_thr > 0, a threshold that
+ * is NaN or outside (0, 1]; and (with nq > 0 and G > 0) a NULL index / work-list pointer or PT, ldq < nq, store mode with a NULL mass
+ * or ldm < nq, hedge mode with a NULL output, more than 65,535 query tiles.  nq == 0 or G == 0: TXE_OK, no device call. */
+#define TXE_HEDGE_SLICE 256
+#define TXE_HEDGE_MAX_THRESHOLDS 8
+int txe_hedge_probs(const float* S, long long ldS, int nq, int G, const double* lse, float beta, int negate, float* PT, long long ldq,
+                    void* stream);
+size_t txe_hedge_sweep_ws_bytes(int n_items, int n_long, int n_part, int nq, int n_thr);
+int txe_hedge_sweep(const int* sub_ptr, const int* sub_idx, const int* depth, int G, int nnz, const int* item_row, const int* item_slice,
+                    const int* item_part, int n_items, const int* long_row, const int* long_ptr, int n_long, int n_part, const float* PT,
+                    long long ldq, int nq, const double* thresholds, int n_thr, double* mass, long long ldm, int* out_col,
+                    double* out_mass, int* out_depth, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optional per-kernel timing (debug / bench): HIP events on the launch stream around every kernel launch, with the
  * algorithmic work (flops or compulsory bytes) its launcher attributes to it.  Global state (see the conventions at the top); off by
  * default.  txe_profile_get synchronises on record i's events. */

@@ -14,6 +14,8 @@ WALK_NO_REFORM = 2048          # TXE_WALK_NO_REFORM: one more `phases` bit of tx
 FOLD_A12_READY, FOLD_HG_SPLIT = 1, 2
 STEP_LOG_CHUNK = 4096          # TXE_STEP_LOG_CHUNK: gradient elements per workgroup of txe_step_log
 TAXO_STAGE_CAP = 64            # TXE_TAXO_STAGE_CAP: the longest positive closure row txe_info_nce_taxo stages in LDS
+HEDGE_SLICE = 256              # TXE_HEDGE_SLICE: closure entries per work item of txe_hedge_sweep (the unit of its summation order)
+HEDGE_MAX_THRESHOLDS = 8       # TXE_HEDGE_MAX_THRESHOLDS: thresholds one sweep evaluates
 
 P, I, L, F, D, U64, SZ = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_ulonglong, C.c_size_t
 
@@ -150,6 +152,9 @@ SIGNATURES = {
     "txe_group_rank": (I, [P, P, I, I, I, P, P, P, P, SZ, P]),
     "txe_group_metrics": (I, [P, P, P, U64, I, P, P]),
     "txe_taxo_slots": (I, [P, P, P, P, P, I, P, I, I, P, P, I, P, P, P, P]),
+    "txe_hedge_probs": (I, [P, L, I, I, P, F, I, P, L, P]),
+    "txe_hedge_sweep_ws_bytes": (SZ, [I, I, I, I, I]),
+    "txe_hedge_sweep": (I, [P, P, P, I, I, P, P, P, I, P, P, I, I, P, L, I, P, I, P, L, P, P, P, P, SZ, P]),
     "txe_row_normalize": (I, [P, L, I, I, P, L, P]),
     "txe_select_k_ws_bytes": (SZ, [I, I]),
     "txe_select_k": (I, [P, L, I, I, P, P, I, P, P, P, SZ, P]),

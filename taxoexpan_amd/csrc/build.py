@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["txe_gemm_nt.hip", "txe_gemm_nn.hip", "txe_gemm_tn.hip", "txe_gemm_split.hip", "txe_gat.hip", "txe_gcn.hip", "txe_project.hip", "txe_fold.hip", "txe_fold_bwd.hip", "txe_dxpos.hip", "txe_readout.hip", "txe_match.hip",
            "txe_graph.hip", "txe_rank.hip", "txe_profile.hip", "txe_egonet.hip", "txe_optim.hip", "txe_loss.hip",
            "txe_mlp_score.hip", "txe_ntn_score.hip", "txe_sample.hip", "txe_grouprank.hip", "txe_retrieve.hip", "txe_steplog.hip", "txe_pairloss.hip", "txe_inbatch.hip",
-           "txe_taxometric.hip", "txe_rowgrad.hip", "txe_taxoloss.hip"]
+           "txe_taxometric.hip", "txe_rowgrad.hip", "txe_taxoloss.hip", "txe_hedge.hip"]
 HEADERS = ["txe_common.h", "txe_gemm.h", "txe_gather.h", "txe_colsum.h", "txe_dxpos.h", "txe_gemm_tnlds.h", "txe_skinny.h", "txe_gemm_split.h", "txe_tail.h", "txe_fold.h", "txe_groups.h", "txe_ego_row.h", "txe_adam.h", "txe_nce_row.h", "txe_moments.h", "../../include/txe.h"]
 LIB = os.path.join(HERE, "libtxe.so")
 OBJ_DIR = os.path.join(HERE, "build")

@@ -253,8 +253,39 @@ def _taxonomic(index_dev, best, pos_off, gold_idx, Q):
     return taxometric.summarize(out["relation"], wup), dict(pred=pred, wu_palmer=wup, **out)
 
 
+def _hedged(model, hg, qf, tindex, cand, pos_off, pos_idx, thr, beta, larger_is_better, lse):
+    """evaluate's `hedge` metrics: the hedged parent of every query per threshold (hedge.hedged_parents) judged against the query's gold
+    parents by taxometric.taxonomic_slots -- the T thresholds are the T slots of one [Q, T] list, one launch.  Returns (metric lists, the
+    [Q, T] device tensors)"""
+    from . import hedge as _hedge, taxometric
+    dev = hg.device
+    Q, T = int(qf.shape[0]), len(thr)
+    cand_np = np.asarray(cand, dtype=np.int64)
+    hix = _hedge.HedgeIndex.build(tindex, cand_np).to(dev)
+    h = _hedge.hedged_parents(model.match, hg, qf, hix, thr, 1.0 / beta, larger_is_better, lse=lse)
+    nan = [float("nan")] * T
+    if Q == 0:
+        return dict(hedge_thresholds=list(thr), hedge_accuracy=nan, hedge_exact=list(nan), hedge_wu_palmer=list(nan), hedge_depth=list(nan),
+                    hedge_mass=list(nan), hedge_none=list(nan)), dict(node_col=h.node_col, mass=h.mass, depth=h.depth)
+    cand_ids = torch.as_tensor(cand_np, device=dev)
+    answered = h.node_col >= 0
+    node = torch.where(answered, cand_ids[h.node_col.long().clamp(min=0)], torch.full_like(h.node_col, -1, dtype=torch.int64)) \
+        if len(cand) else torch.full_like(h.node_col, -1, dtype=torch.int64)
+    _m, t = _taxonomic(tindex, node, pos_off, cand_np[pos_idx], Q)
+    rel = t["relation"]
+    n_ans = answered.sum(0).to(torch.float64)
+    sums = torch.stack([((rel == taxometric.EXACT) | (rel == taxometric.ANCESTOR)).sum(0).to(torch.float64),
+                        (rel == taxometric.EXACT).sum(0).to(torch.float64), t["wu_palmer"].sum(0), h.depth.sum(0).to(torch.float64),
+                        torch.where(answered, h.mass, torch.zeros_like(h.mass)).sum(0), n_ans]).cpu().numpy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        metrics = dict(hedge_thresholds=list(thr), hedge_accuracy=(sums[0] / Q).tolist(), hedge_exact=(sums[1] / Q).tolist(),
+                       hedge_wu_palmer=(sums[2] / Q).tolist(), hedge_depth=(sums[3] / Q).tolist(), hedge_mass=(sums[4] / sums[5]).tolist(),
+                       hedge_none=((Q - sums[5]) / Q).tolist())
+    return metrics, dict(node=node, node_col=h.node_col, mass=h.mass, depth=h.depth, relation=rel, wu_palmer=t["wu_palmer"])
+
+
 def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0, batch_size=-1, case=None, metric_names=CASE_METRICS,
-             topk=5, retrieve=None, nll=False, taxonomic=False, taxonomy_index=None, temperature=None, predictive=False):
+             topk=5, retrieve=None, nll=False, taxonomic=False, taxonomy_index=None, temperature=None, predictive=False, hedge=None):
     """dataset: taxoexpan_amd.dataset.MaskedGraphDataset in 'validation' or 'test' mode.  Returns (metrics dict, ranks int32
     [n_positives], pos_off [Q+1], queries list).  Queries whose true parents are not candidate positions are skipped, like the
     reference's rearrange() would fail on them.
@@ -299,9 +330,29 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     entropy, top1_prob (float64 [Q]) and correct (bool [Q]).  Neither goes with retrieve=k (ValueError before any launch).  Ranks,
     offsets and every other metric are bit-equal to a call without the two keywords -- nll too while `temperature` is None (it stays on
     log_partition_fused's fp32 lse then) --; without both the code path is what it was.
+    hedge: a threshold, a sequence of at most hedge.MAX_THRESHOLDS of them (each finite and in (0, 1]), or a dict {"thresholds": ...} =
+    also answer every query with the DEEPEST candidate whose subtree probability reaches the threshold (hedge.py; Deng et
+    al. 2012) under p = softmax(t) over ALL candidates at `temperature` (T = 1 without it), on the masked taxonomy (`taxonomy_index`, built
+    once and shared with `taxonomic`).  The metrics dict gains, one entry per threshold and in their order, the lists hedge_thresholds,
+    hedge_accuracy (the share of queries whose hedged node is a gold parent or an ancestor of one: relations exact / ancestor of
+    taxometric.taxonomic_slots), hedge_exact, hedge_wu_palmer, hedge_depth (the mean depth over all queries, 0 for an unanswered one),
+    hedge_mass (the mean subtree mass over the answered queries; NaN when there is none) and hedge_none (the share left unanswered: no
+    candidate's subtree reaches the threshold).  A dict is also filled with the [Q, T] device tensors node (node ids, -1 = unanswered),
+    node_col, mass, depth, relation and wu_palmer.  Not with retrieve=k (ValueError before any launch): a subset is not the
+    distribution.  Every other metric, the ranks and the offsets are bit-equal to a call without the keyword.
     Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): evaluate(model, ...)` evaluates the averaged
     model -- the parameters are the averages inside the context; or load a checkpoint's with trainer.load_averaged."""
     device = torch.device(device)
+    want_hedge = hedge is not None
+    if want_hedge:
+        from . import hedge as _hedge
+        if isinstance(hedge, dict) and "thresholds" not in hedge:
+            raise ValueError('evaluate: a hedge dict names its thresholds, {"thresholds": ...}')
+        hedge_thr = _hedge.check_thresholds(hedge["thresholds"] if isinstance(hedge, dict) else hedge)
+        hedge_beta = scoring._beta_of(1.0 if temperature is None else temperature)
+        if retrieve is not None:
+            raise ValueError("evaluate: hedge sums the distribution over every candidate's subtree; with retrieve=k a retrieved subset is "
+                             "not the distribution")
     want_pred = isinstance(predictive, dict) or bool(predictive)
     calibrated = temperature is not None or want_pred
     if calibrated:
@@ -316,7 +367,7 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     want_taxo = isinstance(taxonomic, dict) or bool(taxonomic)
     if case is not None and "wu_palmer" in metric_names and not want_taxo:
         raise ValueError('evaluate: the "wu_palmer" column of the case study needs taxonomic=True')
-    if want_taxo:
+    if want_taxo or want_hedge:
         from .taxometric import TaxonomyIndex
         tindex = (taxonomy_index if taxonomy_index is not None else TaxonomyIndex.from_dataset(dataset)).to(device)
     cand = sorted(dataset.all_positions)                                    # test_fast.py:93
@@ -335,6 +386,7 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
     pos_off = np.concatenate([[0], np.cumsum([len(p) for p in pos_lists])]).astype(np.int64)
     pos_idx = np.concatenate(pos_lists).astype(np.int64) if pos_lists else np.zeros(0, dtype=np.int64)
     qf = dataset.node_features[torch.as_tensor(queries, dtype=torch.long)].to(device)
+    mom = None
     with torch.no_grad():
         if retrieve is None and calibrated:
             ranks, thr = _ranks_of(model, hg, qf, pos_off, pos_idx, larger_is_better, qblock, with_thr=True) if nll else \
@@ -385,6 +437,11 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
             taxo_metrics, taxo_tensors = _taxonomic(tindex, nodes, pos_off, np.asarray(cand, dtype=np.int64)[pos_idx], len(queries))
             if isinstance(taxonomic, dict):
                 taxonomic.update(taxo_tensors)
+        if want_hedge:
+            hedge_metrics, hedge_tensors = _hedged(model, hg, qf, tindex, cand, pos_off, pos_idx, hedge_thr, hedge_beta, larger_is_better,
+                                                   mom.lse if mom is not None else None)
+            if isinstance(hedge, dict):
+                hedge.update(hedge_tensors)
         if case is not None:                                               # test_fast.py:112-147
             top = best.cpu().tolist() if retrieve is None else [[cand[i] for i in row if i >= 0] for row in best.cpu().tolist()]
             per_query_values = None
@@ -413,11 +470,13 @@ def evaluate(model, dataset, device, larger_is_better=True, qblock=None, seed=0,
         metrics.update(taxo_metrics)
     if want_pred:
         metrics.update(pred_metrics)
+    if want_hedge:
+        metrics.update(hedge_metrics)
     return metrics, ranks, pos_off, queries
 
 
 def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-1, save=None, topk=5, normalize=False, qblock=1024,
-          seed=0, retrieve=None, with_scores=False, temperature=None):
+          seed=0, retrieve=None, with_scores=False, temperature=None, hedge=None, taxonomy_index=None):
     """infer.py:77-159: the `topk` best parents of every NEW term.  dataset: MaskedGraphDataset in 'test' mode (infer.py:43-57);
     new_taxons: path of the `<name>\t<v0 v1 ...>` file (infer.py:23-38) or an already loaded (vocab, array) pair.  Candidates are ALL
     nodes of the dataset's graph (infer.py:80-82 iterates `test_dataset.graph.nodes()`, not `all_positions`), in node order; best =
@@ -436,6 +495,12 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     temperature=T (with with_scores=True only; finite and > 0; both ValueError before any launch): the calibrated form, log_probs =
     t - lse_T[q] with t = fl32(z / T) and lse_T over the scaled scores of all candidates (scoring.score_moments_fused) -- T from
     calibrate.fit_temperature on the validation split.  temperature=None: what it was.
+    hedge: a threshold or a sequence of at most hedge.MAX_THRESHOLDS of them (with with_scores=True only; each finite and in (0, 1]; both
+    ValueError before any launch): every item gains a fifth entry, per threshold the triple (hedged parent's vocab entry or None, subtree
+    mass, depth) -- the deepest graph node whose subtree probability under p (at `temperature`, T = 1 without it) reaches the threshold
+    (hedge.py), on the dataset's taxonomy (`taxonomy_index`: a taxometric.TaxonomyIndex of it to reuse; default
+    TaxonomyIndex.from_dataset(dataset)) -- and `save` writes three more tab-separated columns per threshold, `Hedged parent@tau`,
+    `Mass@tau` and `Depth@tau` (an unanswered query: an empty name, nan, 0).  hedge=None: what it was.
     Averaged weights (optim.Adam(ema_decay=...)): `with optimizer.averaged_parameters(): infer(model, ...)` infers with the averaged
     model; or load a checkpoint's with trainer.load_averaged."""
     from .dataset import load_new_taxons
@@ -444,6 +509,12 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
         if not with_scores:
             raise ValueError("infer: temperature scales the probabilities that with_scores=True reports; without it there is nothing to calibrate")
         beta = scoring._beta_of(temperature)
+    if hedge is not None:
+        from . import hedge as _hedge
+        if not with_scores:
+            raise ValueError("infer: hedge reports subtree probabilities beside those of with_scores=True; without it there is nothing to hedge")
+        hedge_thr = _hedge.check_thresholds(hedge)
+        hedge_beta = scoring._beta_of(1.0 if temperature is None else temperature)
     if retrieve is not None:
         if with_scores:
             raise ValueError("infer: with_scores=True normalises over every candidate; with retrieve=k the partition over a retrieved subset is not "
@@ -469,6 +540,13 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
             else:
                 lse = scoring.score_moments_fused(model.match, hg, qf, larger, 1.0 / beta, block=qblock).lse
                 logp = (_scaled(sc, beta, larger) - lse[:, None]).cpu().tolist()
+            if hedge is not None:
+                from .taxometric import TaxonomyIndex
+                hix = _hedge.HedgeIndex.build(taxonomy_index if taxonomy_index is not None else TaxonomyIndex.from_dataset(dataset), anchors)
+                h = _hedge.hedged_parents(model.match, hg, qf, hix.to(device), hedge_thr, 1.0 / hedge_beta, larger,
+                                          lse=lse if temperature is not None else None)
+                hedged = [[(dataset.vocab[int(anchors[c])] if c >= 0 else None, m, d) for c, m, d in zip(cs, ms, ds)]
+                          for cs, ms, ds in zip(h.node_col.cpu().tolist(), h.mass.cpu().tolist(), h.depth.cpu().tolist())]
             picks, sc = ids.cpu().tolist(), sc.cpu().tolist()
         elif retrieve is None:
             picks = _best_parents(model, hg, qf, cand_ids, topk, larger, qblock).cpu().tolist()
@@ -485,12 +563,16 @@ def infer(model, dataset, new_taxons, device, loss="info_nce_loss", batch_size=-
     out = [(q, [dataset.vocab[i] for i in row]) for q, row in zip(vocab, picks)]
     if with_scores:
         out = [(q, parents, s, lp) for (q, parents), s, lp in zip(out, sc, logp)]
+        if hedge is not None:
+            out = [item + (hd,) for item, hd in zip(out, hedged)]
     if save is not None:
         with open(save, "w") as fout:
             if with_scores:
-                fout.write("Query\tPredicted parents\tScores\tLog-probabilities\n")
-                for q, parents, s, lp in out:
-                    fout.write(f"{q}\t{', '.join(parents)}\t{', '.join('%.6g' % v for v in s)}\t{', '.join('%.6g' % v for v in lp)}\n")
+                more = "" if hedge is None else "".join(f"\tHedged parent@{t:g}\tMass@{t:g}\tDepth@{t:g}" for t in hedge_thr)
+                fout.write("Query\tPredicted parents\tScores\tLog-probabilities" + more + "\n")
+                for q, parents, s, lp, *hd in out:
+                    more = "".join(f"\t{name if name is not None else ''}\t{m:.6g}\t{d}" for name, m, d in (hd[0] if hd else ()))
+                    fout.write(f"{q}\t{', '.join(parents)}\t{', '.join('%.6g' % v for v in s)}\t{', '.join('%.6g' % v for v in lp)}{more}\n")
             else:
                 fout.write("Query\tPredicted parents\n")
                 for q, parents in out:
