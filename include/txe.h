@@ -702,6 +702,31 @@ int txe_sample_anchors_hard(const int* order, int n_order, int start, int Q, con
                             unsigned long long seed, int epoch, int repeated, int* packed, int* n_padded, const int* hard_idx,
                             const int* hard_cnt, int H, int hard_slots, void* stream);
 
+/* ---- txe_sample_anchors_hard with near negatives: after the hard_slots table slots, n_sib / n_gpar / n_unc negative slots propose a node
+ * of the positive's taxonomy neighbourhood.  tax_par_ptr / tax_par_idx / tax_chd_ptr / tax_chd_idx: the parent and child CSR of the
+ * masked taxonomy over n_nodes nodes (n_tax_par / n_tax_chd: the lengths of the two index arrays; n_qpar: the length of par_idx, the
+ * sampler's own query-parent index array).  With p the positive the pointer walk gives the query at epoch position s, the three lists are
+ *   S = chd(p) (siblings);  G = par(p) (grandparents);  U = chd(g_0) ++ chd(g_1) ++ .. over g_i in par(p), in order (uncles; repeats stay).
+ * Sibling slots are j in [hard_slots, hard_slots + n_sib), grandparent slots the next n_gpar, uncle slots the next n_unc.  Class X (list
+ * length n_X, c_X slots, t_S, t_G, t_U = 1, 2, 3) has m_X = min(c_X, n_X) and one rotation r_X = (hi32(h) n_X) >> 32,
+ * h = mix64(seed ^ mix64(epoch << 44 | s << 20 | 16383 << 6 | t_X)); the slot at class offset e < m_X proposes L_X[(r_X + e) % n_X] (an
+ * uncle index walks par(p), subtracting child counts).  A proposal is kept iff it lies in [0, n_nodes), is a pool node (binary search;
+ * pool must be ascending) and is not in q's mask row.  A refused proposal, every class slot e >= m_X and every slot outside the class
+ * ranges is txe_sample_anchors' slot j bit for bit (slots below hard_slots: txe_sample_anchors_hard's): the same draws, tries and
+ * *n_padded accounting; no rejection loop on the near side.  A row of the taxonomy CSR whose node is outside [0, n_nodes), whose start is
+ * negative, whose end lies before its start or beyond its index array counts as empty; a positive read outside par_idx falls back to q.
+ * So all three counts 0 give txe_sample_anchors_hard's output (txe_sample_anchors' when hard_slots = 0), and no taxonomy array can put an
+ * invalid or masked id into a batch.  Near negatives are plain negatives (exclude -1), by the argument made for mined ones.
+ * n_near [3] += the accepted sibling / grandparent / uncle proposals.  hard_idx / hard_cnt may be NULL when hard_slots == 0.
+ * TXE_ERR_ARG (before any device work): everything txe_sample_anchors refuses; hard_slots < 0; hard_slots > 0 with a NULL hard_idx or
+ * hard_cnt or H < 1; a NULL taxonomy pointer or n_near; n_nodes < 1; a negative length or count; hard_slots + n_sib + n_gpar + n_unc > k. */
+int txe_sample_anchors_near(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
+                            const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k,
+                            unsigned long long seed, int epoch, int repeated, int* packed, int* n_padded, const int* hard_idx,
+                            const int* hard_cnt, int H, int hard_slots, const int* tax_par_ptr, const int* tax_par_idx,
+                            const int* tax_chd_ptr, const int* tax_chd_idx, int n_nodes, int n_qpar, int n_tax_par, int n_tax_chd,
+                            int n_sib, int n_gpar, int n_unc, int* n_near, void* stream);
+
 /* ---- validation-anchor sampling on device, sampling_mode 0: data_loader/dataset.py:304-307,340-355 (every parent, then at most k
  * negatives) for the Q queries at positions start .. start+Q-1 of the epoch order.  Query i's run: node2parents[q] in order (label 1,
  * exclude q), then the surviving negatives in slot order (label 0, exclude -1).  Negative slot j of epoch position s in round t draws

@@ -147,6 +147,7 @@ SIGNATURES = {
     "txe_egonet_fill": (I, [P, P, P, P, P, P, I, I, U64, I, P, P, P, P, P, P, P, P, P, P]),
     "txe_sample_anchors": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P]),
     "txe_sample_anchors_hard": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P, P, I, I, P]),
+    "txe_sample_anchors_near": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, P, P]),
     "txe_sample_groups": (I, [P, I, I, I, P, P, P, P, P, P, I, I, U64, I, I, I, P, P, P, P, P, P]),
     "txe_group_rank_ws_bytes": (SZ, [I]),
     "txe_group_rank": (I, [P, P, I, I, I, P, P, P, P, SZ, P]),

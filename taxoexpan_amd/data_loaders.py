@@ -221,6 +221,11 @@ class DeviceBatchLoader:
     host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py).
     hard_negatives / hard_slots (this sampler only; default off): a sampler.HardNegatives table whose rows fill the first hard_slots
     negative slots of every query (txe_sample_anchors_hard); set_hard_negatives changes it between epochs.
+    near_negatives (this sampler only; default None: the loader launches what it launched): dict(siblings=, grandparents=, uncles=), the
+    negative slots behind the hard ones that propose a node of the positive's taxonomy neighbourhood -- another child of it, a parent of
+    it, a child of one of its parents (txe_sample_anchors_near); a proposal that is masked, outside the pool or absent
+    leaves its slot to the pool draw.  set_near_negatives changes the counts between epochs; sampler.near_counts() reads the accepted
+    proposals.  The packed layout is unchanged, so in_batch, attach_anchors, the feature table and the hard table compose.
     in_batch=True (this sampler, repeated_queries=True; ValueError otherwise): every batch's graph carries `g.in_batch`, a
     sampler.InBatchGroups -- views of the sampler's index array and mask CSR for loss.in_batch_info_nce; the 4-tuple keeps its shape.
     attach_anchors=True (this sampler; ValueError otherwise; default off: the loader launches and yields what it did): every batch's graph
@@ -237,7 +242,7 @@ class DeviceBatchLoader:
     step b (finish_device_batch).  Every graph gains g.query_ids, the int32 [U] ids of the distinct query rows."""
 
     def __init__(self, dataset, batch_size, device, shuffle=True, seed=0, drop_last=False, repeated_queries=True, sampler="host",
-                 hard_negatives=None, hard_slots=0, in_batch=False, feature_table=None, attach_anchors=False):
+                 hard_negatives=None, hard_slots=0, in_batch=False, feature_table=None, attach_anchors=False, near_negatives=None):
         if sampler not in ("host", "device"):
             raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
         if feature_table is not None and not repeated_queries:
@@ -252,6 +257,8 @@ class DeviceBatchLoader:
         self.attach_anchors = bool(attach_anchors)
         if hard_negatives is not None and not (sampler == "device" and dataset.sampling_mode == 1):
             raise ValueError("hard negatives need sampler='device' on a sampling_mode 1 dataset")
+        if near_negatives is not None and not (sampler == "device" and dataset.sampling_mode == 1):
+            raise ValueError("near negatives need sampler='device' on a sampling_mode 1 dataset")
         self.repeated_queries = bool(repeated_queries)
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         self.shuffle, self.seed, self.drop_last = shuffle, int(seed), drop_last
@@ -278,6 +285,8 @@ class DeviceBatchLoader:
         self._epoch = 0
         if hard_negatives is not None:
             self.set_hard_negatives(hard_negatives, hard_slots)
+        if near_negatives is not None:
+            self.set_near_negatives(**near_negatives)
 
     def set_hard_negatives(self, table, slots=0):
         """from the next epoch's first batch on, the first `slots` negatives of every query come from `table` (sampler.HardNegatives,
@@ -289,6 +298,17 @@ class DeviceBatchLoader:
             raise ValueError("hard negatives need sampler='device' on a sampling_mode 1 dataset (the host sampler and the sampling_mode 0 "
                              "group sampler draw from the pool only)")
         self.sampler.set_hard_negatives(table, slots)
+
+    def set_near_negatives(self, siblings=0, grandparents=0, uncles=0):
+        """from the next epoch's first batch on, that many negative slots of every query (behind the hard slots) propose a sibling, a
+        grandparent, an uncle of the query -- DeviceAnchorSampler.set_near_negatives; all 0: the pool (and the table) alone again.
+        ValueError on a loader whose sampler is 'host' or the sampling_mode 0 group sampler, for a count that is not an integer >= 0 or
+        a sum with the hard slots above negative_size; RuntimeError while an epoch is being iterated."""
+        from .sampler import DeviceAnchorSampler
+        if not isinstance(self.sampler, DeviceAnchorSampler):
+            raise ValueError("near negatives need sampler='device' on a sampling_mode 1 dataset (the host sampler and the sampling_mode 0 "
+                             "group sampler draw from the pool only)")
+        self.sampler.set_near_negatives(siblings, grandparents, uncles)
 
     def __len__(self):
         n = len(self.dataset)
@@ -355,7 +375,7 @@ class DeviceBatchLoader:
             Q = min(bs, n - b * bs)
             return Q, self.sampler.begin(order_dev, b * bs, Q, epoch, self.repeated_queries, self._side,
                                          egonet_seed=self.seed + 7919 * self._epoch + b)
-        self.sampler.in_epoch = True                                 # (set_hard_negatives refuses until the epoch's batches are out)
+        self.sampler.in_epoch = True                                 # (set_hard_negatives / set_near_negatives refuse until the epoch's batches are out)
         try:
             nxt = begin(0) if len(self) else None
             for b in range(len(self)):

@@ -11,7 +11,11 @@ cache (dataset.py:390-400), which the device egonet builder never had either.
 Hard negatives (off by default): mine_hard_negatives ranks every pool node for every training query under the model as it stands
 (candidate encode, score blocks, ops.select_k with the query's masks) and keeps the best `size` per query in a HardNegatives table;
 txe_sample_anchors_hard then fills the first `hard_slots` negative slots of a query from its row (one rotation per query and epoch)
-and the rest from the pool as before.  host_draw(hard=..., hard_slots=...) restates that draw, host_hard_table the table."""
+and the rest from the pool as before.  host_draw(hard=..., hard_slots=...) restates that draw, host_hard_table the table.
+
+Near negatives (off by default): txe_sample_anchors_near fills the slots behind the hard ones from the taxonomy neighbourhood of the
+query's positive -- its other children (siblings), its parents (grandparents), the children of its parents (uncles) -- read off the
+masked taxonomy's CSR that is resident anyway; no model pass, no table.  host_draw(near=..., taxonomy=near_arrays(dataset)) restates it."""
 import numpy as np
 import torch
 
@@ -78,17 +82,77 @@ def _hard_arrays(hard):
     return idx, cnt
 
 
-def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=False, hard=None, hard_slots=0):
+def near_arrays(dataset):
+    """The masked taxonomy as dataset.device_taxonomy uploads it, as numpy int32 arrays (no GPU needed): dict(par_ptr, par_idx, chd_ptr,
+    chd_idx, n_nodes) -- graph.pred / graph.succ per node in CSR order.  host_draw(near=..., taxonomy=this) reads it; it is NOT the
+    query-parent CSR of sampler_arrays (held-out in-edges are removed here)."""
+    n = int(dataset.node_features.shape[0])
+    out = dict(n_nodes=n)
+    for name, adj in (("par", dataset.graph.pred), ("chd", dataset.graph.succ)):
+        rows = [list(adj.get(i, ())) for i in range(n)]
+        out[name + "_ptr"] = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        out[name + "_idx"] = np.asarray([v for r in rows for v in r], dtype=np.int32)
+    return out
+
+
+def _checked_near(near, k, h0, who="near negatives"):
+    """(n_s, n_g, n_u) as ints; ValueError unless each is an integer (no bool, no float) >= 0 and h0 + n_s + n_g + n_u <= k"""
+    near = (0, 0, 0) if near is None else tuple(near)
+    if len(near) != 3 or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0 for c in near):
+        raise ValueError(f"{who}: three integer slot counts (siblings, grandparents, uncles), each >= 0, got {near!r}")
+    near = tuple(int(c) for c in near)
+    if h0 + sum(near) > k:
+        raise ValueError(f"{who}: hard slots {h0} + siblings {near[0]} + grandparents {near[1]} + uncles {near[2]} exceed "
+                         f"negative_size = {k}")
+    return near
+
+
+def _near_row(ptr, n_nodes, length, v):
+    """(start, length) of row v of a CSR whose index array holds `length` entries; (0, 0) for a node outside [0, n_nodes) or a row with a
+    negative start, an end before its start or beyond the index array -- near_row of csrc/txe_sample.hip"""
+    if not 0 <= v < n_nodes:
+        return 0, 0
+    lo, hi = int(ptr[v]), int(ptr[v + 1])
+    return (0, 0) if lo < 0 or hi < lo or hi > length else (lo, hi - lo)
+
+
+def near_lists(taxonomy, p):
+    """(S, G, U) of the positive p as int64 arrays: S = chd(p), G = par(p), U = chd(g_0) ++ chd(g_1) ++ .. over g_i in par(p), in CSR
+    order (malformed rows are empty, as the kernel reads them)"""
+    n, par_idx, chd_idx = int(taxonomy["n_nodes"]), np.asarray(taxonomy["par_idx"]), np.asarray(taxonomy["chd_idx"])
+    sb, ns = _near_row(taxonomy["chd_ptr"], n, len(chd_idx), int(p))
+    gb, ng = _near_row(taxonomy["par_ptr"], n, len(par_idx), int(p))
+    G = par_idx[gb:gb + ng].astype(np.int64)
+    rows = [_near_row(taxonomy["chd_ptr"], n, len(chd_idx), int(g)) for g in G]
+    U = np.concatenate([chd_idx[b:b + c] for b, c in rows]).astype(np.int64) if rows else np.zeros(0, dtype=np.int64)
+    if len(U) > 0x7fffffff:
+        U = U[:0]
+    return chd_idx[sb:sb + ns].astype(np.int64), G, U
+
+
+def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=False, hard=None, hard_slots=0, near=None, taxonomy=None):
     """numpy restatement of txe_sample_anchors for the Q queries at positions start .. start+Q-1 of `order` (indices into node_list).
     ptr: the positive pointers (int32 [n]), advanced in place; default a copy of arrays['ptr'].  Returns dict(anchors, exclude, query
     [B]; runs [Q] and offsets [Q+1] with repeated_queries; n_padded) -- the arrays the kernel writes, bit for bit.
     hard (a HardNegatives, or its (idx, cnt) as arrays) with hard_slots in [0, k]: the restatement of txe_sample_anchors_hard, in
     integers like the rest: query i = order[s] has c = min(max(cnt[i], 0), H) entries, m = min(hard_slots, c) hard slots and the rotation
     r = (hi32(h) c) >> 32, h = mix64(seed ^ mix64(ctr(epoch, s, HARD_ROT_SLOT, 0))); slot j < m is idx[i, (r + j) % c] unless that entry
-    is masked for the query, negative or above the largest pool id -- then, and for j >= m, the slot is the pool draw it is without a table."""
+    is masked for the query, negative or above the largest pool id -- then, and for j >= m, the slot is the pool draw it is without a table.
+    near = (n_s, n_g, n_u) with taxonomy = near_arrays(dataset) (the masked graph's host CSR): the restatement of txe_sample_anchors_near.
+    With p the query's positive and h0 = hard_slots (0 without a table), sibling slots are j in [h0, h0 + n_s), grandparent slots the next
+    n_g, uncle slots the next n_u, over the lists near_lists(taxonomy, p) = (S, G, U).  Class X (t_X = 1, 2, 3; list length n_X, c_X slots)
+    has m_X = min(c_X, n_X) and one rotation r_X = (hi32(h) n_X) >> 32, h = mix64(seed ^ mix64(ctr(epoch, s, HARD_ROT_SLOT, t_X))); the
+    slot at class offset e < m_X proposes L_X[(r_X + e) % n_X], kept iff it is in [0, n_nodes), a pool node and not in q's mask row -- a
+    refused proposal, and every class slot e >= m_X, is the pool draw of its own j.  near None or (0, 0, 0) changes nothing but the new key:
+    the dict gains n_near = [accepted sibling, grandparent, uncle proposals] when `near` is given.  ValueError: counts that are not
+    integers >= 0, h0 + n_s + n_g + n_u > k, nonzero counts without a taxonomy."""
     k = arrays["k"]
     if hard is not None and not 0 <= int(hard_slots) <= k:
         raise ValueError(f"hard_slots must be in [0, {k}], got {hard_slots}")
+    h0 = int(hard_slots) if hard is not None else 0
+    counts = _checked_near(near, k, h0, "host_draw: near")
+    if any(counts) and taxonomy is None:
+        raise ValueError("host_draw: near slots need taxonomy=near_arrays(dataset)")
     pool, mask_ptr, mask_idx = arrays["pool"], arrays["mask_ptr"], arrays["mask_idx"]
     ptr = arrays["ptr"].copy() if ptr is None else ptr
     s = np.arange(start, start + Q, dtype=np.int64)
@@ -111,7 +175,7 @@ def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=F
             hr = _mix64(np.uint64(seed) ^ _mix64(_ctr(epoch, s, HARD_ROT_SLOT, 0)))
             rot = (((hr >> np.uint64(32)) * cnt.astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
     neg = np.empty((Q, k), dtype=np.int64)
-    n_padded = 0
+    n_padded, n_near = 0, [0, 0, 0]
     for i, v in enumerate(q):
         row = mask_idx[mask_ptr[v]:mask_ptr[v + 1]]
         ok = ~np.isin(draws[i], row)
@@ -123,12 +187,29 @@ def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=F
                 e = int(hidx[rows[i], (rot[i] + j) % cnt[i]])
                 if 0 <= e <= int(pool[-1]) and e not in row:       # else: the pool route, as without a table
                     neg[i, j], padded[j] = e, False
+        if any(counts):
+            at = h0
+            for x, (c, L) in enumerate(zip(counts, near_lists(taxonomy, pos[i]))):
+                n = len(L)
+                if min(c, n) > 0:
+                    with np.errstate(over="ignore"):
+                        hx = _mix64(np.uint64(seed) ^ _mix64(_ctr(epoch, s[i], HARD_ROT_SLOT, 1 + x)))
+                    r_x = (int(hx) >> 32) * n >> 32
+                    for e in range(min(c, n)):
+                        a = int(L[(r_x + e) % n])
+                        hit = np.searchsorted(pool, a) if 0 <= a < int(taxonomy["n_nodes"]) else len(pool)
+                        if hit < len(pool) and int(pool[hit]) == a and a not in row:      # else: the pool route of slot at + e
+                            neg[i, at + e], padded[at + e] = a, False
+                            n_near[x] += 1
+                at += c
         n_padded += int(padded.sum())
     anchors = np.concatenate([pos[:, None], neg], 1).reshape(-1)
     exclude = np.concatenate([q[:, None], np.full((Q, k), -1, dtype=np.int64)], 1).reshape(-1)
     out = dict(anchors=anchors, exclude=exclude, query=np.repeat(q, 1 + k), n_padded=n_padded)
     if repeated_queries:
         out["runs"], out["offsets"] = q, np.arange(Q + 1, dtype=np.int64) * (1 + k)
+    if near is not None:
+        out["n_near"] = n_near
     return out
 
 
@@ -280,7 +361,9 @@ def mine_hard_negatives(model, dataset, device, size, qblock=None, seed=0, batch
 class DeviceAnchorSampler:
     """sampler_arrays(dataset) resident on `device`, with the positive pointers (from node2positive_pointer when made; device sampling
     does NOT advance the host dict) and a padded-slot counter.  begin() launches the sampler and the egonet node count on one stream.
-    set_hard_negatives(table, slots): launch() / begin() then call txe_sample_anchors_hard; without a table they call txe_sample_anchors."""
+    set_hard_negatives(table, slots): launch() / begin() then call txe_sample_anchors_hard; without a table they call txe_sample_anchors.
+    set_near_negatives(siblings, grandparents, uncles): with a nonzero count they call txe_sample_anchors_near (table or not), which
+    reads self.dtax's CSR and adds to the counters near_counts() returns; with all counts 0 (the default) nothing changes."""
 
     def __init__(self, dataset, device, seed=0, dtax=None):
         _check(dataset)
@@ -291,6 +374,7 @@ class DeviceAnchorSampler:
         self.arrays = {name: up(v) for name, v in a.items() if name != "k"}
         self._padded = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.dtax = dtax if dtax is not None else dataset.device_taxonomy(self.device)
+        self._near = torch.zeros(3, dtype=torch.int32, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()     # resident before a side stream reads them
 
     def upload_order(self, order, stream=None):
@@ -302,6 +386,17 @@ class DeviceAnchorSampler:
             return torch.from_numpy(o.astype(np.int32)).to(self.device)
 
     hard, hard_slots, in_epoch = None, 0, False
+    near = (0, 0, 0)                                             # (sibling, grandparent, uncle) slots; all 0: the entries of old
+
+    def set_near_negatives(self, siblings=0, grandparents=0, uncles=0):
+        """from the next launch on, the `siblings` negative slots behind the hard slots propose a child of the query's positive, the
+        next `grandparents` a parent of it and the next `uncles` a child of one of its parents (txe_sample_anchors_near; a proposal that
+        is masked, outside the pool or absent leaves its slot to the pool draw).  All 0: launch() calls the entry it called before.
+        ValueError: a count that is not an integer >= 0 (bools and floats included), or hard_slots + the three counts above k.
+        RuntimeError while a loader iterates an epoch over this sampler: it takes effect between epochs only."""
+        if self.in_epoch:
+            raise RuntimeError("set_near_negatives while an epoch is being iterated: it takes effect between epochs only")
+        self.near = _checked_near((siblings, grandparents, uncles), self.k, self.hard_slots)
 
     def set_hard_negatives(self, table, slots=0):
         """from the next launch on, the first `slots` negative slots of a query come from `table` (a HardNegatives on this device; None:
@@ -314,6 +409,7 @@ class DeviceAnchorSampler:
         if isinstance(slots, bool) or int(slots) != slots or not 0 <= int(slots) <= self.k:
             raise ValueError(f"hard slots must be in [0, negative_size = {self.k}], got {slots!r}")
         if table is not None:
+            _checked_near(self.near, self.k, int(slots))         # (the near slots sit behind the hard ones: the same sum)
             if not isinstance(table, HardNegatives):
                 raise ValueError(f"set_hard_negatives takes a sampler.HardNegatives or None, got {type(table).__name__}")
             if table.n_queries != self.n_queries:
@@ -334,7 +430,14 @@ class DeviceAnchorSampler:
             args = (_lib.ptr(order_dev), int(order_dev.numel()), int(start), int(Q), _lib.ptr(a["node_list"]), _lib.ptr(a["par_ptr"]),
                     _lib.ptr(a["par_idx"]), _lib.ptr(a["mask_ptr"]), _lib.ptr(a["mask_idx"]), _lib.ptr(a["pool"]), self.n_pool,
                     _lib.ptr(a["ptr"]), self.k, self.seed, int(epoch), int(bool(repeated_queries)), _lib.ptr(packed), _lib.ptr(self._padded))
-            if self.hard is None:
+            if any(self.near):
+                t = self.dtax
+                hard = (_lib.ptr(self.hard.idx), _lib.ptr(self.hard.cnt), self.hard.H, self.hard_slots) if self.hard is not None else \
+                    (None, None, 0, 0)
+                _lib.call("txe_sample_anchors_near", *args, *hard, _lib.ptr(t.par_ptr), _lib.ptr(t.par_idx), _lib.ptr(t.chd_ptr),
+                          _lib.ptr(t.chd_idx), int(t.par_ptr.numel()) - 1, int(a["par_idx"].numel()), int(t.par_idx.numel()),
+                          int(t.chd_idx.numel()), *self.near, _lib.ptr(self._near), _lib.stream_ptr())
+            elif self.hard is None:
                 _lib.call("txe_sample_anchors", *args, _lib.stream_ptr())
             else:
                 _lib.call("txe_sample_anchors_hard", *args, _lib.ptr(self.hard.idx), _lib.ptr(self.hard.cnt), self.hard.H, self.hard_slots,
@@ -357,6 +460,11 @@ class DeviceAnchorSampler:
         """negative slots that kept a masked draw since the sampler was made (synchronises the device)"""
         torch.cuda.synchronize(self.device)
         return int(self._padded.item())
+
+    def near_counts(self):
+        """accepted (sibling, grandparent, uncle) proposals since the sampler was made (synchronises the device)"""
+        torch.cuda.synchronize(self.device)
+        return tuple(int(v) for v in self._near.cpu().tolist())
 
     def pointers(self):
         """the positive pointers (int32 numpy [n_nodes]) after every launch so far (synchronises the device)"""

@@ -14,6 +14,7 @@ _resume_checkpoint (base/base_trainer.py:59-176) -- in the style of evaluate.val
     host_step_log the numpy restatement of txe_step_log (its written definition; the CPU tests use it)
 """
 import inspect
+import logging
 import math
 import os
 import warnings
@@ -62,14 +63,16 @@ class StepLog:
         if self.device.type != "cuda":
             raise RuntimeError("taxoexpan_amd.trainer.StepLog lives on the GPU (no CPU path; host_step_log is the restatement)")
         # one fp64 buffer, so that read() is ONE copy: [acc (2) | first_bad (1, as int64) | gnorm2 (capacity) | loss (capacity fp32) |
-        # counter (1, as int64)]
+        # counter (1, as int64) | extra (2, as 4 int32)]
         c = self.capacity
-        self._buf = torch.zeros(4 + c + (c + 1) // 2, dtype=torch.float64, device=self.device)
+        self._buf = torch.zeros(6 + c + (c + 1) // 2, dtype=torch.float64, device=self.device)
         self._acc, self._first_bad = self._buf[0:2], self._buf[2:3].view(torch.int64)
         self._gnorm2, self._loss = self._buf[3:3 + c], self._buf[3 + c:].view(torch.float32)[:c]
         # an int64 word the log itself never writes: a loss may add to it on the device (loss.in_batch_info_nce's valid_total); it comes
         # back with read() and is cleared by reset()
-        self.counter = self._buf[-1:].view(torch.int64)
+        self.counter = self._buf[-3:-2].view(torch.int64)
+        # four int32 words of the same kind: train_epoch copies the sampler's near-negative counters of the epoch into them
+        self.extra = self._buf[-2:].view(torch.int32)
         self._first_bad.fill_(-1)
         self._ws, self._ws_bytes = None, 0
         self._table = None
@@ -128,11 +131,13 @@ class StepLog:
                          first_bad=self._first_bad.data_ptr() if first_bad else None, keep=(self._buf,))
 
     def read(self):
-        """the epoch's one read-back: dict(loss fp32 [n], grad_norm fp64 [n], loss_sum, n_steps, first_nonfinite (-1: none), counter)"""
+        """the epoch's one read-back: dict(loss fp32 [n], grad_norm fp64 [n], loss_sum, n_steps, first_nonfinite (-1: none), counter,
+        extra int32 [4])"""
         host = self._buf.cpu().numpy()
         c, n = self.capacity, self.n_recorded
         return dict(loss=host[3 + c:].view(np.float32)[:n].copy(), grad_norm=np.sqrt(host[3:3 + n]), loss_sum=float(host[0]),
-                    n_steps=int(host[1]), first_nonfinite=int(host[2:3].view(np.int64)[0]), counter=int(host[-1:].view(np.int64)[0]))
+                    n_steps=int(host[1]), first_nonfinite=int(host[2:3].view(np.int64)[0]), counter=int(host[-3:-2].view(np.int64)[0]),
+                    extra=host[-2:].view(np.int32).copy())
 
     def reset(self):
         """clear the log for the next epoch"""
@@ -198,7 +203,12 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
     ValueError before the first optimizer step: together with in_batch=True (margins inside the in-batch loss are out of scope) or with
     a loss_fn, a loader that does not attach g.anchors (DeviceBatchLoader(sampler="device", attach_anchors=True)), a gamma that is not
     finite or negative, an index whose n_nodes differs from the dataset's.  The dict gains mean_taxo_distance = the mean of 1 - Wu &
-    Palmer over the epoch's negatives, in steps of 2^-20: the log's int64 counter word / 2^20 / (groups * negatives per group)."""
+    Palmer over the epoch's negatives, in steps of 2^-20: the log's int64 counter word / 2^20 / (groups * negatives per group).
+    Near negatives (an addition; a loader without near slots: the loop is launch for launch what it was, the dict has no new key): when
+    loader.sampler has near slots (DeviceBatchLoader(near_negatives=...) / set_near_negatives), the dict gains near_sibling_share,
+    near_grandparent_share and near_uncle_share = the class's accepted proposals / its requested slots over the epoch (0.0 for a class
+    without slots).  The sampler's three device counters are copied before the first batch and their growth is written into the log's
+    `extra` words behind the last step, so they come back in the log's one read-back."""
     taxo = taxo_margin is not None
     if taxo:
         from .loss import _checked_gamma
@@ -266,6 +276,12 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         if not isinstance(taxonomy_index, DeviceTaxonomyIndex):
             taxonomy_index = taxonomy_index.to(dev)
         n_negatives = 0
+    near_sampler = getattr(loader, "sampler", None)
+    near = tuple(getattr(near_sampler, "near", None) or (0, 0, 0))
+    if any(near) and hasattr(near_sampler, "_near"):                   # the counters as the epoch finds them (cumulative on the sampler)
+        near_before, near_queries = near_sampler._near.clone(), 0
+    else:
+        near = (0, 0, 0)
     model.train()                                                      # trainer.py:42
     n_batches = 0
     for batch in loader:
@@ -319,6 +335,10 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         if feature_table is not None:
             feature_table.step(guard=guard)
         n_batches += 1
+        if any(near):
+            near_queries += label.numel() // (1 + near_sampler.k)
+    if any(near):                                                      # (this stream waited for every sampler launch of the epoch)
+        log.extra[:3].copy_(near_sampler._near - near_before)
     rec = log.read()
     if freeze_on_nonfinite and rec["first_nonfinite"] >= 0:
         optimizer.discount_frozen_steps(n_batches - rec["first_nonfinite"])
@@ -330,6 +350,9 @@ def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None, log=Non
         out["mean_negatives"] = (rec["counter"] - n_queries) / n_queries if n_queries else float("nan")
     if taxo:
         out["mean_taxo_distance"] = rec["counter"] / DIST_SCALE / n_negatives if n_negatives else float("nan")
+    for name, slots, got in zip(("near_sibling_share", "near_grandparent_share", "near_uncle_share"), near, rec["extra"]):
+        if any(near):                                                  # (a class without slots: 0 of 0 requested, reported as 0.0)
+            out[name] = int(got) / (slots * near_queries) if slots * near_queries else 0.0
     return out
 
 
@@ -403,10 +426,30 @@ def _checked_hard_negatives(cfg, train_loader):
     return out
 
 
+def _checked_near_negatives(cfg, train_loader, hard):
+    """fit's near_negatives option as dict(siblings, grandparents, uncles, start), or None; ValueError for anything fit cannot run"""
+    if cfg is None:
+        return None
+    from .sampler import DeviceAnchorSampler, _checked_near
+    names = ("siblings", "grandparents", "uncles")
+    if not isinstance(cfg, dict) or not set(cfg) <= set(names) | {"start"}:
+        raise ValueError(f"near_negatives is None or dict(siblings=0, grandparents=0, uncles=0, start=0), got {cfg!r}")
+    if not (isinstance(getattr(train_loader, "sampler", None), DeviceAnchorSampler) and hasattr(train_loader, "set_near_negatives")):
+        raise ValueError("near_negatives needs a DeviceBatchLoader(sampler='device') over a sampling_mode 1 dataset (the host sampler and "
+                         "the sampling_mode 0 group sampler draw from the pool only)")
+    start = cfg.get("start", 0)
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
+        raise ValueError(f"near_negatives['start'] must be an integer >= 0, got {start!r}")
+    h0 = max(train_loader.sampler.hard_slots, hard["slots"] if hard is not None else 0)
+    counts = _checked_near(tuple(cfg.get(n, 0) for n in names), train_loader.sampler.k, h0, "near_negatives")
+    return dict(zip(names, counts), start=int(start))
+
+
 def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, monitor="min val_macro_mr", early_stop=math.inf,
         lr_scheduler=None, scheduler_metric=None, save_dir=None, save_period=1, resume=None, config=None, larger_is_better=True,
         loss_fn=None, group_size=None, train_epoch_fn=None, validate_fn=None, max_grad_norm=None, freeze_on_nonfinite=False,
-        hard_negatives=None, averaged=False, in_batch=False, feature_table=None, taxo_margin=None, taxonomy_index=None):
+        hard_negatives=None, averaged=False, in_batch=False, feature_table=None, taxo_margin=None, taxonomy_index=None,
+        near_negatives=None):
     """BaseTrainer.train (base_trainer.py:59-107) around trainer.py:79-94.  Per epoch (1-based): train_epoch, then evaluate.validate on
     `valid_loader` (None: no validation) with its values merged into the epoch's log as val_<metric name>; then
       - lr_scheduler: a ReduceLROnPlateau is stepped with the log's `scheduler_metric` (default: the monitored metric; the reference
@@ -458,12 +501,20 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
     taxo_margin / taxonomy_index (an addition; None: nothing changes) go to train_epoch (see there; passed only when taxo_margin is set):
     the epochs train with loss.taxo_info_nce and their logs gain mean_taxo_distance.  The index is built ONCE here, before the first
     epoch (TaxonomyIndex.from_dataset(train_loader.dataset).to(the model's device)), when none is given.  Validation and checkpoints
-    are unchanged: a run without the keyword loads them."""
+    are unchanged: a run without the keyword loads them.
+    near_negatives: None (nothing changes) or dict(siblings=0, grandparents=0, uncles=0, start=0): before the first epoch e >= start,
+    train_loader.set_near_negatives(siblings, grandparents, uncles) makes that many negative slots of every query (behind the hard slots)
+    propose a node of the positive's taxonomy neighbourhood; until then the loader draws what it drew.  Needs no model pass
+    and no table, so start = 0 (the first epoch) is allowed.  Checked before the first step (ValueError): the loader kind, integer
+    counts >= 0, start >= 0, no other key, hard slots (the loader's, or hard_negatives' slots) + the three counts <= negative_size.  The
+    logs of the epochs with near slots gain near_sibling_share, near_grandparent_share and near_uncle_share (train_epoch), and the
+    shares are logged at INFO level; no other key changes."""
     if averaged and not (hasattr(optimizer, "averaged_parameters") and any(g.get("ema_decay") is not None for g in optimizer.param_groups)):
         raise ValueError("fit(averaged=True) needs an optimizer with averaged_parameters() and an ema_decay in at least one parameter "
                          f"group (taxoexpan_amd.optim.Adam(ema_decay=...)); got {type(optimizer).__name__}")
     averaged = bool(averaged)
     hard = _checked_hard_negatives(hard_negatives, train_loader)
+    near = _checked_near_negatives(near_negatives, train_loader, hard)
     if train_epoch_fn is None:
         train_epoch_fn = train_epoch
     if validate_fn is None:
@@ -523,9 +574,15 @@ def fit(model, train_loader, valid_loader, optimizer, epochs, metrics=None, moni
                                         dtax=getattr(train_loader, "dtax", None))
             train_loader.set_hard_negatives(table, hard["slots"])
             mined = {"hard_mined": True, "hard_mean_count": float(table.cnt.double().mean().item())}
+        if near is not None and epoch >= near["start"]:
+            train_loader.set_near_negatives(near["siblings"], near["grandparents"], near["uncles"])
+            near = None                                                # (set once: the loader keeps the counts)
         result = train_epoch_fn(model, train_loader, optimizer, loss_fn=loss_fn, group_size=group_size, **guard_args)
         log = {"epoch": epoch}
         log.update(result)
+        if "near_sibling_share" in result:
+            logging.getLogger(__name__).info("epoch %d: near negatives accepted -- siblings %.3f, grandparents %.3f, uncles %.3f", epoch,
+                                             result["near_sibling_share"], result["near_grandparent_share"], result["near_uncle_share"])
         if mined is not None:
             log.update(mined)
         logs.append(log)

@@ -1,0 +1,297 @@
+"""CPU: near negatives' host side -- sampler.host_draw(near=..., taxonomy=sampler.near_arrays(dataset)) against the rule written out in
+near_negative_cases.py, the count checks of host_draw / set_near_negatives / the loader / fit, and the argument checks of
+txe_sample_anchors_near, which answer before any device work (include/txe.h)."""
+import ctypes
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import near_negative_cases as cases
+
+
+def _draws(ds, order, Q, epoch, seed, counts, **kw):
+    """(plain, near, arrays, taxonomy): host_draw without and with near slots for the first Q positions of `order`"""
+    from taxoexpan_amd.sampler import host_draw, near_arrays, sampler_arrays
+    a, tax = sampler_arrays(ds), near_arrays(ds)
+    p0, p1 = a["ptr"].copy(), a["ptr"].copy()
+    plain = host_draw(a, order, 0, Q, epoch, seed, ptr=p0, **kw)
+    near = host_draw(a, order, 0, Q, epoch, seed, ptr=p1, near=counts, taxonomy=tax, **kw)
+    assert np.array_equal(p0, p1)                                        # the pointers advance alike
+    return plain, near, a, tax
+
+
+def _random_table(ds, H, seed):
+    """a mined-style table: H distinct unmasked pool nodes per query from seeded scores"""
+    from taxoexpan_amd.evaluate import _retrieval_masks
+    from taxoexpan_amd.sampler import host_hard_table
+    pool = sorted(ds.all_positions)
+    off, idx = _retrieval_masks(ds, ds.node_list, {a: i for i, a in enumerate(pool)})
+    S = np.random.RandomState(seed).randn(len(ds.node_list), len(pool)).astype(np.float32)
+    return host_hard_table(S, pool, off, idx, H)
+
+
+def test_near_arrays_are_the_arrays_device_taxonomy_uploads(tmp_path):
+    from taxoexpan_amd.sampler import near_arrays
+    ds = cases.toy(tmp_path)
+    tax, dtax = near_arrays(ds), ds.device_taxonomy("cpu")
+    for f in ("par_ptr", "par_idx", "chd_ptr", "chd_idx"):
+        assert tax[f].dtype == np.int32 and np.array_equal(tax[f], getattr(dtax, f).numpy()), f
+    assert tax["n_nodes"] == ds.node_features.shape[0] == len(tax["par_ptr"]) - 1
+
+
+@pytest.mark.parametrize("with_table", [False, True])
+def test_zero_near_counts_change_nothing(tmp_path, with_table):
+    from taxoexpan_amd.sampler import host_draw, near_arrays, sampler_arrays
+    ds = cases.toy(tmp_path)
+    a, tax, n = sampler_arrays(ds), near_arrays(ds), len(ds)
+    order = cases.shuffled(n, 5)
+    kw = dict(hard=_random_table(ds, 6, 1), hard_slots=3) if with_table else {}
+    for repeated in (False, True):
+        old = host_draw(a, order, 3, 40, 2, 11, repeated_queries=repeated, **kw)
+        for near in (None, (0, 0, 0)):
+            new = host_draw(a, order, 3, 40, 2, 11, repeated_queries=repeated, near=near, taxonomy=tax, **kw)
+            assert set(new) - set(old) <= {"n_near"} and all(np.array_equal(old[f], new[f]) for f in old)
+            assert new.get("n_near", [0, 0, 0]) == [0, 0, 0] and ("n_near" in new) == (near is not None)
+        assert host_draw(a, order, 3, 40, 2, 11, repeated_queries=repeated, near=None, **kw).keys() == old.keys()
+
+
+@pytest.mark.parametrize("data", ["toy", "synthetic"])
+def test_near_slots_follow_the_rule_and_every_other_slot_is_unchanged(tmp_path, data):
+    """near = (2, 1, 2): positives, pointers, exclude, query ids and every slot outside [0, 5) equal the call without `near`; inside,
+    a slot is the literal rule's accepted proposal -- a member of its class list, a pool node, not masked -- or the plain draw, and n_near
+    counts the accepted ones per class.  Not vacuous on the synthetic set: at least half of the sibling and of the uncle slots are
+    accepted there (the issue's bound; 0.914 / 0.794 of its (query, parent) pairs have a usable sibling / uncle)."""
+    ds = (cases.toy if data == "toy" else cases.synthetic)(tmp_path)
+    n, k, counts = len(ds), 7, (2, 1, 2)
+    order = cases.shuffled(n, 1)
+    plain, near, a, _tax = _draws(ds, order, n, 1, 5, counts)
+    assert np.array_equal(near["exclude"], plain["exclude"]) and np.array_equal(near["query"], plain["query"])
+    g, p = near["anchors"].reshape(n, 1 + k), plain["anchors"].reshape(n, 1 + k)
+    assert np.array_equal(g[:, 0], p[:, 0]) and np.array_equal(g[:, 6:], p[:, 6:])
+    want = cases.literal_near(ds, order, 0, n, 1, 5, counts, p[:, 0])
+    pool = set(ds.all_positions)
+    got_counts = [0, 0, 0]
+    for i in range(n):
+        q = ds.node_list[order[i]]
+        lists = cases.class_lists(ds, int(p[i, 0]))
+        for j in range(5):
+            if (i, j) in want:
+                x, node = want[(i, j)]
+                assert g[i, 1 + j] == node and node in lists[x] and node in pool and node not in ds.node2masks[q]
+                got_counts[x] += 1
+            else:
+                assert g[i, 1 + j] == p[i, 1 + j]
+    assert near["n_near"] == got_counts and near["n_padded"] == plain["n_padded"] == 0
+    shares = [c / (n * s) for c, s in zip(got_counts, counts)]
+    print(data, "accepted shares (siblings, grandparents, uncles):", shares)
+    if data == "synthetic":
+        assert shares[0] >= 0.5 and shares[2] >= 0.5
+    else:
+        assert min(got_counts) > 0
+
+
+def test_near_slots_sit_behind_the_hard_slots(tmp_path):
+    """with a table and hard_slots = 3, near = (2, 1, 1), k = 15: slots [0, 3) are the table's, [3, 7) follow the rule from h0 = 3, the
+    rest is the plain draw; batches of any size draw what the whole epoch draws"""
+    from taxoexpan_amd.sampler import host_draw, near_arrays, sampler_arrays
+    ds = cases.toy(tmp_path, negative_size=15)
+    n, k, counts = len(ds), 15, (2, 1, 1)
+    hidx, hcnt = _random_table(ds, 8, 2)
+    order = cases.shuffled(n, 3)
+    plain, near, a, tax = _draws(ds, order, n, 2, 9, counts, hard=(hidx, hcnt), hard_slots=3)
+    bare = host_draw(a, order, 0, n, 2, 9)["anchors"].reshape(n, 1 + k)
+    g, p = near["anchors"].reshape(n, 1 + k), plain["anchors"].reshape(n, 1 + k)
+    assert np.array_equal(g[:, :4], p[:, :4]) and np.array_equal(g[:, 8:], bare[:, 8:])
+    want = cases.literal_near(ds, order, 0, n, 2, 9, counts, p[:, 0], h0=3)
+    assert want and all(3 <= j < 7 for _i, j in want)
+    for i in range(n):
+        for j in range(3, 7):
+            assert g[i, 1 + j] == (want[(i, j)][1] if (i, j) in want else bare[i, 1 + j])
+    assert near["n_near"] == [sum(x == c for x, _ in want.values()) for c in range(3)]
+    for bs in (16, 5):
+        ptr = a["ptr"].copy()
+        parts = [host_draw(a, order, s, min(bs, n - s), 2, 9, ptr=ptr, hard=(hidx, hcnt), hard_slots=3, near=counts, taxonomy=tax)
+                 for s in range(0, n, bs)]
+        assert np.array_equal(np.concatenate([x["anchors"] for x in parts]), near["anchors"])
+        assert [sum(x["n_near"][c] for x in parts) for c in range(3)] == near["n_near"]
+
+
+def test_hand_taxonomy_siblings_grandparent_and_rotation(tmp_path):
+    """0 -> 1 -> {2..9}, q = 2, p = 1: S = {2..9} holds q itself (masked), G = [0] is a root (masked), U = chd(0) = [1] is p (masked).
+    near = (5, 1, 1), k = 7: sibling slots hold nodes of {3..9} only, the grandparent and the uncle slot equal the plain draw, and over
+    8 epochs the 5-wide window visits all of {3..9} (a node is outside one epoch's window with probability 3/8: missed by all 8
+    rotations with probability 4e-4)."""
+    ds = cases.hand(tmp_path, k=7)
+    assert list(ds.graph.succ[1]) == list(range(2, 10)) and list(ds.graph.pred[1]) == [0] and {0, 1, 2} <= set(ds.node2masks[2])
+    n = len(ds)
+    order = list(range(n))
+    at = [ds.node_list[i] for i in order].index(2)
+    seen = set()
+    for epoch in range(8):
+        plain, near, _a, _tax = _draws(ds, order, n, epoch, 4, (5, 1, 1))
+        g, p = near["anchors"].reshape(n, 8)[at], plain["anchors"].reshape(n, 8)[at]
+        assert g[0] == p[0] == 1 and set(g[1:6].tolist()) <= set(range(3, 10))
+        assert g[6] == p[6] and g[7] == p[7]                             # node 0 and node 1 are refused: the pool draws of slots 5, 6
+        want = cases.literal_near(ds, order, at, 1, epoch, 4, (5, 1, 1), [1])
+        assert 4 <= len(want) <= 5 and all(x == 0 for x, _ in want.values())
+        seen |= {node for _x, node in want.values()}
+        assert all(g[1 + j] == node for (_i, j), (_x, node) in want.items())
+    assert seen == set(range(3, 10))
+
+
+def test_uncles_of_a_node_with_two_parents_are_concatenated_in_parent_order(tmp_path):
+    from taxoexpan_amd.sampler import near_arrays, near_lists
+    ds = cases.toy(tmp_path)
+    tax = near_arrays(ds)
+    checked = 0
+    for q in ds.node_list:
+        for p in ds.node2parents[q]:
+            par = list(ds.graph.pred.get(p, ()))
+            if len(par) < 2:
+                continue
+            U = []
+            for g in par:                                                # the literal loop: parent after parent, child after child
+                for c in ds.graph.succ.get(g, ()):
+                    U.append(c)
+            S, G, got = near_lists(tax, p)
+            assert G.tolist() == par and got.tolist() == U and S.tolist() == list(ds.graph.succ.get(p, ()))
+            assert p in U and len(U) == sum(len(ds.graph.succ.get(g, ())) for g in par)
+            checked += 1
+    assert checked > 0
+
+
+def test_malformed_taxonomy_rows_are_empty(tmp_path):
+    """a child id of n_nodes, a child id of -1 and a row whose end lies before its start: no invalid id leaves host_draw, the affected
+    proposals take the pool route"""
+    from taxoexpan_amd.sampler import host_draw, near_arrays, sampler_arrays
+    ds = cases.toy(tmp_path)
+    a, n = sampler_arrays(ds), len(ds)
+    order = cases.shuffled(n, 2)
+    plain = host_draw(a, order, 0, n, 0, 3)["anchors"].reshape(n, 8)
+    good = near_arrays(ds)
+    for case in ("child_n", "child_neg", "end_before_start"):
+        tax = {f: (v.copy() if isinstance(v, np.ndarray) else v) for f, v in good.items()}
+        if case == "child_n":
+            tax["chd_idx"][:] = tax["n_nodes"]
+        elif case == "child_neg":
+            tax["chd_idx"][:] = -1
+        else:
+            tax["chd_ptr"] = tax["chd_ptr"][::-1].copy()                 # descending: no row ends behind its start
+        out = host_draw(a, order, 0, n, 0, 3, near=(2, 1, 2), taxonomy=tax)
+        g = out["anchors"].reshape(n, 8)
+        assert out["n_near"][0] == out["n_near"][2] == 0 and out["n_near"][1] > 0, case
+        assert np.array_equal(g[:, :3], plain[:, :3]) and np.array_equal(g[:, 4:], plain[:, 4:]) and set(g[:, 1:].ravel()) <= set(a["pool"])
+
+
+def _bare_sampler(k=7, n_queries=130):
+    """a DeviceAnchorSampler without its device arrays: what the setters read"""
+    from taxoexpan_amd.sampler import DeviceAnchorSampler
+    s = DeviceAnchorSampler.__new__(DeviceAnchorSampler)
+    s.k, s.n_queries, s.n_pool, s.device = k, n_queries, 134, torch.device("cpu")
+    return s
+
+
+BAD_COUNTS = [(-1, 0, 0), (0, -2, 0), (True, 0, 0), (0, False, 1), (1.0, 0, 0), (0, 0, 2.5), (3, 3, 2), (8, 0, 0)]
+
+
+def test_counts_are_checked_everywhere(tmp_path):
+    """a slot sum above k, negative counts, bools and floats raise ValueError in host_draw, the sampler, the loader and fit; the sum
+    includes the hard slots (set_hard_negatives checks the same sum); inside an epoch the setter raises RuntimeError"""
+    from taxoexpan_amd.data_loaders import DeviceBatchLoader
+    from taxoexpan_amd.sampler import DeviceGroupSampler, HardNegatives, host_draw, near_arrays, sampler_arrays
+    from taxoexpan_amd.trainer import fit
+    ds = cases.toy(tmp_path)
+    a, tax = sampler_arrays(ds), near_arrays(ds)
+    order = list(range(len(ds)))
+    s = _bare_sampler()
+    assert s.near == (0, 0, 0)
+    for bad in BAD_COUNTS:
+        with pytest.raises(ValueError):
+            host_draw(a, order, 0, 4, 0, 1, near=bad, taxonomy=tax)
+        with pytest.raises(ValueError):
+            s.set_near_negatives(*bad)
+    with pytest.raises(ValueError):
+        host_draw(a, order, 0, 4, 0, 1, near=(1, 0, 0))                      # near slots without a taxonomy
+    hidx, hcnt = _random_table(ds, 8, 0)
+    with pytest.raises(ValueError):
+        host_draw(a, order, 0, 4, 0, 1, hard=(hidx, hcnt), hard_slots=4, near=(2, 1, 1), taxonomy=tax)
+    assert s.near == (0, 0, 0)
+    s.set_near_negatives(2, 1, 2)
+    assert s.near == (2, 1, 2)
+    s.set_near_negatives(uncles=np.int64(7))
+    assert s.near == (0, 0, 7) and all(type(c) is int for c in s.near)
+    s.set_near_negatives(2, 1, 2)
+    t = HardNegatives.from_numpy(hidx, ds, "cpu")
+    s.set_hard_negatives(t, 2)
+    with pytest.raises(ValueError):
+        s.set_hard_negatives(t, 3)                                           # 3 + 5 > 7
+    with pytest.raises(ValueError):
+        s.set_near_negatives(3, 1, 2)                                        # 2 + 6 > 7
+    assert s.hard_slots == 2 and s.near == (2, 1, 2)
+    s.in_epoch = True
+    with pytest.raises(RuntimeError):
+        s.set_near_negatives(1, 0, 0)
+    assert s.near == (2, 1, 2)
+    # the loader: the host sampler and the sampling_mode 0 group sampler refuse, worded like the hard-negative refusal
+    for other in (None, DeviceGroupSampler.__new__(DeviceGroupSampler)):
+        loader = DeviceBatchLoader.__new__(DeviceBatchLoader)
+        loader.sampler = other
+        with pytest.raises(ValueError, match="near negatives need sampler='device' on a sampling_mode 1 dataset"):
+            loader.set_near_negatives(siblings=1)
+    loader = DeviceBatchLoader.__new__(DeviceBatchLoader)
+    loader.sampler = _bare_sampler()
+    loader.set_near_negatives(siblings=2, uncles=3)
+    assert loader.sampler.near == (2, 0, 3)
+    with pytest.raises(ValueError):                                          # refused at construction, before any device work
+        DeviceBatchLoader(ds, 16, "cpu", sampler="host", near_negatives=dict(siblings=1))
+    # fit: checked before the first step
+    model = torch.nn.Linear(3, 2)
+    opt = torch.optim.Adam(model.parameters(), lr=0.5)
+    calls, sets = [], []
+
+    def train_epoch(model, loader, optimizer, loss_fn=None, group_size=None):
+        calls.append(list(sets))
+        return dict(loss=1.0, n_batches=1, losses=np.ones(1, np.float32), grad_norms=np.ones(1), first_nonfinite=-1)
+    run = lambda loader, cfg, **kw: fit(model, loader, None, opt, 3, monitor="off", train_epoch_fn=train_epoch, near_negatives=cfg, **kw)
+    setter = lambda siblings=0, grandparents=0, uncles=0: sets.append((siblings, grandparents, uncles))
+    device_loader = types.SimpleNamespace(sampler=_bare_sampler(), set_near_negatives=setter, set_hard_negatives=lambda table, slots: None)
+    host_loader = types.SimpleNamespace(sampler=None, set_near_negatives=setter)
+    for loader, cfg in ([(host_loader, dict(siblings=1)), ([None], dict(siblings=1)), (device_loader, (2, 1, 2)),
+                         (device_loader, dict(siblings=1, cousins=1)), (device_loader, dict(siblings=1, start=-1)),
+                         (device_loader, dict(siblings=1, start=1.5))] +
+                        [(device_loader, dict(zip(("siblings", "grandparents", "uncles"), bad))) for bad in BAD_COUNTS]):
+        with pytest.raises(ValueError):
+            run(loader, cfg)
+    with pytest.raises(ValueError):                                          # the table's slots count towards the sum
+        run(device_loader, dict(siblings=3, uncles=3), hard_negatives=dict(size=8, slots=2))
+    assert not calls and not sets
+    assert len(run(device_loader, dict(siblings=2, grandparents=1, uncles=2, start=2))) == 3
+    assert calls == [[], [(2, 1, 2)], [(2, 1, 2)]]                           # set once, before epoch 2
+    assert len(run([None], None)) == 3                                       # None: today's behaviour, on any loader
+
+
+def test_near_entry_point_checks_its_arguments_without_a_gpu():
+    from taxoexpan_amd import _lib
+    lib = _lib.load()
+    assert "txe_sample_anchors_near" in _lib.SIGNATURES
+    buf = (ctypes.c_int * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, mask_ptr=p, mask_idx=p, pool=p, n_pool=3, pos_ptr=p,
+                k=7, seed=0, epoch=0, repeated=1, packed=p, n_padded=p, hard_idx=p, hard_cnt=p, H=4, hard_slots=1, tax_par_ptr=p,
+                tax_par_idx=p, tax_chd_ptr=p, tax_chd_idx=p, n_nodes=10, n_qpar=9, n_tax_par=9, n_tax_chd=9, n_sib=2, n_gpar=1, n_unc=2,
+                n_near=p, stream=None)
+    assert len(good) == len(_lib.SIGNATURES["txe_sample_anchors_near"][1])
+    call = lambda **kw: lib.txe_sample_anchors_near(*dict(good, **kw).values())
+    for name in ("order", "node_list", "par_ptr", "par_idx", "mask_ptr", "mask_idx", "pool", "pos_ptr", "packed", "n_padded", "hard_idx",
+                 "hard_cnt", "tax_par_ptr", "tax_par_idx", "tax_chd_ptr", "tax_chd_idx", "n_near"):
+        assert call(**{name: None}) == -1, name
+    for bad in (dict(H=0), dict(hard_slots=-1), dict(hard_slots=3), dict(n_sib=-1), dict(n_gpar=-1), dict(n_unc=-1), dict(n_sib=5),
+                dict(n_unc=4), dict(n_sib=1 << 30, n_gpar=1 << 30, n_unc=1 << 30), dict(n_nodes=0), dict(n_qpar=-1), dict(n_tax_par=-1),
+                dict(n_tax_chd=-1), dict(k=0), dict(k=1 << 14), dict(Q=-1), dict(n_pool=0), dict(start=-1), dict(start=3), dict(n_order=1),
+                dict(epoch=-1), dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25), dict(Q=1 << 20, n_order=1 << 20, k=1 << 11)):
+        assert call(**bad) == -1, bad
+    # nothing to launch: Q = 0 answers TXE_OK once the arguments are sound -- a table may be absent when no slot asks for it
+    assert call(Q=0) == 0 and call(Q=0, hard_idx=None, hard_cnt=None, H=0, hard_slots=0) == 0 and call(Q=0, n_sib=3) == 0
+    assert call(Q=0, hard_idx=None, hard_cnt=None, hard_slots=0, n_sib=0, n_gpar=0, n_unc=0) == 0
