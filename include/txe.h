@@ -669,63 +669,65 @@ int txe_egonet_fill(const int* par_ptr, const int* par_idx, const int* chd_ptr, 
                     const int* exclude, int G, int expand, unsigned long long seed, int index_base, const int* node_off, int* ids, int* pos,
                     int* rowptr_in, int* col_src, int* eid_in, int* rowptr_out, int* col_dst, int* pos_out, void* stream);
 
+/* ---- the samplers' arguments, grouped by what they are (txe_sample_anchors and txe_sample_groups read the first two): plain structs of
+ * borrowed device pointers and scalars; the caller keeps what they point to alive and may fill `source` once for all its launches. */
+struct txe_sample_source {     /* the resident arrays: node_list, the query-parent CSR (n_par_idx: the length of par_idx), the mask CSR (rows
+                                * sorted), the negative pool (ascending; n_pool entries) and k = negative_size */
+    const int *node_list, *par_ptr, *par_idx; int n_par_idx; const int *mask_ptr, *mask_idx, *pool; int n_pool, k;
+};
+struct txe_sample_span {       /* which queries -- positions start .. start+Q-1 of the epoch order (order [n_order]: indices into node_list) --
+                                * and the hash's inputs; repeated != 0: the run layout */
+    const int* order; int n_order, start, Q, epoch; unsigned long long seed; int repeated;
+};
+struct txe_sample_hard {       /* the mined table: idx [n_queries, H] int32, row i for node_list[i], node ids best first; cnt [n_queries] the
+                                * valid entries of each row; slots: the first negative slots of a query that come from its row */
+    const int *idx, *cnt; int H, slots;
+};
+struct txe_sample_near {       /* the MASKED taxonomy's parent and child CSR over n_nodes nodes (n_par / n_chd: the lengths of par_idx / chd_idx;
+                                * not the source's query-parent CSR), the sibling / grandparent / uncle slot counts, and counts [3] += the
+                                * accepted proposals of each class */
+    const int *par_ptr, *par_idx, *chd_ptr, *chd_idx; int n_nodes, n_par, n_chd, n_sib, n_gpar, n_unc; int* counts;
+};
+
 /* ---- training-anchor sampling on device, sampling_mode 1: data_loader/dataset.py:334-381 (one positive through the positive pointer,
- * exactly k negatives) for the Q queries at positions start .. start+Q-1 of the epoch order (order [n_order]: indices into node_list).
- * Writes the index arrays of txe_egonet_offsets / txe_egonet_fill in one launch, B = Q (1 + k), packed [4B + 1]:
+ * exactly k negatives) for the span's Q queries.  One launch of ONE kernel body, compiled three times; which one runs is decided by the
+ * pointers, not by the counts: near != NULL: near + optional table + pool (hard may be NULL: no table slots); else hard != NULL: table +
+ * pool; else the pool alone.  A slot no rule below claims, or whose proposal a rule refuses, is the same code in all three -- so a near
+ * launch with all counts 0 writes the table launch's bytes, and a table launch with slots = 0 or an all-empty table the pool launch's.
+ * Writes the index arrays of txe_egonet_offsets / txe_egonet_fill, B = Q (1 + k), packed [4B + 1]:
  *   [0, B) anchors (query i: its positive, then its k negatives) | [B, 2B) exclude (the query for the positive, -1 for negatives) |
  *   repeated == 0: [2B, 3B) the query id of every pair;  repeated != 0: [2B, 2B+Q) the distinct query ids, [3B, 3B+Q+1) run offsets i (1+k).
  * Positive: p = par_idx[par_ptr[q] + pos_ptr[q]], then pos_ptr[q] = (pos_ptr[q] + 1) % (parents of q) -- in place, the host walk exactly.
- * Negative slot j of epoch position s: attempt t = 0 .. 63 draws pool[(hi32(h) n_pool) >> 32], h = mix64(seed ^ mix64(epoch << 44 |
- * s << 20 | j << 6 | t)) (csrc/txe_common.h), accepted when not in q's sorted mask row mask_idx[mask_ptr[q] .. mask_ptr[q+1]); after 64
- * rejections the last draw stays and *n_padded is incremented (dataset.py:370-375 pads with nodes that may be masked).  A query must not
- * appear twice among launches in flight on different streams (the pointer update is not atomic).
- * TXE_ERR_ARG (before any device work): a NULL pointer, k < 1 or k >= 2^14, Q < 0, n_pool < 1, start < 0, start + Q > n_order or > 2^24,
- * epoch outside [0, 2^20), 4B + 1 >= 2^31. */
-int txe_sample_anchors(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
-                       const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k, unsigned long long seed,
-                       int epoch, int repeated, int* packed, int* n_padded, void* stream);
-
-/* ---- txe_sample_anchors with hard negatives: the first negative slots of a query come from a mined table, the rest from the pool.
- * hard_idx [n_queries, H] int32, row i for node_list[i] (i = order[s], the index the epoch order holds): node ids, best first;
- * hard_cnt [n_queries]: the valid entries of each row.  For the query at epoch position s, c = min(max(hard_cnt[i], 0), H),
- * m = min(hard_slots, c) and one rotation r = (hi32(h) c) >> 32, h = mix64(seed ^ mix64(epoch << 44 | s << 20 | 16383 << 6)) (slot
- * value 16383 is free: k < 2^14): negative slot j < m takes hard_idx[i H + (r + j) % c] without a rejection loop (a row's entries are
- * distinct), unless that entry is in q's mask row, negative or above pool[n_pool - 1] (pool must be ascending here) -- then, and for
- * every slot j >= m, the slot is txe_sample_anchors' slot j bit for bit: the same draws, tries and *n_padded accounting.  So
- * hard_slots = 0 or an all-empty table give txe_sample_anchors' output, and no table can put an invalid or masked id into a batch.
- * Mined negatives are plain negatives (exclude -1): the query can be in an anchor's egonet only when the anchor is the query, a parent
- * or a child of it, and all of those are masked.
- * TXE_ERR_ARG (before any device work): everything txe_sample_anchors refuses, a NULL hard_idx or hard_cnt, H < 1, hard_slots < 0 or
- * hard_slots > k. */
-int txe_sample_anchors_hard(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
-                            const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k,
-                            unsigned long long seed, int epoch, int repeated, int* packed, int* n_padded, const int* hard_idx,
-                            const int* hard_cnt, int H, int hard_slots, void* stream);
-
-/* ---- txe_sample_anchors_hard with near negatives: after the hard_slots table slots, n_sib / n_gpar / n_unc negative slots propose a node
- * of the positive's taxonomy neighbourhood.  tax_par_ptr / tax_par_idx / tax_chd_ptr / tax_chd_idx: the parent and child CSR of the
- * masked taxonomy over n_nodes nodes (n_tax_par / n_tax_chd: the lengths of the two index arrays; n_qpar: the length of par_idx, the
- * sampler's own query-parent index array).  With p the positive the pointer walk gives the query at epoch position s, the three lists are
- *   S = chd(p) (siblings);  G = par(p) (grandparents);  U = chd(g_0) ++ chd(g_1) ++ .. over g_i in par(p), in order (uncles; repeats stay).
- * Sibling slots are j in [hard_slots, hard_slots + n_sib), grandparent slots the next n_gpar, uncle slots the next n_unc.  Class X (list
- * length n_X, c_X slots, t_S, t_G, t_U = 1, 2, 3) has m_X = min(c_X, n_X) and one rotation r_X = (hi32(h) n_X) >> 32,
- * h = mix64(seed ^ mix64(epoch << 44 | s << 20 | 16383 << 6 | t_X)); the slot at class offset e < m_X proposes L_X[(r_X + e) % n_X] (an
- * uncle index walks par(p), subtracting child counts).  A proposal is kept iff it lies in [0, n_nodes), is a pool node (binary search;
- * pool must be ascending) and is not in q's mask row.  A refused proposal, every class slot e >= m_X and every slot outside the class
- * ranges is txe_sample_anchors' slot j bit for bit (slots below hard_slots: txe_sample_anchors_hard's): the same draws, tries and
- * *n_padded accounting; no rejection loop on the near side.  A row of the taxonomy CSR whose node is outside [0, n_nodes), whose start is
- * negative, whose end lies before its start or beyond its index array counts as empty; a positive read outside par_idx falls back to q.
- * So all three counts 0 give txe_sample_anchors_hard's output (txe_sample_anchors' when hard_slots = 0), and no taxonomy array can put an
- * invalid or masked id into a batch.  Near negatives are plain negatives (exclude -1), by the argument made for mined ones.
- * n_near [3] += the accepted sibling / grandparent / uncle proposals.  hard_idx / hard_cnt may be NULL when hard_slots == 0.
- * TXE_ERR_ARG (before any device work): everything txe_sample_anchors refuses; hard_slots < 0; hard_slots > 0 with a NULL hard_idx or
- * hard_cnt or H < 1; a NULL taxonomy pointer or n_near; n_nodes < 1; a negative length or count; hard_slots + n_sib + n_gpar + n_unc > k. */
-int txe_sample_anchors_near(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
-                            const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int* pos_ptr, int k,
-                            unsigned long long seed, int epoch, int repeated, int* packed, int* n_padded, const int* hard_idx,
-                            const int* hard_cnt, int H, int hard_slots, const int* tax_par_ptr, const int* tax_par_idx,
-                            const int* tax_chd_ptr, const int* tax_chd_idx, int n_nodes, int n_qpar, int n_tax_par, int n_tax_chd,
-                            int n_sib, int n_gpar, int n_unc, int* n_near, void* stream);
+ * A query-parent row that is empty, starts below 0 or ends beyond n_par_idx is not read: p = q and the pointer stays (all three
+ * instantiations; on arrays from sampler.sampler_arrays every row is sound).  A query must not appear twice among launches in flight on
+ * different streams (the pointer update is not atomic).
+ * The rules of negative slot j of the query at epoch position s (i = order[s], q = node_list[i]), in order:
+ *   1. table (hard != NULL, hard->slots > 0): c = min(max(cnt[i], 0), H), m = min(slots, c), one rotation r = (hi32(h) c) >> 32,
+ *      h = mix64(seed ^ mix64(epoch << 44 | s << 20 | 16383 << 6)) (slot value 16383 is free: k < 2^14).  Slot j < m takes
+ *      idx[i H + (r + j) % c] without a rejection loop (a row's entries are distinct), unless that entry is in q's mask row, negative or
+ *      above pool[n_pool - 1].
+ *   2. near (near != NULL): sibling slots are j in [slots, slots + n_sib) (slots = 0 without a table), grandparent slots the next n_gpar,
+ *      uncle slots the next n_unc.  The lists of the positive p:  S = chd(p);  G = par(p);  U = chd(g_0) ++ chd(g_1) ++ .. over g_i in
+ *      par(p), in order (repeats stay).  Class X (list length n_X, c_X slots, t_S, t_G, t_U = 1, 2, 3) has m_X = min(c_X, n_X) and one
+ *      rotation r_X = (hi32(h) n_X) >> 32, h = mix64(seed ^ mix64(epoch << 44 | s << 20 | 16383 << 6 | t_X)); the slot at class offset
+ *      e < m_X proposes L_X[(r_X + e) % n_X] (an uncle index walks par(p), subtracting child counts).  A proposal is kept iff it lies in
+ *      [0, n_nodes), is a pool node (binary search) and is not in q's mask row; counts[X] += the kept ones.  No rejection loop.  A row of
+ *      the taxonomy CSR whose node is outside [0, n_nodes), whose start is negative, whose end lies before its start or beyond its index
+ *      array counts as empty.
+ *   3. pool (every other slot, and every refused proposal): attempt t = 0 .. 63 draws pool[(hi32(h) n_pool) >> 32], h = mix64(seed ^
+ *      mix64(epoch << 44 | s << 20 | j << 6 | t)) (csrc/txe_common.h), accepted when not in q's sorted mask row
+ *      mask_idx[mask_ptr[q] .. mask_ptr[q+1]); after 64 rejections the last draw stays and *n_padded is incremented (dataset.py:370-375
+ *      pads with nodes that may be masked).
+ * So no table and no taxonomy array can put an invalid or masked id into a batch.  Mined and near negatives are plain negatives (exclude
+ * -1): the query can be in an anchor's egonet only when the anchor is the query, a parent or a child of it, and all of those are masked.
+ * TXE_ERR_ARG (before any device work): a NULL src, span or pointer in them, a NULL pos_ptr, packed or n_padded, k < 1 or k >= 2^14, Q < 0,
+ * n_pool < 1, n_par_idx < 0, n_order < 0, start < 0, start + Q > n_order or > 2^24, epoch outside [0, 2^20), 4B + 1 >= 2^31; with hard: a
+ * NULL idx or cnt, H < 1, slots outside [0, k]; with near: a NULL array or counts, n_nodes < 1, a negative length or count,
+ * slots + n_sib + n_gpar + n_unc > k.  The arguments are checked in order: span is not read unless src is sound.  Q == 0 with sound
+ * arguments: TXE_OK, no launch. */
+int txe_sample_anchors(const struct txe_sample_source* src, const struct txe_sample_span* span, int* pos_ptr, int* packed, int* n_padded,
+                       const struct txe_sample_hard* hard /* NULL: no table */, const struct txe_sample_near* near /* NULL: no near slots */,
+                       void* stream);
 
 /* ---- validation-anchor sampling on device, sampling_mode 0: data_loader/dataset.py:304-307,340-355 (every parent, then at most k
  * negatives) for the Q queries at positions start .. start+Q-1 of the epoch order.  Query i's run: node2parents[q] in order (label 1,
@@ -736,11 +738,10 @@ int txe_sample_anchors_near(const int* order, int n_order, int start, int Q, con
  * *total = B, packed [4B + 1] is laid out as txe_sample_anchors' (repeated: [3B, 3B+Q+1) the run offsets), labels [B] int64.
  * cap: the caller's capacity, >= sum of |parents| + Q k (packed holds 4 cap + 1 ints, labels cap); a B above it writes nothing but
  * *total.  ws: 3Q + 1 ints of scratch.  Three launches (count, scan, fill) on `stream`.
- * TXE_ERR_ARG (before any device work): a NULL pointer, k < 1 or k >= 2^14, Q < 0, n_pool < 1, start < 0, start + Q > n_order or > 2^24,
- * epoch outside [0, 2^20), cap < Q, 4 cap + 1 >= 2^31. */
-int txe_sample_groups(const int* order, int n_order, int start, int Q, const int* node_list, const int* par_ptr, const int* par_idx,
-                      const int* mask_ptr, const int* mask_idx, const int* pool, int n_pool, int k, unsigned long long seed, int epoch,
-                      int repeated, int cap, int* packed, long long* labels, int* total, int* ws, int* n_padded, void* stream);
+ * TXE_ERR_ARG (before any device work): what txe_sample_anchors refuses in src and span (one check serves both), a NULL packed, labels,
+ * total, ws or n_padded, cap < Q, 4 cap + 1 >= 2^31. */
+int txe_sample_groups(const struct txe_sample_source* src, const struct txe_sample_span* span, int cap, int* packed, long long* labels,
+                      int* total, int* ws, int* n_padded, void* stream);
 
 /* ---- grouped ranking of a labelled batch: model/metric.py:33-60 (obtain_ranks) on the device.  score [B] fp32, labels [B] int32
  * (label_bytes 4) or int64 (8).  Groups start at 0 and at every 0 -> 1 label transition; the rank of a positive (label 1) is 1 + the

@@ -145,10 +145,8 @@ SIGNATURES = {
     "txe_egonet_ws_bytes": (SZ, [I]),
     "txe_egonet_offsets": (I, [P, P, P, P, P, I, I, U64, I, P, P, SZ, P]),
     "txe_egonet_fill": (I, [P, P, P, P, P, P, I, I, U64, I, P, P, P, P, P, P, P, P, P, P]),
-    "txe_sample_anchors": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P]),
-    "txe_sample_anchors_hard": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P, P, I, I, P]),
-    "txe_sample_anchors_near": (I, [P, I, I, I, P, P, P, P, P, P, I, P, I, U64, I, I, P, P, P, P, I, I, P, P, P, P, I, I, I, I, I, I, I, P, P]),
-    "txe_sample_groups": (I, [P, I, I, I, P, P, P, P, P, P, I, I, U64, I, I, I, P, P, P, P, P, P]),
+    "txe_sample_anchors": (I, [P, P, P, P, P, P, P, P]),
+    "txe_sample_groups": (I, [P, P, I, P, P, P, P, P, P]),
     "txe_group_rank_ws_bytes": (SZ, [I]),
     "txe_group_rank": (I, [P, P, I, I, I, P, P, P, P, SZ, P]),
     "txe_group_metrics": (I, [P, P, P, U64, I, P, P]),
@@ -246,6 +244,28 @@ class GcnFoldLayer(C.Structure):
 class GcnFoldGrads(C.Structure):
     """struct txe_gcn_fold_grads"""
     _fields_ = [("dW", P), ("d_b", P), ("dP", P), ("d_pw", P)]
+
+
+class SampleSource(C.Structure):
+    """struct txe_sample_source"""
+    _fields_ = [("node_list", P), ("par_ptr", P), ("par_idx", P), ("n_par_idx", I), ("mask_ptr", P), ("mask_idx", P), ("pool", P),
+                ("n_pool", I), ("k", I)]
+
+
+class SampleSpan(C.Structure):
+    """struct txe_sample_span"""
+    _fields_ = [("order", P), ("n_order", I), ("start", I), ("Q", I), ("epoch", I), ("seed", U64), ("repeated", I)]
+
+
+class SampleHard(C.Structure):
+    """struct txe_sample_hard"""
+    _fields_ = [("idx", P), ("cnt", P), ("H", I), ("slots", I)]
+
+
+class SampleNear(C.Structure):
+    """struct txe_sample_near"""
+    _fields_ = [("par_ptr", P), ("par_idx", P), ("chd_ptr", P), ("chd_idx", P), ("n_nodes", I), ("n_par", I), ("n_chd", I), ("n_sib", I),
+                ("n_gpar", I), ("n_unc", I), ("counts", P)]
 
 
 def ref(desc):

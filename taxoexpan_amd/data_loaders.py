@@ -220,10 +220,10 @@ class DeviceBatchLoader:
     positives walk the same pointers as the host sampler, starting from the dataset's node2positive_pointer when the loader is made; the
     host dict is NOT advanced by device sampling.  Negatives follow the reference's distribution, not its `random` trace (sampler.py).
     hard_negatives / hard_slots (this sampler only; default off): a sampler.HardNegatives table whose rows fill the first hard_slots
-    negative slots of every query (txe_sample_anchors_hard); set_hard_negatives changes it between epochs.
+    negative slots of every query (txe_sample_anchors' table slots); set_hard_negatives changes it between epochs.
     near_negatives (this sampler only; default None: the loader launches what it launched): dict(siblings=, grandparents=, uncles=), the
     negative slots behind the hard ones that propose a node of the positive's taxonomy neighbourhood -- another child of it, a parent of
-    it, a child of one of its parents (txe_sample_anchors_near); a proposal that is masked, outside the pool or absent
+    it, a child of one of its parents (txe_sample_anchors' near slots); a proposal that is masked, outside the pool or absent
     leaves its slot to the pool draw.  set_near_negatives changes the counts between epochs; sampler.near_counts() reads the accepted
     proposals.  The packed layout is unchanged, so in_batch, attach_anchors, the feature table and the hard table compose.
     in_batch=True (this sampler, repeated_queries=True; ValueError otherwise): every batch's graph carries `g.in_batch`, a

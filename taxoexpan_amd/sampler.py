@@ -10,10 +10,10 @@ cache (dataset.py:390-400), which the device egonet builder never had either.
 
 Hard negatives (off by default): mine_hard_negatives ranks every pool node for every training query under the model as it stands
 (candidate encode, score blocks, ops.select_k with the query's masks) and keeps the best `size` per query in a HardNegatives table;
-txe_sample_anchors_hard then fills the first `hard_slots` negative slots of a query from its row (one rotation per query and epoch)
+txe_sample_anchors' table slots then fill the first `hard_slots` negative slots of a query from its row (one rotation per query and epoch)
 and the rest from the pool as before.  host_draw(hard=..., hard_slots=...) restates that draw, host_hard_table the table.
 
-Near negatives (off by default): txe_sample_anchors_near fills the slots behind the hard ones from the taxonomy neighbourhood of the
+Near negatives (off by default): txe_sample_anchors' near slots fill the slots behind the hard ones from the taxonomy neighbourhood of the
 query's positive -- its other children (siblings), its parents (grandparents), the children of its parents (uncles) -- read off the
 masked taxonomy's CSR that is resident anyway; no model pass, no table.  host_draw(near=..., taxonomy=near_arrays(dataset)) restates it."""
 import numpy as np
@@ -134,11 +134,11 @@ def host_draw(arrays, order, start, Q, epoch, seed, ptr=None, repeated_queries=F
     """numpy restatement of txe_sample_anchors for the Q queries at positions start .. start+Q-1 of `order` (indices into node_list).
     ptr: the positive pointers (int32 [n]), advanced in place; default a copy of arrays['ptr'].  Returns dict(anchors, exclude, query
     [B]; runs [Q] and offsets [Q+1] with repeated_queries; n_padded) -- the arrays the kernel writes, bit for bit.
-    hard (a HardNegatives, or its (idx, cnt) as arrays) with hard_slots in [0, k]: the restatement of txe_sample_anchors_hard, in
+    hard (a HardNegatives, or its (idx, cnt) as arrays) with hard_slots in [0, k]: the restatement of the table slots, in
     integers like the rest: query i = order[s] has c = min(max(cnt[i], 0), H) entries, m = min(hard_slots, c) hard slots and the rotation
     r = (hi32(h) c) >> 32, h = mix64(seed ^ mix64(ctr(epoch, s, HARD_ROT_SLOT, 0))); slot j < m is idx[i, (r + j) % c] unless that entry
     is masked for the query, negative or above the largest pool id -- then, and for j >= m, the slot is the pool draw it is without a table.
-    near = (n_s, n_g, n_u) with taxonomy = near_arrays(dataset) (the masked graph's host CSR): the restatement of txe_sample_anchors_near.
+    near = (n_s, n_g, n_u) with taxonomy = near_arrays(dataset) (the masked graph's host CSR): the restatement of the near slots.
     With p the query's positive and h0 = hard_slots (0 without a table), sibling slots are j in [h0, h0 + n_s), grandparent slots the next
     n_g, uncle slots the next n_u, over the lists near_lists(taxonomy, p) = (S, G, U).  Class X (t_X = 1, 2, 3; list length n_X, c_X slots)
     has m_X = min(c_X, n_X) and one rotation r_X = (hi32(h) n_X) >> 32, h = mix64(seed ^ mix64(ctr(epoch, s, HARD_ROT_SLOT, t_X))); the
@@ -358,12 +358,27 @@ def mine_hard_negatives(model, dataset, device, size, qblock=None, seed=0, batch
     return HardNegatives(idx, (sel >= 0).sum(1).to(torch.int32))
 
 
+def _source(arrays, k):
+    """struct txe_sample_source over the resident device tensors of `arrays` (the caller keeps them alive as long as the struct)"""
+    a = arrays
+    return _lib.SampleSource(node_list=_lib.ptr(a["node_list"]), par_ptr=_lib.ptr(a["par_ptr"]), par_idx=_lib.ptr(a["par_idx"]),
+                             n_par_idx=int(a["par_idx"].numel()), mask_ptr=_lib.ptr(a["mask_ptr"]), mask_idx=_lib.ptr(a["mask_idx"]),
+                             pool=_lib.ptr(a["pool"]), n_pool=int(a["pool"].numel()), k=int(k))
+
+
+def _span(order_dev, start, Q, epoch, seed, repeated_queries):
+    """struct txe_sample_span: the Q queries at positions start .. start+Q-1 of the uploaded epoch order, and the hash's inputs"""
+    return _lib.SampleSpan(order=_lib.ptr(order_dev), n_order=int(order_dev.numel()), start=int(start), Q=int(Q), epoch=int(epoch),
+                           seed=seed, repeated=int(bool(repeated_queries)))
+
+
 class DeviceAnchorSampler:
     """sampler_arrays(dataset) resident on `device`, with the positive pointers (from node2positive_pointer when made; device sampling
     does NOT advance the host dict) and a padded-slot counter.  begin() launches the sampler and the egonet node count on one stream.
-    set_hard_negatives(table, slots): launch() / begin() then call txe_sample_anchors_hard; without a table they call txe_sample_anchors.
-    set_near_negatives(siblings, grandparents, uncles): with a nonzero count they call txe_sample_anchors_near (table or not), which
-    reads self.dtax's CSR and adds to the counters near_counts() returns; with all counts 0 (the default) nothing changes."""
+    launch() / begin() call txe_sample_anchors; what they hand it decides the route.  set_hard_negatives(table, slots): table slots in
+    front of the pool slots; without a table the pool alone.  set_near_negatives(siblings, grandparents, uncles): with a nonzero count
+    near slots behind the table slots (table or not), which read self.dtax's CSR and add to the counters near_counts() returns; with all
+    counts 0 (the default) nothing changes."""
 
     def __init__(self, dataset, device, seed=0, dtax=None):
         _check(dataset)
@@ -372,6 +387,7 @@ class DeviceAnchorSampler:
         self.k, self.n_pool, self.n_queries = a["k"], len(a["pool"]), len(a["node_list"])
         up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
         self.arrays = {name: up(v) for name, v in a.items() if name != "k"}
+        self._src = _source(self.arrays, self.k)
         self._padded = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.dtax = dtax if dtax is not None else dataset.device_taxonomy(self.device)
         self._near = torch.zeros(3, dtype=torch.int32, device=self.device)
@@ -386,17 +402,24 @@ class DeviceAnchorSampler:
             return torch.from_numpy(o.astype(np.int32)).to(self.device)
 
     hard, hard_slots, in_epoch = None, 0, False
-    near = (0, 0, 0)                                             # (sibling, grandparent, uncle) slots; all 0: the entries of old
+    near = (0, 0, 0)                                             # (sibling, grandparent, uncle) slots; all 0: no near route
+    _hard_arg = _near_arg = None                                 # struct txe_sample_hard / txe_sample_near of the launches, or None
 
     def set_near_negatives(self, siblings=0, grandparents=0, uncles=0):
         """from the next launch on, the `siblings` negative slots behind the hard slots propose a child of the query's positive, the
-        next `grandparents` a parent of it and the next `uncles` a child of one of its parents (txe_sample_anchors_near; a proposal that
-        is masked, outside the pool or absent leaves its slot to the pool draw).  All 0: launch() calls the entry it called before.
+        next `grandparents` a parent of it and the next `uncles` a child of one of its parents (the near slots of txe_sample_anchors; a
+        proposal that is masked, outside the pool or absent leaves its slot to the pool draw).  All 0: launch() takes the route it took
+        before.
         ValueError: a count that is not an integer >= 0 (bools and floats included), or hard_slots + the three counts above k.
         RuntimeError while a loader iterates an epoch over this sampler: it takes effect between epochs only."""
         if self.in_epoch:
             raise RuntimeError("set_near_negatives while an epoch is being iterated: it takes effect between epochs only")
         self.near = _checked_near((siblings, grandparents, uncles), self.k, self.hard_slots)
+        t = self.dtax                                            # (resident as long as the sampler: the struct borrows its tensors)
+        self._near_arg = _lib.SampleNear(par_ptr=_lib.ptr(t.par_ptr), par_idx=_lib.ptr(t.par_idx), chd_ptr=_lib.ptr(t.chd_ptr),
+                                         chd_idx=_lib.ptr(t.chd_idx), n_nodes=int(t.par_ptr.numel()) - 1, n_par=int(t.par_idx.numel()),
+                                         n_chd=int(t.chd_idx.numel()), n_sib=self.near[0], n_gpar=self.near[1], n_unc=self.near[2],
+                                         counts=_lib.ptr(self._near)) if any(self.near) else None
 
     def set_hard_negatives(self, table, slots=0):
         """from the next launch on, the first `slots` negative slots of a query come from `table` (a HardNegatives on this device; None:
@@ -419,29 +442,18 @@ class DeviceAnchorSampler:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         self.hard, self.hard_slots = table, int(slots) if table is not None else 0
+        self._hard_arg = _lib.SampleHard(idx=_lib.ptr(table.idx), cnt=_lib.ptr(table.cnt), H=table.H, slots=self.hard_slots) \
+            if table is not None else None                       # (self.hard keeps the table's tensors alive)
 
     def launch(self, order_dev, start, Q, epoch, repeated_queries=True, stream=None):
-        """txe_sample_anchors (with a table set: txe_sample_anchors_hard) alone: the packed [4B + 1] int32 index arrays of the batch,
-        written on `stream` (default: current)"""
-        a = self.arrays
+        """txe_sample_anchors alone (the route: table slots with a table set, near slots with a nonzero near count): the packed [4B + 1]
+        int32 index arrays of the batch, written on `stream` (default: current)"""
         B = Q * (1 + self.k)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)), _lib.on_device(self.device):
             packed = torch.empty(4 * B + 1, dtype=torch.int32, device=self.device)
-            args = (_lib.ptr(order_dev), int(order_dev.numel()), int(start), int(Q), _lib.ptr(a["node_list"]), _lib.ptr(a["par_ptr"]),
-                    _lib.ptr(a["par_idx"]), _lib.ptr(a["mask_ptr"]), _lib.ptr(a["mask_idx"]), _lib.ptr(a["pool"]), self.n_pool,
-                    _lib.ptr(a["ptr"]), self.k, self.seed, int(epoch), int(bool(repeated_queries)), _lib.ptr(packed), _lib.ptr(self._padded))
-            if any(self.near):
-                t = self.dtax
-                hard = (_lib.ptr(self.hard.idx), _lib.ptr(self.hard.cnt), self.hard.H, self.hard_slots) if self.hard is not None else \
-                    (None, None, 0, 0)
-                _lib.call("txe_sample_anchors_near", *args, *hard, _lib.ptr(t.par_ptr), _lib.ptr(t.par_idx), _lib.ptr(t.chd_ptr),
-                          _lib.ptr(t.chd_idx), int(t.par_ptr.numel()) - 1, int(a["par_idx"].numel()), int(t.par_idx.numel()),
-                          int(t.chd_idx.numel()), *self.near, _lib.ptr(self._near), _lib.stream_ptr())
-            elif self.hard is None:
-                _lib.call("txe_sample_anchors", *args, _lib.stream_ptr())
-            else:
-                _lib.call("txe_sample_anchors_hard", *args, _lib.ptr(self.hard.idx), _lib.ptr(self.hard.cnt), self.hard.H, self.hard_slots,
-                          _lib.stream_ptr())
+            span = _span(order_dev, start, Q, epoch, self.seed, repeated_queries)
+            _lib.call("txe_sample_anchors", _lib.ref(self._src), _lib.ref(span), _lib.ptr(self.arrays["ptr"]), _lib.ptr(packed),
+                      _lib.ptr(self._padded), _lib.ref(self._hard_arg), _lib.ref(self._near_arg), _lib.stream_ptr())
         return packed
 
     def begin(self, order_dev, start, Q, epoch, repeated_queries=True, stream=None, egonet_seed=0):
@@ -638,6 +650,7 @@ class DeviceGroupSampler:
         self._n_par = np.diff(a["par_ptr"]).astype(np.int64)[a["node_list"].astype(np.int64)]      # |parents| per node_list entry
         up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
         self.arrays = {name: up(v) for name, v in a.items() if name != "k"}
+        self._src = _source(self.arrays, self.k)
         self._padded = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.dtax = dtax if dtax is not None else dataset.device_taxonomy(self.device)
         self._slots = []                                             # free pinned int32 read-back slots
@@ -661,16 +674,14 @@ class DeviceGroupSampler:
     def launch(self, order_dev, start, Q, epoch, repeated_queries=True, stream=None):
         """txe_sample_groups alone, on `stream` (default: current): dict(packed [4 cap + 1] int32, labels [cap] int64, total [1] int32
         (B, on the device), cap).  packed's layout uses the stride B: packed[:4B + 1] is what begin_device_batch would upload."""
-        a = self.arrays
         cap = self.capacity(order_dev.host_order, start, Q)
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)), _lib.on_device(self.device):
             packed = torch.empty(4 * cap + 1, dtype=torch.int32, device=self.device)
             labels = torch.empty(max(cap, 1), dtype=torch.int64, device=self.device)
             total = torch.empty(2 + 3 * Q, dtype=torch.int32, device=self.device)         # [B | pad | ws 3Q + 1 ... ]
-            _lib.call("txe_sample_groups", _lib.ptr(order_dev), int(order_dev.numel()), int(start), int(Q), _lib.ptr(a["node_list"]),
-                      _lib.ptr(a["par_ptr"]), _lib.ptr(a["par_idx"]), _lib.ptr(a["mask_ptr"]), _lib.ptr(a["mask_idx"]), _lib.ptr(a["pool"]),
-                      self.n_pool, self.k, self.seed, int(epoch), int(bool(repeated_queries)), cap, _lib.ptr(packed), _lib.ptr(labels),
-                      _lib.ptr(total), _lib.ptr(total[1:]), _lib.ptr(self._padded), _lib.stream_ptr())
+            span = _span(order_dev, start, Q, epoch, self.seed, repeated_queries)
+            _lib.call("txe_sample_groups", _lib.ref(self._src), _lib.ref(span), cap, _lib.ptr(packed), _lib.ptr(labels), _lib.ptr(total),
+                      _lib.ptr(total[1:]), _lib.ptr(self._padded), _lib.stream_ptr())
         return dict(packed=packed, labels=labels, total=total[:1], cap=cap, Q=Q)
 
     def sample(self, order_dev, start, Q, epoch, repeated_queries=True, stream=None):

@@ -50,6 +50,18 @@ def hand(tmp_path, k=5):
     return MaskedGraphDataset(MAGDataset("hand", str(d), raw=True), mode="train", sampling_mode=1, negative_size=k, expand_factor=4)
 
 
+# negative_size -> (table slots, near counts) of the lane-loop test: k = 1 (63 idle lanes beside the ballots), 64 (one full pass) and 65
+# (a second pass with one live lane).  k = 1 has room for one source at a time: its near launch comes without a table.
+LANE_LOOP_PLANS = {1: (1, (1, 0, 0)), 64: (3, (30, 1, 30)), 65: (3, (30, 2, 30))}
+
+
+def lane_loop_routes(k, table):
+    """the host_draw keywords of the three instantiations for negative_size k: pool; table + pool; near (+ table unless k = 1) + pool"""
+    slots, counts = LANE_LOOP_PLANS[k]
+    hard = dict(hard=table, hard_slots=slots)
+    return dict(pool={}, table=hard, near=dict(near=counts, **({} if k == 1 else hard)))
+
+
 def shuffled(n, seed):
     order = list(range(n))
     random.Random(seed).shuffle(order)

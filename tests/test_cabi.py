@@ -61,7 +61,7 @@ def test_ctypes_structures_mirror_the_header_structs():
     for obj in vars(_lib).values():
         if isinstance(obj, type) and issubclass(obj, ctypes.Structure) and obj is not ctypes.Structure:
             mirrors[re.match(r"struct (txe_\w+)", obj.__doc__).group(1)] = obj
-    assert set(mirrors) == set(structs) and len(structs) >= 9, set(mirrors) ^ set(structs)
+    assert set(mirrors) == set(structs) and len(structs) >= 13, set(mirrors) ^ set(structs)
     for name, fields in structs.items():
         assert [(f, CMAP[t]) for f, t in fields] == [(f, t) for f, t in mirrors[name]._fields_], name
     # (the parser itself: a pointer list, a scalar list and a two-word type)

@@ -101,12 +101,24 @@ def test_sample_anchors_entry_point_checks_its_arguments_without_a_gpu():
     lib = _lib.load()
     buf = (ctypes.c_int * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
-    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, mask_ptr=p, mask_idx=p, pool=p, n_pool=3, pos_ptr=p,
-                k=2, seed=0, epoch=0, repeated=1, packed=p, n_padded=p, stream=None)
-    call = lambda **kw: lib.txe_sample_anchors(*dict(good, **kw).values())
+    assert "txe_sample_anchors" in _lib.SIGNATURES and not [n for n in _lib.SIGNATURES if n.startswith("txe_sample_anchors_")]
+    assert all(issubclass(getattr(_lib, n), ctypes.Structure) for n in ("SampleSource", "SampleSpan", "SampleHard", "SampleNear"))
+    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, n_par_idx=9, mask_ptr=p, mask_idx=p, pool=p, n_pool=3,
+                pos_ptr=p, k=2, seed=0, epoch=0, repeated=1, packed=p, n_padded=p)
+    src_f, span_f = [f for f, _ in _lib.SampleSource._fields_], [f for f, _ in _lib.SampleSpan._fields_]
+    assert set(src_f) | set(span_f) | {"pos_ptr", "packed", "n_padded"} == set(good)
+
+    def call(**kw):                                              # every value addressed to the field (or plain argument) that carries it
+        v = dict(good, **kw)
+        src, span = _lib.SampleSource(**{f: v[f] for f in src_f}), _lib.SampleSpan(**{f: v[f] for f in span_f})
+        return lib.txe_sample_anchors(_lib.ref(src), _lib.ref(span), v["pos_ptr"], v["packed"], v["n_padded"], None, None, None)
     for name in ("order", "node_list", "par_ptr", "par_idx", "mask_ptr", "mask_idx", "pool", "pos_ptr", "packed", "n_padded"):
         assert call(**{name: None}) == -1, name
     for bad in (dict(k=0), dict(k=-3), dict(k=1 << 14), dict(Q=-1), dict(n_pool=0), dict(start=-1), dict(start=3), dict(n_order=1),
-                dict(epoch=-1), dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25), dict(Q=1 << 20, n_order=1 << 20, k=1 << 11)):
+                dict(epoch=-1), dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25), dict(Q=1 << 20, n_order=1 << 20, k=1 << 11),
+                dict(n_par_idx=-1)):
         assert call(**bad) == -1, bad
     assert call(Q=0) == 0                                        # nothing to launch
+    src, span = _lib.SampleSource(**{f: good[f] for f in src_f}), _lib.SampleSpan(**dict({f: good[f] for f in span_f}, Q=0))
+    assert lib.txe_sample_anchors(None, _lib.ref(span), p, p, p, None, None, None) == -1         # a NULL struct
+    assert lib.txe_sample_anchors(_lib.ref(src), None, p, p, p, None, None, None) == -1

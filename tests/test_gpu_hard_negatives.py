@@ -1,4 +1,4 @@
-"""GPU: hard-negative mining -- txe_sample_anchors_hard against sampler.host_draw bit for bit, mine_hard_negatives against
+"""GPU: hard-negative mining -- txe_sample_anchors' table instantiation against sampler.host_draw bit for bit, mine_hard_negatives against
 sampler.host_hard_table on the model's own score matrix, the loader's and fit's use of the table."""
 import os
 import random

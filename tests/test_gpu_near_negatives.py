@@ -1,5 +1,5 @@
-"""GPU: near negatives -- txe_sample_anchors_near against sampler.host_draw bit for bit, against the two older entry points where the rule
-says they agree, on malformed taxonomy arrays, and through DeviceBatchLoader / train_epoch."""
+"""GPU: near negatives -- txe_sample_anchors' near instantiation against sampler.host_draw bit for bit, against the pool and table
+instantiations where the rule says they agree, on malformed taxonomy arrays, and through DeviceBatchLoader / train_epoch."""
 import numpy as np
 import pytest
 import torch
@@ -50,19 +50,21 @@ def _random_table(ds, H, seed):
 
 
 def _call_near(sampler, order_dev, start, Q, epoch, repeated, counts, table=None, hard_slots=0, tax=None):
-    """txe_sample_anchors_near itself (DeviceAnchorSampler.launch calls it only with a nonzero count), over `tax` = dict of int32 device
-    tensors (par_ptr, par_idx, chd_ptr, chd_idx; default: the sampler's resident taxonomy)"""
+    """txe_sample_anchors with an explicit txe_sample_near -- the near instantiation whatever the counts (DeviceAnchorSampler.launch hands
+    one over only with a nonzero count) -- over `tax` = dict of int32 device tensors (par_ptr, par_idx, chd_ptr, chd_idx; default: the
+    sampler's resident taxonomy); table None: hard = NULL"""
     from taxoexpan_amd import _lib
-    a, t = sampler.arrays, sampler.dtax
+    from taxoexpan_amd.sampler import _span
+    t = sampler.dtax
     tax = tax or dict(par_ptr=t.par_ptr, par_idx=t.par_idx, chd_ptr=t.chd_ptr, chd_idx=t.chd_idx)
     packed = torch.empty(4 * Q * (1 + sampler.k) + 1, dtype=torch.int32, device=sampler.device)
-    hard = (_lib.ptr(table.idx), _lib.ptr(table.cnt), table.H, hard_slots) if table is not None else (None, None, 0, 0)
-    _lib.call("txe_sample_anchors_near", _lib.ptr(order_dev), int(order_dev.numel()), start, Q, _lib.ptr(a["node_list"]), _lib.ptr(a["par_ptr"]),
-              _lib.ptr(a["par_idx"]), _lib.ptr(a["mask_ptr"]), _lib.ptr(a["mask_idx"]), _lib.ptr(a["pool"]), sampler.n_pool, _lib.ptr(a["ptr"]),
-              sampler.k, sampler.seed, epoch, int(repeated), _lib.ptr(packed), _lib.ptr(sampler._padded), *hard, _lib.ptr(tax["par_ptr"]),
-              _lib.ptr(tax["par_idx"]), _lib.ptr(tax["chd_ptr"]), _lib.ptr(tax["chd_idx"]), int(tax["par_ptr"].numel()) - 1,
-              int(a["par_idx"].numel()), int(tax["par_idx"].numel()), int(tax["chd_idx"].numel()), *counts, _lib.ptr(sampler._near),
-              _lib.stream_ptr())
+    hard = _lib.SampleHard(idx=_lib.ptr(table.idx), cnt=_lib.ptr(table.cnt), H=table.H, slots=hard_slots) if table is not None else None
+    near = _lib.SampleNear(par_ptr=_lib.ptr(tax["par_ptr"]), par_idx=_lib.ptr(tax["par_idx"]), chd_ptr=_lib.ptr(tax["chd_ptr"]),
+                           chd_idx=_lib.ptr(tax["chd_idx"]), n_nodes=int(tax["par_ptr"].numel()) - 1, n_par=int(tax["par_idx"].numel()),
+                           n_chd=int(tax["chd_idx"].numel()), n_sib=counts[0], n_gpar=counts[1], n_unc=counts[2], counts=_lib.ptr(sampler._near))
+    span = _span(order_dev, start, Q, epoch, sampler.seed, repeated)
+    _lib.call("txe_sample_anchors", _lib.ref(sampler._src), _lib.ref(span), _lib.ptr(sampler.arrays["ptr"]), _lib.ptr(packed),
+              _lib.ptr(sampler._padded), _lib.ref(hard), _lib.ref(near), _lib.stream_ptr())
     return packed
 
 
@@ -105,8 +107,8 @@ def test_near_draw_is_bit_equal_to_host_draw_over_three_epochs(tmp_path, case):
 
 @pytest.mark.parametrize("k", [7, 70])
 def test_zero_counts_give_the_older_entries_bytes(tmp_path, k):
-    """all three counts 0 through txe_sample_anchors_near: txe_sample_anchors' bytes without a table (a NULL one), and
-    txe_sample_anchors_hard's with a mined-style table and hard_slots = 3; the near counters stay 0"""
+    """all three counts 0 through the near instantiation (an explicit txe_sample_near): the pool instantiation's bytes without a table
+    (hard = NULL), and the table instantiation's with a mined-style table and hard_slots = 3; the near counters stay 0"""
     from taxoexpan_amd.sampler import DeviceAnchorSampler, HardNegatives
     dev = _dev()
     ds = cases.toy(tmp_path, negative_size=k)
@@ -127,9 +129,45 @@ def test_zero_counts_give_the_older_entries_bytes(tmp_path, k):
     assert np.array_equal(new.pointers(), old.pointers()) and np.array_equal(new_hard.pointers(), old_hard.pointers())
 
 
+@pytest.mark.parametrize("k", list(cases.LANE_LOOP_PLANS))
+def test_every_lane_stays_in_the_slot_loop_through_the_ballots(tmp_path, k):
+    """negative_size 1, 64 and 65 (idle lanes beside one slot; one full pass; a second pass with one live lane) through all three
+    instantiations -- pool, table, near (cases.LANE_LOOP_PLANS) -- against host_draw over two epochs, each in both layouts, as one batch of
+    5 queries (a partly filled workgroup) and one batch of the rest: every array a launch writes, the pointers, padded() and near_counts()"""
+    from taxoexpan_amd.sampler import DeviceAnchorSampler, HardNegatives, host_draw, near_arrays, sampler_arrays
+    dev = _dev()
+    ds = cases.toy(tmp_path, negative_size=k)
+    a, tax, n = sampler_arrays(ds), near_arrays(ds), len(ds)
+    hidx, hcnt = _random_table(ds, 6, 1)
+    table = HardNegatives(torch.from_numpy(hidx).to(dev), torch.from_numpy(hcnt).to(dev))
+    for route, kw in cases.lane_loop_routes(k, (hidx, hcnt)).items():
+        sampler = DeviceAnchorSampler(ds, dev, seed=5)
+        if "hard" in kw:
+            sampler.set_hard_negatives(table, kw["hard_slots"])
+        if "near" in kw:
+            sampler.set_near_negatives(*kw["near"])
+        assert (sampler._hard_arg is not None, sampler._near_arg is not None) == ("hard" in kw, "near" in kw)      # the instantiation meant
+        hptr = a["ptr"].copy()
+        n_padded, n_near = 0, [0, 0, 0]
+        for epoch in range(2):
+            order = cases.shuffled(n, epoch)
+            order_dev = sampler.upload_order(order)
+            for repeated in (True, False):
+                for s, Q in ((0, 5), (5, n - 5)):
+                    got = _unpack(sampler.launch(order_dev, s, Q, epoch, repeated), Q, k, repeated)
+                    want = host_draw(a, order, s, Q, epoch, 5, ptr=hptr, repeated_queries=repeated, taxonomy=tax if "near" in kw else None, **kw)
+                    n_padded += want["n_padded"]
+                    n_near = [x + y for x, y in zip(n_near, want.get("n_near", [0, 0, 0]))]
+                    for f, v in got.items():
+                        assert np.array_equal(v, want[f]), (route, epoch, repeated, s, f)
+        assert sampler.padded() == n_padded and list(sampler.near_counts()) == n_near, route
+        assert np.array_equal(sampler.pointers(), hptr), route
+        assert (sum(n_near) > 0) == (route == "near")
+
+
 def test_near_slots_between_the_hard_slots_and_the_pool_slots(tmp_path):
-    """a table with hard_slots = 3, near = (2, 1, 1), k = 15: slots [0, 3) are txe_sample_anchors_hard's, slots at or above 7
-    txe_sample_anchors', every array is host_draw's, and two samplers made alike launch equal bytes"""
+    """a table with hard_slots = 3, near = (2, 1, 1), k = 15: slots [0, 3) are the table launch's, slots at or above 7
+    the pool launch's, every array is host_draw's, and two samplers made alike launch equal bytes"""
     from taxoexpan_amd.sampler import DeviceAnchorSampler, HardNegatives, host_draw, near_arrays, sampler_arrays
     dev = _dev()
     k, counts = 15, (2, 1, 1)

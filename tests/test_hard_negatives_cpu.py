@@ -1,6 +1,6 @@
 """CPU: hard-negative mining's host side -- the table's numpy restatement (sampler.host_hard_table), the draw's (sampler.host_draw with a
 table), the checks of HardNegatives.from_numpy / set_hard_negatives / fit(hard_negatives=...), and the argument checks of
-txe_sample_anchors_hard, which answer before any device work (include/txe.h)."""
+txe_sample_anchors with a txe_sample_hard, which answer before any device work (include/txe.h)."""
 import ctypes
 import os
 import random
@@ -236,17 +236,26 @@ def test_fit_checks_the_hard_negative_option_before_any_step():
 def test_hard_entry_point_checks_its_arguments_without_a_gpu():
     from taxoexpan_amd import _lib
     lib = _lib.load()
-    assert "txe_sample_anchors_hard" in _lib.SIGNATURES
+    assert "txe_sample_anchors" in _lib.SIGNATURES and "txe_sample_anchors_hard" not in _lib.SIGNATURES
+    assert all(issubclass(getattr(_lib, n), ctypes.Structure) for n in ("SampleSource", "SampleSpan", "SampleHard", "SampleNear"))
     buf = (ctypes.c_int * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
-    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, mask_ptr=p, mask_idx=p, pool=p, n_pool=3, pos_ptr=p,
-                k=2, seed=0, epoch=0, repeated=1, packed=p, n_padded=p, hard_idx=p, hard_cnt=p, H=4, hard_slots=1, stream=None)
-    call = lambda **kw: lib.txe_sample_anchors_hard(*dict(good, **kw).values())
+    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, n_par_idx=9, mask_ptr=p, mask_idx=p, pool=p, n_pool=3,
+                pos_ptr=p, k=2, seed=0, epoch=0, repeated=1, packed=p, n_padded=p, hard_idx=p, hard_cnt=p, H=4, hard_slots=1)
+    src_f, span_f = [f for f, _ in _lib.SampleSource._fields_], [f for f, _ in _lib.SampleSpan._fields_]
+    assert len(src_f) + len(span_f) + 7 == len(good)
+
+    def call(**kw):                                                          # the table form: a txe_sample_hard, no txe_sample_near
+        v = dict(good, **kw)
+        src, span = _lib.SampleSource(**{f: v[f] for f in src_f}), _lib.SampleSpan(**{f: v[f] for f in span_f})
+        hard = _lib.SampleHard(idx=v["hard_idx"], cnt=v["hard_cnt"], H=v["H"], slots=v["hard_slots"])
+        return lib.txe_sample_anchors(_lib.ref(src), _lib.ref(span), v["pos_ptr"], v["packed"], v["n_padded"], _lib.ref(hard), None, None)
     for name in ("order", "node_list", "par_ptr", "par_idx", "mask_ptr", "mask_idx", "pool", "pos_ptr", "packed", "n_padded", "hard_idx",
                  "hard_cnt"):
         assert call(**{name: None}) == -1, name
     for bad in (dict(H=0), dict(H=-2), dict(hard_slots=-1), dict(hard_slots=3),
                 dict(k=0), dict(k=-3), dict(k=1 << 14), dict(Q=-1), dict(n_pool=0), dict(start=-1), dict(start=3), dict(n_order=1),
-                dict(epoch=-1), dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25), dict(Q=1 << 20, n_order=1 << 20, k=1 << 11)):
+                dict(epoch=-1), dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25), dict(Q=1 << 20, n_order=1 << 20, k=1 << 11),
+                dict(n_par_idx=-1)):
         assert call(**bad) == -1, bad
     assert call(Q=0) == 0 and call(Q=0, hard_slots=2) == 0                   # nothing to launch

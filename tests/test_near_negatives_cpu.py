@@ -1,6 +1,6 @@
 """CPU: near negatives' host side -- sampler.host_draw(near=..., taxonomy=sampler.near_arrays(dataset)) against the rule written out in
 near_negative_cases.py, the count checks of host_draw / set_near_negatives / the loader / fit, and the argument checks of
-txe_sample_anchors_near, which answer before any device work (include/txe.h)."""
+txe_sample_anchors with a txe_sample_near, which answer before any device work (include/txe.h)."""
 import ctypes
 import types
 
@@ -185,11 +185,28 @@ def test_malformed_taxonomy_rows_are_empty(tmp_path):
         assert np.array_equal(g[:, :3], plain[:, :3]) and np.array_equal(g[:, 4:], plain[:, 4:]) and set(g[:, 1:].ravel()) <= set(a["pool"])
 
 
+@pytest.mark.parametrize("k", list(cases.LANE_LOOP_PLANS))
+def test_host_draw_accepts_the_lane_loop_plans(tmp_path, k):
+    """the slot plans of the GPU lane-loop test (negative_size 1, 64, 65 on the toy set) are plans host_draw takes: every route draws
+    n (1 + k) pairs, the table and the near slots are in use (they change anchors; the near route accepts proposals), nothing pads"""
+    from taxoexpan_amd.sampler import host_draw, near_arrays, sampler_arrays
+    ds = cases.toy(tmp_path, negative_size=k)
+    a, tax, n = sampler_arrays(ds), near_arrays(ds), len(ds)
+    order = cases.shuffled(n, 0)
+    out = {name: host_draw(a, order, 0, n, 0, 4, taxonomy=tax if "near" in kw else None, **kw)
+           for name, kw in cases.lane_loop_routes(k, _random_table(ds, 6, 1)).items()}
+    assert all(len(o["anchors"]) == n * (1 + k) and o["n_padded"] == 0 for o in out.values())
+    assert not np.array_equal(out["table"]["anchors"], out["pool"]["anchors"]) and sum(out["near"]["n_near"]) > 0
+    assert np.array_equal(out["near"]["exclude"], out["pool"]["exclude"])
+
+
 def _bare_sampler(k=7, n_queries=130):
     """a DeviceAnchorSampler without its device arrays: what the setters read"""
     from taxoexpan_amd.sampler import DeviceAnchorSampler
     s = DeviceAnchorSampler.__new__(DeviceAnchorSampler)
     s.k, s.n_queries, s.n_pool, s.device = k, n_queries, 134, torch.device("cpu")
+    z = torch.zeros(2, dtype=torch.int32)                                    # (the near struct borrows the taxonomy CSR and the counters)
+    s.dtax, s._near = types.SimpleNamespace(par_ptr=z, par_idx=z, chd_ptr=z, chd_idx=z), torch.zeros(3, dtype=torch.int32)
     return s
 
 
@@ -275,15 +292,29 @@ def test_counts_are_checked_everywhere(tmp_path):
 def test_near_entry_point_checks_its_arguments_without_a_gpu():
     from taxoexpan_amd import _lib
     lib = _lib.load()
-    assert "txe_sample_anchors_near" in _lib.SIGNATURES
+    assert "txe_sample_anchors" in _lib.SIGNATURES and "txe_sample_anchors_near" not in _lib.SIGNATURES
+    assert all(issubclass(getattr(_lib, n), ctypes.Structure) for n in ("SampleSource", "SampleSpan", "SampleHard", "SampleNear"))
     buf = (ctypes.c_int * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
+    # (the names of the positional form: n_qpar is src->n_par_idx, the tax_* / n_tax_* / n_near entries are the txe_sample_near fields)
     good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, mask_ptr=p, mask_idx=p, pool=p, n_pool=3, pos_ptr=p,
                 k=7, seed=0, epoch=0, repeated=1, packed=p, n_padded=p, hard_idx=p, hard_cnt=p, H=4, hard_slots=1, tax_par_ptr=p,
                 tax_par_idx=p, tax_chd_ptr=p, tax_chd_idx=p, n_nodes=10, n_qpar=9, n_tax_par=9, n_tax_chd=9, n_sib=2, n_gpar=1, n_unc=2,
-                n_near=p, stream=None)
-    assert len(good) == len(_lib.SIGNATURES["txe_sample_anchors_near"][1])
-    call = lambda **kw: lib.txe_sample_anchors_near(*dict(good, **kw).values())
+                n_near=p, no_table=False)
+    n_fields = sum(len(getattr(_lib, n)._fields_) for n in ("SampleSource", "SampleSpan", "SampleHard", "SampleNear"))
+    assert len(good) - 1 == n_fields + 3                                     # every field, and pos_ptr, packed, n_padded
+
+    def call(**kw):                                                          # no_table=True: hard = NULL
+        v = dict(good, **kw)
+        src = _lib.SampleSource(node_list=v["node_list"], par_ptr=v["par_ptr"], par_idx=v["par_idx"], n_par_idx=v["n_qpar"],
+                                mask_ptr=v["mask_ptr"], mask_idx=v["mask_idx"], pool=v["pool"], n_pool=v["n_pool"], k=v["k"])
+        span = _lib.SampleSpan(**{f: v[f] for f, _ in _lib.SampleSpan._fields_})
+        hard = None if v["no_table"] else _lib.SampleHard(idx=v["hard_idx"], cnt=v["hard_cnt"], H=v["H"], slots=v["hard_slots"])
+        near = _lib.SampleNear(par_ptr=v["tax_par_ptr"], par_idx=v["tax_par_idx"], chd_ptr=v["tax_chd_ptr"], chd_idx=v["tax_chd_idx"],
+                               n_nodes=v["n_nodes"], n_par=v["n_tax_par"], n_chd=v["n_tax_chd"], n_sib=v["n_sib"], n_gpar=v["n_gpar"],
+                               n_unc=v["n_unc"], counts=v["n_near"])
+        return lib.txe_sample_anchors(_lib.ref(src), _lib.ref(span), v["pos_ptr"], v["packed"], v["n_padded"], _lib.ref(hard), _lib.ref(near),
+                                      None)
     for name in ("order", "node_list", "par_ptr", "par_idx", "mask_ptr", "mask_idx", "pool", "pos_ptr", "packed", "n_padded", "hard_idx",
                  "hard_cnt", "tax_par_ptr", "tax_par_idx", "tax_chd_ptr", "tax_chd_idx", "n_near"):
         assert call(**{name: None}) == -1, name
@@ -292,6 +323,7 @@ def test_near_entry_point_checks_its_arguments_without_a_gpu():
                 dict(n_tax_chd=-1), dict(k=0), dict(k=1 << 14), dict(Q=-1), dict(n_pool=0), dict(start=-1), dict(start=3), dict(n_order=1),
                 dict(epoch=-1), dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25), dict(Q=1 << 20, n_order=1 << 20, k=1 << 11)):
         assert call(**bad) == -1, bad
-    # nothing to launch: Q = 0 answers TXE_OK once the arguments are sound -- a table may be absent when no slot asks for it
-    assert call(Q=0) == 0 and call(Q=0, hard_idx=None, hard_cnt=None, H=0, hard_slots=0) == 0 and call(Q=0, n_sib=3) == 0
-    assert call(Q=0, hard_idx=None, hard_cnt=None, hard_slots=0, n_sib=0, n_gpar=0, n_unc=0) == 0
+    # nothing to launch: Q = 0 answers TXE_OK once the arguments are sound -- the table is absent (hard = NULL) when no slot asks for it
+    assert call(Q=0) == 0 and call(Q=0, no_table=True) == 0 and call(Q=0, n_sib=3) == 0
+    assert call(Q=0, no_table=True, n_sib=0, n_gpar=0, n_unc=0) == 0
+    assert call(Q=0, n_sib=3, n_unc=3) == -1 and call(Q=0, no_table=True, n_sib=3, n_unc=3) == 0      # 1 + 7 > k; slots = 0 without a table

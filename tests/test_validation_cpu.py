@@ -165,15 +165,22 @@ def test_new_entry_points_check_their_arguments_without_a_gpu():
     lib = _lib.load()
     buf = (ctypes.c_int * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
-    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, mask_ptr=p, mask_idx=p, pool=p, n_pool=3, k=2, seed=0,
-                epoch=0, repeated=1, cap=8, packed=p, labels=p, total=p, ws=p, n_padded=p, stream=None)
-    call = lambda **kw: lib.txe_sample_groups(*dict(good, **kw).values())
+    good = dict(order=p, n_order=4, start=0, Q=2, node_list=p, par_ptr=p, par_idx=p, n_par_idx=9, mask_ptr=p, mask_idx=p, pool=p, n_pool=3,
+                k=2, seed=0, epoch=0, repeated=1, cap=8, packed=p, labels=p, total=p, ws=p, n_padded=p)
+    src_f, span_f = [f for f, _ in _lib.SampleSource._fields_], [f for f, _ in _lib.SampleSpan._fields_]
+    assert len(src_f) + len(span_f) + 6 == len(good)
+
+    def call(**kw):                                              # txe_sample_anchors' two structs, then the plain arguments
+        v = dict(good, **kw)
+        src, span = _lib.SampleSource(**{f: v[f] for f in src_f}), _lib.SampleSpan(**{f: v[f] for f in span_f})
+        return lib.txe_sample_groups(_lib.ref(src), _lib.ref(span), v["cap"], v["packed"], v["labels"], v["total"], v["ws"], v["n_padded"], None)
     for name in ("order", "node_list", "par_ptr", "par_idx", "mask_ptr", "mask_idx", "pool", "packed", "labels", "total", "ws", "n_padded"):
         assert call(**{name: None}) == -1, name
     for bad in (dict(k=0), dict(k=1 << 14), dict(Q=-1), dict(n_pool=0), dict(start=-1), dict(start=3), dict(n_order=1), dict(epoch=-1),
-                dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25, cap=1 << 25), dict(cap=1), dict(cap=1 << 29)):
+                dict(epoch=1 << 20), dict(Q=(1 << 24) + 1, n_order=1 << 25, cap=1 << 25), dict(cap=1), dict(cap=1 << 29), dict(n_par_idx=-1)):
         assert call(**bad) == -1, bad
     assert call(Q=0) == 0
+    assert lib.txe_sample_groups(None, None, 8, p, p, p, p, p, None) == -1                  # NULL structs
     ws = lib.txe_group_rank_ws_bytes(1000)
     assert ws > 1000 * 20 and lib.txe_group_rank_ws_bytes(0) == 0
     good = dict(score=p, labels=p, label_bytes=4, B=1000, mode=1, ranks=p, pos_off=p, counts=p, ws=p, ws_bytes=ws, stream=None)

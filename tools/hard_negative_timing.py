@@ -4,8 +4,8 @@ sampling_mode 1, 128 queries x (1 + 31) = 4,096 egonets per step, PGAT + Adam + 
 
   mining   sampler.mine_hard_negatives for all training queries x the pool at size 16 and 64, split into encode (candidate egonets +
            encoder), score (the matcher's block kernel) and select (ops.select_k with the masks); median of --reps runs after a warm-up
-  loop     wall ms per step of the DeviceBatchLoader(sampler="device") training loop without a table (txe_sample_anchors), with a table
-           and hard_slots = 0, and with hard_slots = negative_size // 2 (both txe_sample_anchors_hard), each with the egonet nodes and
+  loop     wall ms per step of the DeviceBatchLoader(sampler="device") training loop without a table (txe_sample_anchors, pool only), with a table
+           and hard_slots = 0, and with hard_slots = negative_size // 2 (both its table route), each with the egonet nodes and
            edges a step held; the table-free loop runs twice (first and last) -- the spread of the same code -- and the sampler launch
            alone is timed between HIP events
 

@@ -3,9 +3,9 @@
 sampling_mode 1, 128 queries x (1 + 31) = 4,096 egonets per step, PGAT + Adam + info_nce_loss).  Legs, alternating in ONE process for
 --rounds rounds (medians with ranges over the rounds):
 
-  no_near   the DeviceBatchLoader(sampler="device") training loop as it is: txe_sample_anchors
-  near_15   15 of the 31 negative slots near, split 8 siblings / 2 grandparents / 5 uncles: txe_sample_anchors_near
-  mined_15  (unless --no-mined) 15 slots from a table mined once at size 16 with the model as it stands: txe_sample_anchors_hard -- the
+  no_near   the DeviceBatchLoader(sampler="device") training loop as it is: txe_sample_anchors' pool instantiation
+  near_15   15 of the 31 negative slots near, split 8 siblings / 2 grandparents / 5 uncles: its near instantiation
+  mined_15  (unless --no-mined) 15 slots from a table mined once at size 16 with the model as it stands: its table instantiation -- the
             same number of model-ranked slots, for the comparison per step; the mining pass itself is timed once
 
 Each leg reports wall ms per step, the egonet nodes and edges a step held, the sampler launch alone between HIP events, and for near_15

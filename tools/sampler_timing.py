@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The training loop of INTEGRATION.md -- `for g, x, qf, label in DeviceBatchLoader(train, 128, ...)` -- on a MAG-CS-shaped masked dataset
 (synthetic.make_named_taxonomy("mag_cs") written as raw .terms / .taxo / .terms.embed files and read back; sampling_mode 1, 128 queries
-x (1 + 31) = 4,096 egonets per step), with the host sampler (dataset.sample_anchors) and with the device sampler (csrc/txe_sample.hip).
+x (1 + 31) = 4,096 egonets per step), with the host sampler (dataset.sample_anchors) and with the device sampler (csrc/txe_sample.hip:
+txe_sample_anchors without a table or near slots, its pool-only instantiation).
 Prints, per sampler: host ms spent in next(), wall ms per PGAT step (bench.make_model("pgat"), Adam, info_nce_loss); the sampler
 kernel's time from HIP events around single launches; the host time of next()'s two halves; and, for comparison, bench.py's
 resident-batch step and its fresh-batch loop (numpy sampler without masks, batch i+1 begun before step i) measured in the same process.
