@@ -289,7 +289,7 @@ __device__ __forceinline__ void stage_finish(const VMat& M, int row0, int k0, fl
 // address of pass p of a thread is  base + p * pass_stride,  and base moves by a uniform stride per tile: one 64-bit
 // pointer per operand lives in registers, no clamps, no selects, and nothing to do in the finish phase unless the
 // operand carries a dropout mask.
-template <bool KC, int ROWS>
+template <bool KC, int V, int ROWS>
 __device__ __forceinline__ bool block_is_plain(const VMat& M, int row0) {
     if constexpr (KC) {       // rows = the GEMM's m/n range of this workgroup: all from p or all from p3.  A ragged LAST panel is plain
                               // too: the passes past the operand re-read a valid row (fast_issue<..., CLAMP>), and the product rows /
@@ -299,8 +299,10 @@ __device__ __forceinline__ bool block_is_plain(const VMat& M, int row0) {
         const int rend = (row0 + ROWS < M.rows) ? row0 + ROWS : M.rows;
         return (row0 < M.rows) && ((rend <= M.rows_main) || (row0 >= M.rows_main));
     } else {                  // columns = the m/n range: inside the plain column range; for an operand without an extension a
-                              // ragged last tile is fine too (out-of-range column vectors are clamped and zeroed)
-        return (M.cols_main == M.cols) ? (row0 < M.cols) : (row0 + ROWS <= M.cols_main);
+                              // ragged last tile is fine too (column vectors past the operand are clamped, fast_finish) -- as long as
+                              // no vector STRADDLES the operand's edge: with cols % V != 0 (130 columns under 16-byte loads) the clamp
+                              // would hand the last valid columns the data of column 0; such a tile stays with the generic loader
+        return (M.cols_main == M.cols) ? (row0 < M.cols && (row0 + ROWS <= M.cols || M.cols % V == 0)) : (row0 + ROWS <= M.cols_main);
     }
 }
 
@@ -897,7 +899,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(VMat A, VMat B, c
     // leading k-tiles that are plain for BOTH operands.  The pipelined loop is split by the kind of the tile being
     // ISSUED (fast prefix, then generic tail) so that no branch sits between a load and its first use.
     int nkf = 0;
-    if (block_is_plain<AK, GEMM_BM>(A, m0) && block_is_plain<BKC, BN>(B, n0)) {
+    if (block_is_plain<AK, VA, GEMM_BM>(A, m0) && block_is_plain<BKC, VB, BN>(B, n0)) {
         const int full = (kend - kbeg) / GEMM_BK;     // complete k-tiles (a ragged last tile takes the generic path)
         const int fa_ = AK ? max(0, (A.cols_main - kbeg) / GEMM_BK) : min(full, max(0, (min(A.rows, A.rows_main) - kbeg) / GEMM_BK));
         const int fb_ = BKC ? max(0, (B.cols_main - kbeg) / GEMM_BK) : min(full, max(0, (min(B.rows, B.rows_main) - kbeg) / GEMM_BK));
@@ -1357,7 +1359,8 @@ static inline int gemm_launch_layout(const VMat& A, const VMat& B, const Epi& E_
     if (splits == 1 && tail_ws != nullptr && va == 4 && vb == 4 && N > 64 && !(E.route & GEMM_ROUTE_NO_PERSIST) && !E.mask_on && !E.act_on &&
         E.cnt_mode == EPI_STORE && (E.c2 == nullptr || E.cols_main >= N) && (K % GEMM_BK) == 0 && K >= 5 * GEMM_BK && K <= TXE_PERSIST_MAXK &&
         A.p2 == nullptr && B.p2 == nullptr && A.cols_main == A.cols && B.cols_main == B.cols && A.rows_main >= A.rows && B.rows_main >= B.rows &&
-        (AK ? A.cols : A.rows) >= K && (BKC ? B.cols : B.rows) >= K) {
+        (AK ? A.cols : A.rows) >= K && (BKC ? B.cols : B.rows) >= K &&
+        (AK || A.cols % 4 == 0) && (BKC || B.cols % 4 == 0)) {      // (its loader has no vector that straddles a row-contiguous operand's edge)
         const int slots = 2 * device_cu_count();
         const int nbm = (M + GEMM_BM - 1) / GEMM_BM, nbn = (N + 127) / 128;
         const int row_fast = (nbn > nbm) ? 1 : 0;

@@ -77,7 +77,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_lds_kernel(const TnLds p) {
             bp[q] += adv_b;                                                                                          \
         }                                                                                                            \
     }
-    /* the ragged last k-tile of a slice: rows at or past kend re-read row kend-1 (A's are zeroed afterwards) */
+    /* the ragged last k-tile of a slice: rows at or past kend re-read row kend-1 and are zeroed afterwards -- in BOTH operands: a zeroed A
+       row against B's re-read last row would be 0 x Inf = NaN where that row holds an infinity (gemm_kernel selects both to zero) */
 #define TXE_TL_ISSUE_LAST(st_, t_)                                                                                    \
     {                                                                                                                \
         lds_f* as = (lds_f*)(st_) + w * 4 * 256;                                                                     \
@@ -95,6 +96,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_lds_kernel(const TnLds p) {
     {                                                                                                                \
         const int valid = kend - (kbeg + (t_) * TL_BK);                                                              \
         for (int i = valid * TL_BM + threadIdx.x; i < TL_ASZ; i += 256) (st_)[i] = 0.f;                              \
+        for (int i = valid * TL_BN + threadIdx.x; i < TL_BSZ; i += 256) (st_)[TL_ASZ + i] = 0.f;                     \
     }
 #define TXE_TL_COMPUTE(st_)                                                                                           \
     {                                                                                                                \
